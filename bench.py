@@ -9,9 +9,14 @@ through the reference-shaped API (ControlLDM / Diffusion / SpacedSampler of edtr
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W          # one rank per GPU; batch axis sharded, no collective in the loop
 
-Rank 0 prints ONE JSON line.  Extra objects: "roofline" (dominant kernel = the MFMA implicit-GEMM, timed per launch
-with HIP events on the launch stream) and, at N=1, "cpu_baseline" (the CPU oracle timed on the host cores on a
-bounded sample of the same workload) plus "parity" (GPU vs oracle on that sample).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps passes and prints the headline.  With --full it
+also reports "roofline" (dominant kernel = the MFMA implicit-GEMM, timed per launch with HIP events on the launch stream),
+the reference-golden parity of one extra untimed pass, the other workloads and precision modes, and, at N=1,
+"cpu_baseline" (the CPU oracle timed on the host cores on a bounded sample of the same workload) plus "parity" (GPU vs
+oracle on that sample).
+
+    python bench.py --full --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR     # DIR/image.npy, DIR/latent.npy of the last timed pass
 """
 from __future__ import annotations
 
@@ -81,8 +86,17 @@ def main() -> None:
     ap.add_argument("--breakdown", action="store_true", help="print a per-kernel-name time table to stderr")
     ap.add_argument("--swinir", action="store_true",
                     help="also time the SwinIR pre-restoration in front of the path (excluded from the metric, SURVEY.md §8d) and "
-                         "report it separately as \"pre_restoration\" (the default run does: --also none skips it)")
+                         "report it separately as \"pre_restoration\" (the --full run does: --also none skips it)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else the benchmark measures or checks: the untimed golden-parity "
+                         "pass, roofline, CPU baseline, SwinIR, other workloads and parity modes (a plain run does none of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed pass returned (image.npy, latent.npy; float32) to DIR")
     args = ap.parse_args()
+    if not args.full:
+        extra = [f for f, on in (("--breakdown", args.breakdown), ("--breakdown-json", args.breakdown_json), ("--swinir", args.swinir)) if on]
+        if extra:
+            ap.error(f"{', '.join(extra)} report(s) of the --full run: add --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without torch.distributed.run: start the N ranks ourselves.  This process has made no GPU
@@ -108,7 +122,7 @@ def main() -> None:
     # ---- the CPU-baseline child is spawned before this process makes any HIP call; it builds its fp32 weights, reports "ready"
     #      and idles.  The GPU side waits for that "ready" before its warm-up, so the two never compete for the host cores.
     cpu_handle = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_handle = start_cpu_baseline(args.config, args.size)
     if world != args.gpus:
         log(f"warning: --gpus {args.gpus} but WORLD_SIZE={world}; using WORLD_SIZE")
@@ -188,6 +202,9 @@ def main() -> None:
 
     if cpu_handle is not None:
         wait_cpu_ready(cpu_handle)
+    # the sampler's per-step noise (torch.randn_like inside every pass) starts from a fixed seed: the same arguments give the
+    # same inputs to every pass, so the outputs of two builds can be compared (--dump-outputs)
+    torch.manual_seed(0)
     # ---- warm-up (builds the kernel programs on the first pass), optional hipGraph capture
     slots = list(range(args.inflight))
     streams = [torch.cuda.Stream() for _ in slots]
@@ -267,10 +284,12 @@ def main() -> None:
     nf = args.inflight      # passes i and i + nf complete on the same stream
     gaps = sorted(ends[i].elapsed_time(ends[i + nf]) / nf for i in range(len(ends) - nf)) if len(ends) > 2 * nf else []
     ms_per_step_median = gaps[len(gaps) // 2] if gaps else None
-    # ---- parity pass (untimed): the same path once more with the reference golden's noise tensors injected
-    cldm.engine_slot = 0
-    img, z = one_pass(inject=True)
-    torch.cuda.synchronize()
+    dumped = dump_outputs(args.dump_outputs, {"image": img, "latent": z}) if args.dump_outputs and rank == 0 else None
+    if args.full:
+        # ---- parity pass (untimed): the same path once more with the reference golden's noise tensors injected
+        cldm.engine_slot = 0
+        img, z = one_pass(inject=True)
+        torch.cuda.synchronize()
     if dist is not None:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -300,8 +319,9 @@ def main() -> None:
         "weight_broadcast": bcast, "rccl_ranks": rccl_ranks,
         "pass_latency_ms_median_hip_events": round(pass_latency_ms, 3) if pass_latency_ms is not None else None,
         "ms_per_step_median_hip_events": round(ms_per_step_median, 3) if ms_per_step_median is not None else None,
-        "sampler_noise": "torch.randn_like on the GPU inside every timed pass (reference utils/sampler.py:199); the parity figures come "
-                         "from one extra untimed pass with the golden's noise injected",
+        "sampler_noise": "torch.randn_like on the GPU inside every timed pass (reference utils/sampler.py:199), seeded with 0 before the "
+                         "warm-up; the parity figures (--full) come from one extra untimed pass with the golden's noise injected",
+        "full": args.full, "dumped_outputs": dumped,
         "mfma_frac_whole_path": round(value * FLOP_PER_IMAGE_BY_WORKLOAD[args.workload] / (world * PEAK_TFLOPS * 1e12), 4)
         if (args.config == "sd21" and std_shape) else None,
     }
@@ -315,15 +335,15 @@ def main() -> None:
 
     default_legs = (world == 1 and args.also != "none" and args.precision == "fast" and args.workload == "det512" and args.config == "sd21"
                     and std_shape and not args.dup and not args.no_graph)
-    if rank == 0 and (args.swinir or default_legs):      # (on the default run too: the step in front of the path, on the driver's record)
+    if args.full and rank == 0 and (args.swinir or default_legs):      # (on every --full run: the step in front of the path)
         try:
             result["pre_restoration"] = swinir_leg(dev, dtype, B, S, args.steps)
         except Exception as e:       # reported separately: must never take the headline line down with it
             result["pre_restoration"] = {"error": repr(e)}
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         result.update(roofline_pass(cldm, args, ms_per_step))
-    if (rank == 0 and world == 1 and args.also != "none" and args.precision == "fast" and args.workload == "det512" and args.config == "sd21"
-            and std_shape and not args.dup and not args.no_graph):
+    if (args.full and rank == 0 and world == 1 and args.also != "none" and args.precision == "fast" and args.workload == "det512"
+            and args.config == "sd21" and std_shape and not args.dup and not args.no_graph):
         # ---- the other single-GPU BASELINE configurations, briefly, on the driver's record too
         result["other_workloads"] = {}
         for name in [w for w in args.also.split(",") if w in ("det512s50", "seg1024tiled")]:
@@ -331,11 +351,11 @@ def main() -> None:
                 result["other_workloads"][name] = other_workload_leg(cldm, diffusion, sampler, name, dev, ctx_dim, args, capture_all, rel_err)
             except Exception as e:       # never take the headline down
                 result["other_workloads"][name] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if cpu_handle is not None:          # (--full, rank 0, N = 1, no --no-cpu-baseline)
         result.update(finish_cpu_baseline(cpu_handle, inp, img.cpu(), z.cpu(), S, rel_err, tol_key))
-    if rank == 0 and args.config == "sd21":     # rank 0's shard starts at image 0 of the global batch: same images as the golden's
+    if args.full and rank == 0 and args.config == "sd21":     # rank 0's shard starts at image 0 of the global batch: same images as the golden's
         result.update(golden_parity(args.workload, img, z, rel_err, tol_key))
-    if (rank == 0 and world == 1 and args.parity_steps > 0 and args.precision == "fast" and args.workload == "det512"
+    if (args.full and rank == 0 and world == 1 and args.parity_steps > 0 and args.precision == "fast" and args.workload == "det512"
             and args.config == "sd21" and std_shape and not args.dup):
         # ---- the modes that meet the north-star tolerance, timed in the SAME run (the headline above is the fast bf16 mode):
         #      "hybrid" = the fastest one on well-conditioned weights (round 6: fp16 encoder + denoiser, mixed decoder); "robust" = the
@@ -380,6 +400,26 @@ def main() -> None:
         except Exception:
             pass
         print(json.dumps(result), flush=True)
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """Write the arrays the last timed pass returned as out_dir/<name>.npy (float32).  All arrays share the batch axis; if the
+    whole batch is over DUMP_BUDGET_BYTES, a fixed seeded sample of images (the same for every array) is written instead."""
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    B = next(iter(host.values())).shape[0]
+    per_image = sum(a[0].nbytes for a in host.values())
+    keep = list(range(B))
+    if per_image * B > DUMP_BUDGET_BYTES:
+        k = max(1, DUMP_BUDGET_BYTES // per_image)
+        keep = sorted(np.random.default_rng(0).choice(B, size=k, replace=False).tolist())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a[keep]))
+    log(f"outputs of the last timed pass written to {out_dir}: " + ", ".join(f"{n}{list(a[keep].shape)}" for n, a in host.items()))
+    return {"dir": out_dir, "arrays": {n: list(a[keep].shape) for n, a in host.items()}, "dtype": "float32", "images": keep}
 
 
 def _free_port() -> int:

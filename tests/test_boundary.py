@@ -10,7 +10,6 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFERENCE = "/root/reference"
 
 
 def _run(code: str, pythonpath: str) -> str:
@@ -51,32 +50,62 @@ def test_standalone_shim_resolves_reference_import_paths():
     assert "OK" in out
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="needs the reference checkout (build container only)")
-def test_overlay_shim_on_a_reference_checkout():
-    """edtr_amd.shim.install() on top of the real reference tree: the REFERENCE's `instantiate_from_config` resolves
-    `model.cldm.ControlLDM` / `utils.sampler.SpacedSampler` to the MI355X classes while everything else (`model.resnet`,
-    `utils.common` itself) still comes from the reference."""
+# A stand-in for a reference checkout, with the reference's package layout: `model/__init__.py` re-exports the classes of its
+# submodules (so importing `model` imports the checkout's own `model.cldm`), `model.resnet` is a module the shim leaves alone,
+# and `utils.common.instantiate_from_config` resolves dotted names through importlib (reference utils/common.py:23-34).
+CHECKOUT_FILES = {
+    "model/__init__.py": "from .cldm import ControlLDM\nfrom .gaussian_diffusion import Diffusion\n",
+    "model/cldm.py": "class ControlLDM:\n    pass\n",
+    "model/gaussian_diffusion.py": "class Diffusion:\n    pass\n",
+    "model/resnet.py": "class ResBlock:\n    pass\n",
+    "utils/__init__.py": "",
+    "utils/sampler.py": "class SpacedSampler:\n    pass\n",
+    "utils/common.py": textwrap.dedent("""\
+        import importlib
+
+
+        def get_obj_from_str(string, reload=False):
+            module, cls = string.rsplit(".", 1)
+            if reload:
+                importlib.reload(importlib.import_module(module))
+            return getattr(importlib.import_module(module, package=None), cls)
+
+
+        def instantiate_from_config(config):
+            if "target" not in config:
+                raise KeyError("Expected key `target` to instantiate.")
+            return get_obj_from_str(config["target"])(**config.get("params", dict()))
+        """),
+}
+
+
+def test_overlay_shim_on_a_reference_checkout(tmp_path):
+    """edtr_amd.shim.install() on top of a checkout with the reference's layout (CHECKOUT_FILES): the checkout's
+    `instantiate_from_config` resolves `model.cldm.ControlLDM` / `utils.sampler.SpacedSampler` to the MI355X classes while
+    everything else (`model.resnet`, `utils.common` itself) still comes from the checkout."""
+    checkout = str(tmp_path / "checkout")
+    for rel, text in CHECKOUT_FILES.items():
+        os.makedirs(os.path.dirname(os.path.join(checkout, rel)), exist_ok=True)
+        with open(os.path.join(checkout, rel), "w") as f:
+            f.write(text)
     out = _run(f"""
         import sys
         sys.dont_write_bytecode = True
-        sys.path.insert(0, {os.path.join(ROOT, "tools")!r})
-        import ref_import
-        ref_import.install_stubs()
-        sys.path.insert(0, {REFERENCE!r})
+        sys.path.insert(0, {checkout!r})
         import edtr_amd.shim as shim
         shim.install()
         import edtr_amd.model.cldm as ours, edtr_amd.sampler
         from edtr_amd import synth
-        from utils.common import instantiate_from_config          # the reference's function
+        from utils.common import instantiate_from_config          # the checkout's function
         import utils.common
-        assert utils.common.__file__.startswith({REFERENCE!r})
+        assert utils.common.__file__.startswith({checkout!r})
         m = instantiate_from_config({{"target": "model.cldm.ControlLDM", "params": synth.tiny_config()}})
         assert type(m) is ours.ControlLDM
         from model import ControlLDM, Diffusion
         from utils.sampler import SpacedSampler
         assert ControlLDM is ours.ControlLDM and SpacedSampler is edtr_amd.sampler.SpacedSampler
         import model.resnet
-        assert model.resnet.__file__.startswith({REFERENCE!r})
+        assert model.resnet.__file__.startswith({checkout!r})
         print("OK")
     """, ROOT)
     assert "OK" in out

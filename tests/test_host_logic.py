@@ -394,14 +394,14 @@ def test_engine_cache_lru():
     assert len(cache) == 0 and sorted(released) == ["A", "B", "C"]
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/model/open_clip/bpe_simple_vocab_16e6.txt.gz"),
-                    reason="needs the OpenCLIP BPE vocabulary of the reference checkout (build container only)")
 def test_clip_tokenizer_token_ids_vs_reference(golden_dir):
     """Non-empty prompts: token ids equal the reference tokenizer's (tests/golden/clip_tokens.json, tools/make_goldens.py
-    gen_tokens) — contractions, unicode letters / digits, html entities, special markers, long words, truncation at 77."""
+    gen_tokens) — contractions, unicode letters / digits, html entities, special markers, long words, truncation at 77.
+    The vocabulary is the part of the OpenCLIP BPE file that the tokenizer reads (tests/golden/clip_bpe_merges.txt.gz,
+    tools/make_goldens.py gen_bpe)."""
     import json
     from edtr_amd.model.clip import SimpleTokenizer, tokenize
-    path = "/root/reference/model/open_clip/bpe_simple_vocab_16e6.txt.gz"
+    path = os.path.join(golden_dir, "clip_bpe_merges.txt.gz")
     with open(os.path.join(golden_dir, "clip_tokens.json")) as f:
         g = json.load(f)
     tok = SimpleTokenizer(path)
@@ -527,6 +527,34 @@ def test_max_norm_gate_catches_a_localised_defect(golden_dir):
     st = err_stats(bad[sel], g["z"])
     assert st["max"] > 20 * st["l2"] and st["p9999"] > 10 * st["l2"]
     assert err_stats(torch.ones(10), torch.ones(10)) == {"l2": 0.0, "max": 0.0, "p9999": 0.0}
+
+
+def test_bench_dump_outputs_and_full_only_reports(tmp_path):
+    """bench.py --dump-outputs: float32 .npy per returned array, the whole batch when it fits the budget, otherwise the same fixed
+    sample of images for every array.  The reports of the --full run are refused without --full (before any GPU work)."""
+    import importlib.util
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    img, z = torch.randn((4, 3, 64, 64), dtype=torch.bfloat16), torch.randn((4, 4, 8, 8))
+    info = bench.dump_outputs(str(tmp_path / "a"), {"image": img, "latent": z})
+    got = np.load(tmp_path / "a" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img.float().numpy()) and info["images"] == [0, 1, 2, 3]
+    assert np.array_equal(np.load(tmp_path / "a" / "latent.npy"), z.numpy())
+    per_image = (3 * 64 * 64 + 4 * 8 * 8) * 4
+    budget, bench.DUMP_BUDGET_BYTES = bench.DUMP_BUDGET_BYTES, 2 * per_image
+    try:
+        first = bench.dump_outputs(str(tmp_path / "b"), {"image": img, "latent": z})
+        again = bench.dump_outputs(str(tmp_path / "c"), {"image": img, "latent": z})
+    finally:
+        bench.DUMP_BUDGET_BYTES = budget
+    assert len(first["images"]) == 2 and first["images"] == again["images"]
+    assert np.array_equal(np.load(tmp_path / "b" / "latent.npy"), z[first["images"]].numpy())
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--breakdown"], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 2 and "--full" in res.stderr
 
 
 def test_host_launch_predicates_imply_the_librarys_own(monkeypatch):

@@ -6,7 +6,7 @@ echo "# name            images/s   ms_per_step   marginal_ms"
 base=""
 for n in NONE vae.conv1 vae.conv2 vae.upsample res.conv1 res.conv2 upsample.conv ff.geglu ff.out flash gn.apply attn.out layernorm st.proj attn1.qkv attn2.q zero_conv res.skip gn.stats gn.finalize add NONE; do
   A="${MC_ARGS:---steps 12 --warmup 3 --no-cpu-baseline --no-roofline --parity-steps 0 --also none}"
-  if [ "$n" = "NONE" ]; then out=$(python bench.py $A 2>/dev/null | tail -1); else out=$(python bench.py $A --dup $n 2>/dev/null | tail -1); fi
+  if [ "$n" = "NONE" ]; then out=$(python bench.py --full $A 2>/dev/null | tail -1); else out=$(python bench.py --full $A --dup $n 2>/dev/null | tail -1); fi
   python3 - "$n" "$out" "$base" <<'PY'
 import json,sys
 n,o,b=sys.argv[1],sys.argv[2],sys.argv[3]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Turn the measured per-class sensitivities (tools/exp/precision_budget_gpu.py) and the per-class launch times at 1 / 2 / 3
-parts (`bench.py --precision mixed --breakdown-json` under the three constant policies) into a part count per GEMM class:
+parts (`bench.py --full --precision mixed --breakdown-json` under the three constant policies) into a part count per GEMM class:
 
     minimise   sum_c time_c(p_c)      subject to   e_base^2 + sum_c var_c(p_c) <= (target)^2    for the latent AND the image
 

@@ -10,7 +10,7 @@ tests/test_gpu_precision.py::test_det512_full_size_meets_the_north_star) against
   var(c, p) = e(c, p)^2 - e_base^2   (independent roundings add in quadrature)
 
 plus the three constant policies.  Writes gpurun_out/r03/precision_sensitivity.json; tools/exp/precision_allocate.py turns it
-(with the per-class launch times of `bench.py --precision mixed --breakdown-json`) into the shipped allocation.
+(with the per-class launch times of `bench.py --full --precision mixed --breakdown-json`) into the shipped allocation.
 
     python tools/exp/precision_budget_gpu.py [--classes a,b,...] [--out path]
 """

@@ -5,7 +5,7 @@ mkdir -p gpurun_out/r04
 tag=$1; shift
 i=0
 for envs in "$@"; do
-  env $envs python bench.py --steps 16 --warmup 2 --no-cpu-baseline --also none --parity-steps 0 --precision mixed --breakdown \
+  env $envs python bench.py --full --steps 16 --warmup 2 --no-cpu-baseline --also none --parity-steps 0 --precision mixed --breakdown \
       > gpurun_out/r04/ab_${tag}_$i.json 2> gpurun_out/r04/ab_${tag}_$i.log
   python - <<PY
 import json

@@ -6,7 +6,7 @@ python -m pytest tests/test_gpu_ops.py -x -q -m gpu -k "halo or conv3x3 or gemm_
 cat gpurun_out/r04/subpixel_tests.log
 for sp in 0 1; do
   for prec in fast mixed; do
-    EDTR_SUBPIXEL=$sp python bench.py --steps 24 --warmup 2 --no-cpu-baseline --also none --parity-steps 0 --precision $prec --breakdown \
+    EDTR_SUBPIXEL=$sp python bench.py --full --steps 24 --warmup 2 --no-cpu-baseline --also none --parity-steps 0 --precision $prec --breakdown \
       > gpurun_out/r04/ab_subpixel_${sp}_${prec}.json 2> gpurun_out/r04/ab_subpixel_${sp}_${prec}.log
     python - <<PY
 import json

@@ -30,7 +30,7 @@ def main():
         if sections is not None:
             env["EDTR_AMD_HYBRID"] = json.dumps(sections)
         env.update(extra_env or {})
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "24", "--warmup", "2", "--also", "none", "--no-cpu-baseline",
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "24", "--warmup", "2", "--also", "none", "--no-cpu-baseline",
                "--no-roofline", "--parity-steps", "0"] + flags
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, cwd=ROOT)
         line = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -25,7 +25,7 @@ def main():
         if only and not any(o in label for o in only):
             continue
         env = dict(os.environ, EDTR_AMD_HYBRID=json.dumps(SEC), EDTR_AMD_POLICY=json.dumps(pol))
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "24", "--warmup", "2", "--also", "none", "--no-cpu-baseline",
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "24", "--warmup", "2", "--also", "none", "--no-cpu-baseline",
                "--no-roofline", "--parity-steps", "0", "--precision", "hybrid"]
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, cwd=ROOT)
         line = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -8,5 +8,5 @@ run denoiser3_split1_vae_shipped "EDTR_AMD_POLICY={\"base\":\"shipped\",\"defaul
 run denoiser3_vae_conv2 "EDTR_AMD_POLICY={\"base\":\"shipped\",\"default\":3,\"vae.conv1\":2,\"vae.conv2\":2,\"vae.attn.qk\":1,\"vae.attn.vT\":1,\"vae.attn.proj_out\":1}"
 for pol in "{\"base\":\"shipped\",\"default\":3,$VAE1}" "{\"default\":3}"; do
   echo "== bench det512 --precision mixed, policy $pol"
-  EDTR_AMD_POLICY="$pol" python bench.py --precision mixed --steps 16 --also none --no-cpu-baseline --no-roofline --parity-steps 0 2>/dev/null | python -c "import json,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); g=j['parity_vs_reference_golden']; print(j['value'], j['ms_per_step'], g['rel_err_latent'], g['rel_err_image_samples'])"
+  EDTR_AMD_POLICY="$pol" python bench.py --full --precision mixed --steps 16 --also none --no-cpu-baseline --no-roofline --parity-steps 0 2>/dev/null | python -c "import json,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); g=j['parity_vs_reference_golden']; print(j['value'], j['ms_per_step'], g['rel_err_latent'], g['rel_err_image_samples'])"
 done

@@ -475,6 +475,20 @@ def gen_tokens():
     print("clip_tokens.json written:", [len(r) for r in raw])
 
 
+def gen_bpe():
+    """The part of the reference's OpenCLIP BPE vocabulary (model/open_clip/bpe_simple_vocab_16e6.txt.gz) that the tokenizer
+    reads: the version line and the first N_MERGES merge rules -> tests/golden/clip_bpe_merges.txt.gz (the whole file is
+    larger than a committed fixture may be; the rows after N_MERGES are never read)."""
+    import gzip
+    from edtr_amd.model.clip import N_MERGES
+    with gzip.open(os.path.join(ref_import.REFERENCE_ROOT, "model", "open_clip", "bpe_simple_vocab_16e6.txt.gz")) as f:
+        rows = f.read().decode("utf-8").split("\n")[:N_MERGES + 1]
+    with open(os.path.join(GOLD, "clip_bpe_merges.txt.gz"), "wb") as raw:
+        with gzip.GzipFile(fileobj=raw, mode="wb", compresslevel=9, mtime=0, filename="") as f:
+            f.write(("\n".join(rows) + "\n").encode("utf-8"))
+    print("clip_bpe_merges.txt.gz written:", len(rows) - 1, "merges")
+
+
 def _img_digest(img: torch.Tensor) -> dict:
     """Compact pin of a large image tensor: stride-4 samples (fp16) + global statistics."""
     return {"samples": img[:, :, 1::4, 2::4].numpy().astype(np.float32),
@@ -577,14 +591,14 @@ def gen_full():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="schedule,tiny,sd21,tiled,tiledvae,vaesample,heavy,wavelet,clip,psnr,swinir,full,tokens")
+    ap.add_argument("--only", default="schedule,tiny,sd21,tiled,tiledvae,vaesample,heavy,wavelet,clip,psnr,swinir,full,tokens,bpe")
     args = ap.parse_args()
     os.makedirs(GOLD, exist_ok=True)
     torch.set_num_threads(os.cpu_count() or 1)
     todo = args.only.split(",")
     for name in todo:
         {"schedule": gen_schedule, "tiny": gen_tiny, "sd21": gen_sd21, "tiled": gen_tiled, "tiledvae": gen_tiledvae,
-         "vaesample": gen_vaesample, "heavy": gen_heavy, "wavelet": gen_wavelet, "clip": gen_clip, "psnr": gen_psnr, "swinir": gen_swinir, "full": gen_full, "tokens": gen_tokens, "demo": gen_demo, "moderate": gen_moderate}[name]()
+         "vaesample": gen_vaesample, "heavy": gen_heavy, "wavelet": gen_wavelet, "clip": gen_clip, "psnr": gen_psnr, "swinir": gen_swinir, "full": gen_full, "tokens": gen_tokens, "bpe": gen_bpe, "demo": gen_demo, "moderate": gen_moderate}[name]()
 
 
 if __name__ == "__main__":

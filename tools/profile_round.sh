@@ -11,12 +11,12 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$R/prof
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 4 --warmup 1 --no-cpu-baseline --no-roofline --parity-steps 0 --also none"
+ARGS="--full --steps 4 --warmup 1 --no-cpu-baseline --no-roofline --parity-steps 0 --also none"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py $ARGS > $OUT/trace.json 2> $OUT/trace.log
 python3 $ROOT/tools/prof_summary.py stats $OUT/trace $OUT/kernel_stats.csv
 # warm-up (first pass per slot = 2) + 1 warm-up round (2) + 4 timed + 1 parity pass = 9 passes under the default two batches in flight
 python3 $ROOT/tools/prof_summary.py union $OUT/trace $OUT/kernel_busy_union.json --passes 9 > /dev/null
-PARGS="--steps 1 --warmup 1 --inflight 1 --no-graph --no-cpu-baseline --no-roofline --parity-steps 0 --also none"
+PARGS="--full --steps 1 --warmup 1 --inflight 1 --no-graph --no-cpu-baseline --no-roofline --parity-steps 0 --also none"
 export EDTR_SYNTH_DEVICE=cpu      # rocprofv3 --pmc FETCH_SIZE crashes inside torch's int64 elementwise kernels (weight hashing)
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 $ROOT/bench.py $PARGS > /dev/null 2> $OUT/pmc_fetch.log
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 $ROOT/bench.py $PARGS > /dev/null 2> $OUT/pmc_write.log
@@ -32,7 +32,7 @@ out, root = sys.argv[1], sys.argv[2]
 sys.path.insert(0, root)
 from edtr_amd.build import source_hash
 f, w = json.load(open(f"{out}/pmc_fetch.json")), json.load(open(f"{out}/pmc_write.json"))
-res = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --output-format csv) -- python3 bench.py --steps 1 --warmup 1 "
+res = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --output-format csv) -- python3 bench.py --full --steps 1 --warmup 1 "
                  "--inflight 1 --no-graph --no-cpu-baseline --no-roofline --parity-steps 0 (EDTR_SYNTH_DEVICE=cpu); 4 passes of the path "
                  "(program build, warm-up, timed, parity), 1 x MI355X, batch 8 of 512x512 bf16",
        "correction": "fetch bytes = 2 x FETCH_SIZE x 1024 (gfx950 counts wide coalesced reads at half their bytes: MI355X_MICROARCH.md, "
