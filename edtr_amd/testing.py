@@ -3,6 +3,7 @@ Nothing here touches the CPU oracle (oracle/ is imported by tests/, __graft_entr
 from __future__ import annotations
 
 import contextlib
+import math
 from typing import Dict, Iterable
 
 import torch
@@ -83,3 +84,108 @@ def err_stats(a, b) -> Dict[str, float]:
     k = max(1, int(round(d.numel() * 1e-4)))
     p9999 = float(torch.topk(d, k).values[-1]) if d.numel() > 1 else float(d.max())
     return {"l2": float(d.norm() / b.norm().clamp_min(1e-30)), "max": float(d.max()) / peak, "p9999": p9999 / peak}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Rounding-aware element bound (the per-kernel parity tests).  A kernel that reads 16-bit operands, accumulates in fp32 and
+# rounds its output once satisfies, element by element,
+#     |got - ref| <= 2 u |ref| + k 2^-22 absref + extra + floor
+# with ref in fp64 from exactly the 16-bit values the kernel reads, absref the same expression on absolute values
+# (|alpha| |A| @ |W|^T + |bias| + |residual|, conv2d(|x|, |w|), ...), k the reduction length and u the unit roundoff of the
+# stored output (2u = one ulp).  k 2^-22 absref bounds fp32 accumulation in any order generously (fp32 MFMA chains measure
+# ~1e-7 sum|a b|); `extra` names the roundings a kernel performs on purpose (a 16-bit P before P V, a 16-bit hidden tensor);
+# `floor` covers fp16 subnormals.  A correct kernel stays near 0.5; one wrong tile, seam, tail or column exceeds 1 even
+# where the relative L2 norm of the whole tensor does not move.
+# ---------------------------------------------------------------------------------------------------------------------
+ACC_F32 = 2.0 ** -22                      # per-term fp32 accumulation slack (k 2^-22 absref)
+LIPSCHITZ = {"none": 1.0, "silu": 1.1, "gelu": 1.13, "leaky": 1.0}
+GELU_APPROX = 2.0e-7                      # csrc/common.h gelu_erf_f: A&S 7.1.26 erf (|err| <= 1.5e-7) + rcp / exp ulps, times 0.5 |x|
+
+
+def unit_roundoff(dtype) -> float:
+    """u of the stored output: 2^-8 bf16, 2^-11 fp16, 2^-24 fp32 (round to nearest: |fl(x) - x| <= u |x|)."""
+    return {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11, torch.float32: 2.0 ** -24}[dtype]
+
+
+def _floor(dtype) -> float:
+    return 2.0 ** -24 if dtype == torch.float16 else 1e-300
+
+
+def elem_bound(ref, absref, out_dtype, k, extra=None) -> torch.Tensor:
+    """The bound above as an fp64 tensor of ref's shape (extra: {name: tensor or float}, every term added)."""
+    ref = torch.as_tensor(ref).double().cpu()
+    b = 2.0 * unit_roundoff(out_dtype) * ref.abs() + _floor(out_dtype)
+    if absref is not None and k:
+        b = b + float(k) * ACC_F32 * torch.as_tensor(absref).double().cpu()
+    for term in (extra or {}).values():
+        b = b + (torch.as_tensor(term).double().cpu() if torch.is_tensor(term) else float(term))
+    return b
+
+
+def elem_ratio(got, ref, absref, out_dtype, k, extra=None):
+    """Worst |got - ref| / bound and where it occurs: (ratio, {"index", "got", "ref", "bound"}).  A non-finite `got` is inf."""
+    got = torch.as_tensor(got).double().cpu()
+    ref = torch.as_tensor(ref).double().cpu()
+    assert got.shape == ref.shape, (tuple(got.shape), tuple(ref.shape))
+    b = elem_bound(ref, absref, out_dtype, k, extra).expand(ref.shape)
+    r = (got - ref).abs() / b
+    r = torch.where(torch.isfinite(got), r, torch.full_like(r, float("inf")))
+    if r.numel() == 0:
+        return 0.0, {}
+    flat = int(torch.argmax(torch.nan_to_num(r, nan=float("inf"))))
+    idx = tuple(int(i) for i in torch.unravel_index(torch.tensor(flat), r.shape))
+    info = {"index": idx, "got": float(got[idx]), "ref": float(ref[idx]), "bound": float(b[idx])}
+    return float(r[idx]), info
+
+
+def geglu_err(val, gate, ev, eg):
+    """Absolute error bound of val * gelu(gate) when val / gate are off by at most ev / eg: the product rule with GELU's
+    Lipschitz constant and the epilogue's erf approximation."""
+    val, gate = torch.as_tensor(val).double(), torch.as_tensor(gate).double()
+    eg = LIPSCHITZ["gelu"] * torch.as_tensor(eg).double() + GELU_APPROX * gate.abs()
+    ev = torch.as_tensor(ev).double()
+    return ev * torch.nn.functional.gelu(gate).abs() + val.abs() * eg + ev * eg
+
+
+def geglu_slack(val, gate, abs_val, abs_gate, k):
+    """geglu_err for val / gate that carry the fp32 accumulation error k 2^-22 abs_* (pass it as an `extra` term with k = 0)."""
+    return geglu_err(val, gate, float(k) * ACC_F32 * torch.as_tensor(abs_val).double(), float(k) * ACC_F32 * torch.as_tensor(abs_gate).double())
+
+
+def rounded_operand(v, dv, dtype):
+    """A kernel rounds an fp32 intermediate to 16 bits on purpose (a normalised row, a hidden tensor) before multiplying it; the
+    reference mirrors that rounding on its fp64 value v.  Where the kernel's fp32 value may differ from v by dv, it rounds to
+    the same 16-bit value unless a rounding boundary lies within dv of v; there it may land one spacing away.  Returns
+    (v rounded to dtype, in fp64; that spacing where a boundary lies within dv, else 0) — the second is the operand error
+    to propagate, instead of assuming every operand is one ulp off."""
+    v = torch.as_tensor(v).double()
+    v16 = v.to(dtype).double()
+    p = {torch.bfloat16: 8, torch.float16: 11}[dtype]
+    emin = {torch.bfloat16: -126, torch.float16: -14}[dtype]
+    e = torch.floor(torch.log2(v16.abs().clamp_min(2.0 ** emin))).clamp_min(emin)
+    ulp = torch.pow(2.0, e - (p - 1))                                  # spacing above |v16|
+    pow2 = (v16.abs() == torch.pow(2.0, e)) & (e > emin)
+    below = torch.where(pow2, ulp / 2, ulp)                            # spacing below |v16| (half at a power of two)
+    dist = torch.minimum(ulp, below) / 2 - (v - v16).abs()             # distance from v to the nearest rounding boundary
+    dv = torch.as_tensor(dv).double() + 2.0 ** -23 * v.abs()          # (+ the fp32 representation of v itself, a tie at the boundary)
+    return v16, torch.where(dist <= dv, ulp, torch.zeros_like(ulp))
+
+
+def block_rel(got, ref, cols, block=32) -> float:
+    """Worst relative L2 error over the block x block tiles of the [rows, cols] view, each tile's reference norm floored at
+    the tensor's RMS (a tile of near-zero values does not turn rounding noise into a large ratio)."""
+    got = torch.as_tensor(got).double().cpu().reshape(-1, cols)
+    ref = torch.as_tensor(ref).double().cpu().reshape(-1, cols)
+    rms = float(ref.pow(2).mean().sqrt())
+    if not bool(torch.isfinite(got).all()):
+        return float("inf")
+    rows = ref.shape[0]
+    pr, pc = -rows % block, -cols % block
+    d2 = torch.nn.functional.pad((got - ref) ** 2, (0, pc, 0, pr))
+    f2 = torch.nn.functional.pad(ref ** 2, (0, pc, 0, pr))
+    n = torch.nn.functional.pad(torch.ones_like(ref), (0, pc, 0, pr))
+
+    def tiles(t):
+        return t.reshape(t.shape[0] // block, block, t.shape[1] // block, block).sum((1, 3))
+    den = torch.maximum(tiles(f2), rms * rms * tiles(n)).sqrt().clamp_min(1e-300)
+    return float((tiles(d2).sqrt() / den).max())
