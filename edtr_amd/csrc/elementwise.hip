@@ -1,5 +1,6 @@
 // Layout conversion and small elementwise kernels (HBM-bound or negligible) + runtime helpers.
 #include "common.h"
+#include "noise_elem.h"
 #include <string.h>
 
 namespace {
@@ -240,15 +241,7 @@ __global__ void temb_kernel(const int64_t* t, int dim, typename T::elem* out, in
     }
 }
 
-// one element of the spaced-sampler update, with the rounding points fixed (explicit fma) so that the scalar-coefficient and
-// the device-indexed kernels agree bit for bit
-__device__ __forceinline__ void sampler_update_elem(float xv, float e, float nz, float c_recip, float c_recipm1, float coef1,
-                                                    float coef2, float sigma, float& p0, float& xp) {
-    p0 = __builtin_fmaf(c_recip, xv, -(c_recipm1 * e));
-    const float mean = __builtin_fmaf(coef1, p0, coef2 * xv);
-    xp = __builtin_fmaf(sigma, nz, mean);
-}
-
+// (sampler_update_elem, q_sample_elem, gaussian_sample_elem: noise_elem.h, shared with the seeded forms of rng.hip)
 __global__ void __launch_bounds__(256) sampler_update_kernel(const float* x, const float* eps, const float* noise,
                                                             float c_recip, float c_recipm1, float coef1, float coef2,
                                                             float sigma, float* x_prev, float* pred_x0, int64_t n) {
@@ -272,7 +265,7 @@ __global__ void __launch_bounds__(256) q_sample_kernel(const float* x, const flo
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         int64_t ti = t[i / per_image];
         ti = ti < 0 ? 0 : (ti >= n_tab ? n_tab - 1 : ti);
-        out[i] = tab_a[ti] * x[i] + tab_b[ti] * noise[i];
+        out[i] = q_sample_elem(tab_a[ti], x[i], tab_b[ti], noise[i]);
     }
 }
 
@@ -299,12 +292,7 @@ __global__ void __launch_bounds__(256) gaussian_sample_kernel(const float* momen
         const int c = (int)(bc % C);
         const int64_t b = bc / C;
         const float* row = moments + (b * HW + px) * ld;
-        float v = row[c];
-        if (noise) {
-            const float lv = fminf(fmaxf(row[C + c], -30.0f), 20.0f);
-            v += expf(0.5f * lv) * noise[i];
-        }
-        out[i] = v * scale;
+        out[i] = noise ? gaussian_sample_elem(row[c], row[C + c], noise[i], scale) : row[c] * scale;
     }
 }
 

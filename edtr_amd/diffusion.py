@@ -54,15 +54,24 @@ class Diffusion(nn.Module):
     def register(self, name: str, value: np.ndarray) -> None:
         self.register_buffer(name, torch.tensor(value, dtype=torch.float32))
 
-    def q_sample(self, x_start: torch.Tensor, t: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
+    def q_sample(self, x_start: torch.Tensor, t: torch.Tensor, noise) -> torch.Tensor:
         """sqrt(ac_t) x0 + sqrt(1 - ac_t) noise, one libedtr_hip launch.  A GPU-resident ``t`` (every reference call
         site: demo.py:107-108, main/*/test_edtr.py) is read ON the device by edtr_q_sample — no ``.tolist()`` / host
         round trip; a host ``t`` is turned into scalars for edtr_axpby (per-sample launches when it is not uniform)."""
         if x_start.device.type != "cuda":
             raise RuntimeError("Diffusion.q_sample: GPU tensors required (no CPU fallback on the EDTR MI355X path)")
         x_start = x_start.contiguous().float()
-        noise = noise.contiguous().float()
         out = torch.empty_like(x_start)
+        if not torch.is_tensor(noise):
+            # an edtr_amd.rng.NoiseSource: the seeded per-image stream (purpose 0) drawn inside edtr_q_sample_rng — one launch, no
+            # noise tensor; a host `t` is moved to the device first (the kernel reads it there)
+            if self.sqrt_alphas_cumprod.device != x_start.device:
+                raise RuntimeError("Diffusion.q_sample: call diffusion.to(device) first (the schedule tables are on "
+                                   f"{self.sqrt_alphas_cumprod.device})")
+            ops.launch(ops.make_q_sample_rng(x=x_start, source=noise, t=t.to(device=x_start.device, dtype=torch.int64).contiguous(),
+                                             tab_a=self.sqrt_alphas_cumprod, tab_b=self.sqrt_one_minus_alphas_cumprod, out=out))
+            return out
+        noise = noise.contiguous().float()
         if t.device.type == "cuda":
             if self.sqrt_alphas_cumprod.device != x_start.device:
                 raise RuntimeError("Diffusion.q_sample: call diffusion.to(device) first (the schedule tables are on "

@@ -9,6 +9,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from .parallel import shard_slice
+from .rng import NoiseSource, shard_chunk_ids
 
 
 def list_to_batch(img_list: Sequence[torch.Tensor], img_size: int, device) -> torch.Tensor:
@@ -69,7 +70,7 @@ def calculate_psnr_pt(img: torch.Tensor, img2: torch.Tensor, crop_border: int, t
 def restore_dataset(cldm, diffusion, sampler, pre_restored: Sequence[torch.Tensor], gts: Optional[Sequence[torch.Tensor]] = None,
                     img_size: int = 512, batch_size: int = 8, used_timesteps=(50, 100, 150, 200), start_timestep: int = 200,
                     colour_fix: bool = True, swinir=None, pad_mode: str = "batch", multiple: int = 64,
-                    clamp: bool = True) -> Tuple[List[torch.Tensor], Optional[torch.Tensor]]:
+                    clamp: bool = True, seed: Optional[int] = None) -> Tuple[List[torch.Tensor], Optional[torch.Tensor]]:
     """The restoration loop of main/det/test_edtr.py:121-135 without accelerate: this rank's shard of the
     (C, h, w <= img_size) pre-restored images is padded, pushed through vae_encode -> q_sample(t) -> spaced sampler ->
     vae_decode (-> wavelet colour fix), cropped back, and — when ground truth is given — scored with PSNR; the scalar
@@ -77,7 +78,10 @@ def restore_dataset(cldm, diffusion, sampler, pre_restored: Sequence[torch.Tenso
     low-quality images themselves and the pre-restoration runs on the padded batch first (`cfg.model.pre_restoration`,
     main/det/test_edtr.py:118).  ``pad_mode="demo"`` is the single-image flow of demo.py:84-131,165 instead: every image on its own,
     `pad_if_smaller(img_size)` -> `pad_to_multiples_of(multiple)` -> (SwinIR) -> the same path -> crop back to the input's size
-    (``clamp=False`` keeps the values the reference hands to `save_image`).  Returns (restored images of this shard, mean PSNR or None)."""
+    (``clamp=False`` keeps the values the reference hands to `save_image`).  ``seed``: None = the noise comes from torch's generator
+    as in the reference; an int = every image gets the seeded stream of its index in the GLOBAL ``pre_restored`` list
+    (edtr_amd.rng), so its noise — and, with EDTR_AMD_BATCH_INVARIANT=1, its restoration bit for bit — does not depend on
+    ``batch_size``, ``pad_mode`` or the number of ranks.  Returns (restored images of this shard, mean PSNR or None)."""
     import torch.distributed as dist
     from .wavelet import wavelet_reconstruction
     dev = next(cldm.unet.parameters()).device
@@ -89,8 +93,10 @@ def restore_dataset(cldm, diffusion, sampler, pre_restored: Sequence[torch.Tenso
     if pad_mode not in ("batch", "demo"):
         raise ValueError(f"pad_mode must be 'batch' or 'demo', got {pad_mode!r}")
     step = 1 if pad_mode == "demo" else batch_size
+    chunk_ids = shard_chunk_ids(len(pre_restored), rank, world, batch_size, pad_mode) if seed is not None else None
     for i in range(0, len(mine), step):
         chunk = mine[i:i + step]
+        source = NoiseSource(seed, chunk_ids[i // step]) if seed is not None else None
         if pad_mode == "demo":
             pre = pad_to_multiples_of(pad_if_smaller(chunk[0][None].to(dev).float(), img_size), multiple)
         else:
@@ -99,10 +105,11 @@ def restore_dataset(cldm, diffusion, sampler, pre_restored: Sequence[torch.Tenso
             pre = swinir(pre)
         cond = cldm.prepare_condition(pre, [""] * pre.size(0))
         t = torch.full((pre.size(0),), start_timestep, dtype=torch.int64)
-        x_T = diffusion.q_sample(cond["c_img"], t, torch.randn_like(cond["c_img"]))
+        x_T = diffusion.q_sample(cond["c_img"], t, torch.randn_like(cond["c_img"]) if source is None else source)
         z = sampler.manual_sample_with_timesteps(model=cldm, device=dev, x_T=x_T, steps=len(used_timesteps),
                                                  used_timesteps=list(used_timesteps), batch_size=pre.size(0), cond=cond,
-                                                 uncond=None, cfg_scale=1.0, progress=False)
+                                                 uncond=None, cfg_scale=1.0, progress=False,
+                                                 **({} if source is None else {"noise_source": source}))
         res = (cldm.vae_decode(z) + 1) / 2
         if colour_fix:
             res = wavelet_reconstruction(res, pre)

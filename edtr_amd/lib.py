@@ -20,6 +20,7 @@ DECLARED_SYMBOLS = [
     "edtr_graph_destroy", "edtr_zero_bytes", "edtr_embed_tokens", "edtr_window_attn", "edtr_pixel_unshuffle", "edtr_swin_mlp", "edtr_swin_attn", "edtr_swin_layer", "edtr_conv64", "edtr_conv128_out",
     "edtr_split_operand", "edtr_sampler_update_indexed", "edtr_gaussian_sample", "edtr_add_mirror", "edtr_igemm_plan", "edtr_flash_attn512",
     "edtr_ffn", "edtr_ffn_plan", "edtr_add_stats", "edtr_lin320", "edtr_lin320_plan",
+    "edtr_normal_fill", "edtr_q_sample_rng", "edtr_sampler_update_rng", "edtr_sampler_update_indexed_rng", "edtr_gaussian_sample_rng",
 ]
 
 
@@ -241,6 +242,13 @@ def load() -> C.CDLL:
     lib.edtr_ffn_plan.argtypes = [C.POINTER(FfnParams)]
     lib.edtr_lin320.argtypes = [C.POINTER(Lin320Params), vp]
     lib.edtr_lin320_plan.argtypes = [C.POINTER(Lin320Params)]
+    # seeded noise (edtr_hip.h "Reproducible noise"): ..., seed, image_ids, image_id_base, ...
+    u64 = C.c_uint64
+    lib.edtr_normal_fill.argtypes = [vp, i32, i64, u64, vp, i64, i32, i64, vp]
+    lib.edtr_q_sample_rng.argtypes = [vp, vp, vp, vp, i32, vp, i32, i64, u64, vp, i64, vp]
+    lib.edtr_sampler_update_rng.argtypes = [vp, vp, f32, f32, f32, f32, f32, vp, vp, i32, i64, u64, vp, i64, i64, vp]
+    lib.edtr_sampler_update_indexed_rng.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, i64, u64, vp, i64, vp]
+    lib.edtr_gaussian_sample_rng.argtypes = [vp, i32, vp, i32, i32, i64, f32, u64, vp, i64, vp]
     if lib.edtr_abi_version() != 10:
         raise RuntimeError("libedtr_hip.so ABI version mismatch")
     _lib = lib

@@ -493,7 +493,7 @@ class VaeEngine:
 
     def run(self, x: torch.Tensor, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
         self.inp.copy_(x)
-        if self.noise_in is not None:
+        if self.noise_in is not None and noise is not self.noise_in:      # (already in place: the seeded fill of vae_encode)
             self.noise_in.copy_(noise)
         self.prog.run()
         if (self.nan_probe is not None and VaeEngine.NAN_PROBE and not torch.cuda.is_current_stream_capturing()):
@@ -651,7 +651,8 @@ class ControlLDM(nn.Module):
 
     # -- VAE (reference model/cldm.py:107-156) ------------------------------------------------------
     @torch.no_grad()
-    def vae_encode(self, image: torch.Tensor, sample: bool = True, tiled: bool = False, tile_size: int = -1) -> torch.Tensor:
+    def vae_encode(self, image: torch.Tensor, sample: bool = True, tiled: bool = False, tile_size: int = -1,
+                   noise_source=None) -> torch.Tensor:
         _require_gpu(image, "vae_encode")
         B, _, H, W = image.shape
         if tiled and tile_size <= 0:
@@ -661,6 +662,14 @@ class ControlLDM(nn.Module):
             return eng.run(image).clone()
         # DiagonalGaussianDistribution.sample(): the reference draws torch.randn(mean.shape) on the HOST generator and moves it
         # to the device (model/distributions.py:38-41); the same call here, so a seeded run sees the same draw
+        if noise_source is not None:
+            # an edtr_amd.rng.NoiseSource: the posterior's draw is the seeded per-image stream (purpose 3), written by edtr_normal_fill
+            # straight into the engine's noise operand.  (The engine's program is replayed from a captured graph, whose by-value
+            # arguments — the seed — are frozen at capture, so the fill stays outside it; edtr_gaussian_sample_rng is the one-launch
+            # form for callers that own their launch list, and gives the same bits.)
+            from ..rng import PURPOSE_VAE
+            ops_mod.launch(ops_mod.make_normal_fill(out=eng.noise_in, source=noise_source, purpose=PURPOSE_VAE))
+            return eng.run(image, eng.noise_in).clone()
         noise = torch.randn(tuple(eng.out.shape)).to(device=image.device)
         return eng.run(image, noise).clone()
 

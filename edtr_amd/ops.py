@@ -665,6 +665,54 @@ def make_gaussian_sample(*, moments, ld, noise, out, B, C, HW, scale, name="gaus
     return Rec(L.load().edtr_gaussian_sample, args, (moments, noise, out), name, 0.0, 16.0 * B * C * HW)
 
 
+# -- seeded noise (edtr_hip.h "Reproducible noise"): the records of the tensor-noise launches above with the noise operand replaced by
+#    a `rng.NoiseSource` (seed by value, the batch's global image ids read from its device copy) --------------------------------------
+def _noise_args(source, B: int, device, what: str):
+    """(seed, image_ids pointer, image_id_base, keepalive) of a NoiseSource checked against the batch size"""
+    ids = source.check_batch(B, what).ids_on(device)
+    return source.seed, ptr(ids), 0, ids
+
+
+def make_normal_fill(*, out, source, purpose: int, draw: int = 0, name="normal_fill") -> Rec:
+    """out [B, ...] fp32 = the stream of ``source``'s images for (purpose, draw)."""
+    B = out.shape[0]
+    per = out.numel() // B
+    seed, ids_p, base, ids = _noise_args(source, B, out.device, name)
+    args = (ptr(out), B, per, seed, ids_p, base, int(purpose), int(draw))
+    return Rec(L.load().edtr_normal_fill, args, (out, ids), name, 0.0, 4.0 * out.numel())
+
+
+def make_q_sample_rng(*, x, source, t, tab_a, tab_b, out, name="q_sample_rng") -> Rec:
+    B = x.shape[0]
+    per = x.numel() // B
+    seed, ids_p, base, ids = _noise_args(source, B, x.device, name)
+    args = (ptr(x), ptr(t), ptr(tab_a), ptr(tab_b), tab_a.numel(), ptr(out), B, per, seed, ids_p, base)
+    return Rec(L.load().edtr_q_sample_rng, args, (x, t, tab_a, tab_b, out, ids), name, 0.0, 8.0 * x.numel())
+
+
+def make_sampler_update_rng(*, x, eps, source, draw: int, coefs: Sequence[float], x_prev, pred_x0, name="sampler_update_rng") -> Rec:
+    a, b, c1, c2, sigma = (float(v) for v in coefs)
+    B = x.shape[0]
+    per = x.numel() // B
+    seed, ids_p, base, ids = _noise_args(source, B, x.device, name)
+    args = (ptr(x), ptr(eps), a, b, c1, c2, sigma, ptr(x_prev), ptr(pred_x0), B, per, seed, ids_p, base, int(draw))
+    return Rec(L.load().edtr_sampler_update_rng, args, (x, eps, x_prev, pred_x0, ids), name, 0.0, 16.0 * x.numel())
+
+
+def make_sampler_update_indexed_rng(*, x, eps, source, index, coefs, x_prev, pred_x0, name="sampler_update_rng") -> Rec:
+    B = x.shape[0]
+    per = x.numel() // B
+    seed, ids_p, base, ids = _noise_args(source, B, x.device, name)
+    args = (ptr(x), ptr(eps), ptr(index), ptr(coefs), coefs.shape[0], ptr(x_prev), ptr(pred_x0), B, per, seed, ids_p, base)
+    return Rec(L.load().edtr_sampler_update_indexed_rng, args, (x, eps, index, coefs, x_prev, pred_x0, ids), name, 0.0, 16.0 * x.numel())
+
+
+def make_gaussian_sample_rng(*, moments, ld, source, out, B, C, HW, scale, name="gaussian_sample_rng") -> Rec:
+    seed, ids_p, base, ids = _noise_args(source, B, out.device, name)
+    args = (ptr(moments), ld, ptr(out), B, C, HW, float(scale), seed, ids_p, base)
+    return Rec(L.load().edtr_gaussian_sample_rng, args, (moments, out, ids), name, 0.0, 12.0 * B * C * HW)
+
+
 def make_cast16(*, dtype, src: torch.Tensor, rows: int, C: int, dst: torch.Tensor, name="cast16") -> Rec:
     args = (dt_code(dtype), ptr(src), rows, C, src.stride(0), ptr(dst), dst.stride(0))
     return Rec(L.load().edtr_cast16, args, (src, dst), name, 0.0, 6.0 * rows * C)

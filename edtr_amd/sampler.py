@@ -113,10 +113,13 @@ class SpacedSampler(nn.Module):
                 float(h["posterior_mean_coef1"][index]), float(h["posterior_mean_coef2"][index]), sigma)
 
     @torch.no_grad()
-    def p_sample(self, model, x, t, index, cond, uncond, cfg_scale):
+    def p_sample(self, model, x, t, index, cond, uncond, cfg_scale, noise_source=None):
         """eps -> x0 -> posterior mean -> x_{t-1} (reference :184-204).  `index` must be uniform over the batch (it
-        always is: the loop builds it with torch.full_like)."""
+        always is: the loop builds it with torch.full_like).  ``noise_source`` (an edtr_amd.rng.NoiseSource): the step noise is the
+        seeded per-image stream, drawn inside the update kernel (purpose 1, draw = `index`); None = torch.randn_like, as the reference."""
         eps = self.predict_noise(model, x, t, cond, uncond, cfg_scale).contiguous().float()
+        if noise_source is not None:
+            return self._p_sample_seeded(x, eps, index, noise_source)
         noise = torch.randn_like(x)     # drawn every step, masked on the last one (reference :199-203)
         x = x.contiguous().float()
         x_prev, pred_x0 = torch.empty_like(x), torch.empty_like(x)
@@ -134,6 +137,26 @@ class SpacedSampler(nn.Module):
         idx = int(index) if not torch.is_tensor(index) else int(index.reshape(-1)[0])      # host tensor / int: no device sync
         ops.launch(ops.make_sampler_update(x=x, eps=eps, noise=noise.contiguous().float(), coefs=self._coefs(idx),
                                            x_prev=x_prev, pred_x0=pred_x0, n=x.numel()))
+        return x_prev, pred_x0
+
+    def _p_sample_seeded(self, x, eps, index, noise_source):
+        """The update of p_sample with the noise formed in registers (edtr_sampler_update_rng / _indexed_rng): no noise tensor, no
+        torch.randn* call.  Same two forms as p_sample: a device `index` is read on the device (coefficients and draw)."""
+        x = x.contiguous().float()
+        noise_source.check_batch(x.shape[0], "p_sample")
+        x_prev, pred_x0 = torch.empty_like(x), torch.empty_like(x)
+        if torch.is_tensor(index) and index.device.type == "cuda":
+            idx = index.reshape(-1).to(torch.int64)
+            if idx.numel() == 1 and x.shape[0] > 1:
+                idx = idx.expand(x.shape[0])
+            if idx.numel() != x.shape[0]:
+                raise ValueError(f"p_sample: index has {idx.numel()} entries for a batch of {x.shape[0]} (1 or the batch size)")
+            ops.launch(ops.make_sampler_update_indexed_rng(x=x, eps=eps, source=noise_source, index=idx.contiguous(),
+                                                           coefs=self._coef_table(x.device), x_prev=x_prev, pred_x0=pred_x0))
+            return x_prev, pred_x0
+        idx = int(index) if not torch.is_tensor(index) else int(index.reshape(-1)[0])
+        ops.launch(ops.make_sampler_update_rng(x=x, eps=eps, source=noise_source, draw=idx, coefs=self._coefs(idx),
+                                               x_prev=x_prev, pred_x0=pred_x0))
         return x_prev, pred_x0
 
     def _coef_table(self, device) -> torch.Tensor:
@@ -165,7 +188,8 @@ class SpacedSampler(nn.Module):
                 x_tile, t, {"c_txt": cond["c_txt"], "c_img": cond["c_img"][..., hi:hi_end, wi:wi_end]}),
             tile_size, tile_stride, batched_fn=batched)
 
-    def _loop(self, model, device, img, batch_size, cond, uncond, cfg_scale, return_intermediates, progress=False, progress_leave=True):
+    def _loop(self, model, device, img, batch_size, cond, uncond, cfg_scale, return_intermediates, progress=False, progress_leave=True,
+              noise_source=None):
         timesteps = np.flip(self.timesteps)
         total = len(self.timesteps)
         intermediates = []
@@ -177,27 +201,40 @@ class SpacedSampler(nn.Module):
                 pass
         for i, step in enumerate(timesteps):
             ts = torch.full((batch_size,), int(step), device=device, dtype=torch.long)
-            img, pred_x0 = self.p_sample(model, img, ts, total - i - 1, cond, uncond, cfg_scale)
+            if noise_source is None:
+                img, pred_x0 = self.p_sample(model, img, ts, total - i - 1, cond, uncond, cfg_scale)
+            else:
+                img, pred_x0 = self.p_sample(model, img, ts, total - i - 1, cond, uncond, cfg_scale, noise_source)
             if return_intermediates:
                 intermediates.append(pred_x0)
         return (img, intermediates) if return_intermediates else img
 
     @torch.no_grad()
     def sample(self, model, device, steps, batch_size, x_size, cond, uncond, cfg_scale, tiled=False, tile_size=-1,
-               tile_stride=-1, x_T=None, progress=True, progress_leave=True, return_intermediates=False):
+               tile_stride=-1, x_T=None, progress=True, progress_leave=True, return_intermediates=False, noise_source=None):
+        """``noise_source``: x_T (when not given) and every step's noise come from the seeded per-image stream (purposes 2 and 1)."""
         self.make_schedule(steps)
         self.to(device)
         if tiled:
             self._install_tiling(model, tile_size, tile_stride)
-        img = torch.randn((batch_size, *x_size), device=device) if x_T is None else x_T
-        return self._loop(model, device, img, batch_size, cond, uncond, cfg_scale, return_intermediates, progress, progress_leave)
+        if x_T is not None:
+            img = x_T
+        elif noise_source is None:
+            img = torch.randn((batch_size, *x_size), device=device)
+        else:
+            from .rng import PURPOSE_X_T
+            img = torch.empty((batch_size, *x_size), device=device, dtype=torch.float32)
+            ops.launch(ops.make_normal_fill(out=img, source=noise_source, purpose=PURPOSE_X_T))
+        return self._loop(model, device, img, batch_size, cond, uncond, cfg_scale, return_intermediates, progress, progress_leave,
+                          noise_source)
 
     @torch.no_grad()
     def manual_sample_with_timesteps(self, model, device, x_T, steps, used_timesteps, batch_size, cond, uncond, cfg_scale,
                                      tiled=False, tile_size=-1, tile_stride=-1, progress=True, progress_leave=True,
-                                     return_intermediates=False):
+                                     return_intermediates=False, noise_source=None):
         self.make_schedule(steps, used_timesteps)
         self.to(device)
         if tiled:
             self._install_tiling(model, tile_size, tile_stride)
-        return self._loop(model, device, x_T, batch_size, cond, uncond, cfg_scale, return_intermediates, progress, progress_leave)
+        return self._loop(model, device, x_T, batch_size, cond, uncond, cfg_scale, return_intermediates, progress, progress_leave,
+                          noise_source)

@@ -56,10 +56,12 @@ def make_inputs(workload: str, ctx_dim: int, dev, batch: int, size: int, rank: i
 
 
 def restore_pass(cldm, diffusion, sampler, inp: Inputs, workload: str, untiled_forward=None,
-                 inject: bool = True) -> Tuple[torch.Tensor, torch.Tensor, Dict[str, torch.Tensor]]:
+                 inject: bool = True, noise_source=None) -> Tuple[torch.Tensor, torch.Tensor, Dict[str, torch.Tensor]]:
     """One pass of the hot path over one batch.  Returns (decoded image in [-1, 1], final latent, {"z_pre": ...}).
     ``inject``: the sampler's per-step noise comes from ``inp.noises`` (parity runs: the tensors the reference golden was made with);
-    False = `torch.randn_like` draws it on the GPU inside the pass, as the reference does (utils/sampler.py:199) — what bench.py times."""
+    False = `torch.randn_like` draws it on the GPU inside the pass, as the reference does (utils/sampler.py:199) — what bench.py times.
+    ``noise_source`` (an edtr_amd.rng.NoiseSource): every noise of the pass — q_sample, x_T of det512s50, the steps — is the seeded
+    per-image stream instead, drawn inside the kernels; ``inp.noises`` / ``inject`` are then not used."""
     import contextlib
     dev = inp.pre_res.device
     B = inp.pre_res.shape[0]
@@ -72,6 +74,16 @@ def restore_pass(cldm, diffusion, sampler, inp: Inputs, workload: str, untiled_f
     else:
         z_pre = cldm.vae_encode(inp.pre_res * 2 - 1, sample=False)
     cond = {"c_txt": inp.c_txt, "c_img": z_pre}
+    if noise_source is not None:
+        if workload == "det512s50":
+            z = sampler.sample(model=cldm, device=dev, steps=50, batch_size=B, x_size=(4, h, w), cond=cond, uncond=None, cfg_scale=1.0,
+                               x_T=None, progress=False, noise_source=noise_source)
+        else:
+            x_T = diffusion.q_sample(z_pre, inp.t_start, noise_source)
+            z = sampler.manual_sample_with_timesteps(
+                model=cldm, device=dev, x_T=x_T, steps=4, used_timesteps=USED_TIMESTEPS, batch_size=B, cond=cond, uncond=None,
+                cfg_scale=1.0, progress=False, tiled=tiled, tile_size=64, tile_stride=32, noise_source=noise_source)
+        return cldm.vae_decode(z), z, {"z_pre": z_pre}
     if workload == "det512s50":
         # DiffBIR-style: 50 spaced steps from pure noise; fresh torch.randn_like on the GPU per step unless a parity run injects it
         def run():

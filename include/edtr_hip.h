@@ -625,6 +625,48 @@ int edtr_axpby(const float* x, const float* y, float a, float b, float* out, int
  * reference model/gaussian_diffusion.py:34-37,80-84 as called with a device `t` at demo.py:107-108, main/det/test_edtr.py:127-128. */
 int edtr_q_sample(const float* x, const float* noise, const int64_t* t, const float* tab_a, const float* tab_b,
                   int n_tab, float* out, int B, int64_t per_image, edtr_stream_t stream);
+
+/* ---- Reproducible noise: a seeded per-image N(0, 1) stream evaluated inside the kernels that consume it ----------------------
+ * The value an element receives is a pure function of (seed, image id, purpose, draw, element offset inside the image): not of
+ * the batch the image travels in, its position there, or the number of devices that share a data set.  Normative definition
+ * (edtr_amd/rng.py restates it in numpy; tests on both sides of this ABI rely on it):
+ *   Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; multipliers 0xD2511F53, 0xCD9E8D57,
+ *   Weyl constants 0x9E3779B9, 0xBB67AE85, ten rounds)
+ *   key     = (seed & 0xffffffff, seed >> 32)
+ *   counter = (e >> 2, draw, purpose, image_id)   four uint32 words; e = the element's offset inside its image (NCHW:
+ *             (c*H + h)*W + w), image_id = the image's GLOBAL index (< 2^32), purpose = EDTR_NOISE_* below, draw = the sampler's
+ *             table row `index` for EDTR_NOISE_STEP and 0 for the other purposes
+ *   one call gives words x0..x3 and the normals of elements 4*(e>>2) + 0..3:
+ *             u1 = ((x0 >> 8) + 1) * 2^-24,  u2 = (x1 >> 8) * 2^-24,  r = sqrt(-2 ln u1),  z0 = r cos(2 pi u2),  z1 = r sin(2 pi u2);
+ *             z2, z3 the same from (x2, x3).  Both u are exact in fp32 and u1 is in (0, 1]: |z| <= sqrt(48 ln 2) = 5.77, no log(0).
+ * Common to the entries below: `seed` by value; the ids either as a device array image_ids[B] (int64, each in [0, 2^32): a
+ * captured launch is replayed for another batch by rewriting 8*B bytes) or, when image_ids == NULL, image_id_base + b.
+ * per_image % 4 == 0 and 16-byte aligned tensors (EDTR_E_ALIGN otherwise: one lane owns one group of four elements).
+ * Every fused form gives the bits of edtr_normal_fill followed by the tensor-noise entry it is named after. */
+#define EDTR_NOISE_Q_SAMPLE 0   /* Diffusion.q_sample noise */
+#define EDTR_NOISE_STEP 1       /* spaced-sampler step noise (draw = table row) */
+#define EDTR_NOISE_X_T 2        /* x_T of SpacedSampler.sample() */
+#define EDTR_NOISE_VAE 3        /* DiagonalGaussianDistribution.sample() of the VAE posterior */
+/* out[b][0 .. per_image) = the stream of image b, fp32.  replaces: torch.randn((B, *x_size)), utils/sampler.py:245. */
+int edtr_normal_fill(float* out, int B, int64_t per_image, uint64_t seed, const int64_t* image_ids, int64_t image_id_base,
+                     int purpose, int64_t draw, edtr_stream_t stream);
+/* edtr_q_sample with the noise operand replaced by the stream (EDTR_NOISE_Q_SAMPLE, draw 0). */
+int edtr_q_sample_rng(const float* x, const int64_t* t, const float* tab_a, const float* tab_b, int n_tab, float* out, int B,
+                      int64_t per_image, uint64_t seed, const int64_t* image_ids, int64_t image_id_base, edtr_stream_t stream);
+/* edtr_sampler_update with the noise operand replaced by the stream (EDTR_NOISE_STEP, the given draw).
+ * replaces: torch.randn_like(x) + the update, utils/sampler.py:199-203. */
+int edtr_sampler_update_rng(const float* x, const float* eps, float c_recip, float c_recipm1, float coef1, float coef2,
+                            float sigma, float* x_prev, float* pred_x0, int B, int64_t per_image, uint64_t seed,
+                            const int64_t* image_ids, int64_t image_id_base, int64_t draw, edtr_stream_t stream);
+/* edtr_sampler_update_indexed with the noise operand replaced by the stream; image b's draw is its (clamped) index[b], read on
+ * the device like its coefficient row, so a replayed launch needs no new argument per step. */
+int edtr_sampler_update_indexed_rng(const float* x, const float* eps, const int64_t* index, const float* coefs, int n_steps,
+                                    float* x_prev, float* pred_x0, int B, int64_t per_image, uint64_t seed,
+                                    const int64_t* image_ids, int64_t image_id_base, edtr_stream_t stream);
+/* edtr_gaussian_sample with the noise operand replaced by the stream (EDTR_NOISE_VAE, draw 0); per_image = C * HW. */
+int edtr_gaussian_sample_rng(const float* moments, int ld, float* out, int B, int C, int64_t HW, float scale, uint64_t seed,
+                             const int64_t* image_ids, int64_t image_id_base, edtr_stream_t stream);
+
 /* bf16 split-3 GEMM operand of a [rows][C] matrix (high-precision mode, see EDTR_F32_SPLIT): dst[rows][3*C] =
  * [hi | lo | hi] (pattern 0, the activation side) or [hi | hi | lo] (pattern 1, the weight side of an activation x activation
  * product).  src_dtype: EDTR_F32_SPLIT = fp32 source, EDTR_BF16 / EDTR_F16 = 16-bit source.  C, ld_src, ld_dst multiples of 8. */
