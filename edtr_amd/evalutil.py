@@ -1,7 +1,8 @@
 """Evaluation-harness helpers around the restoration path: host-side mirrors of the reference's
 batch padding (`utils/detection.py:141-165`) and PSNR metric (`utils/common.py:194-247`), plus an accelerate-free
 data-parallel driver that shards a list of pre-restored images over the ranks of `torch.distributed`, runs the
-edtr_amd path on each shard and reports PSNR.  Plain tensor bookkeeping: no kernels of their own."""
+edtr_amd path on each shard and reports PSNR.  The helpers up to `calculate_psnr_pt` are plain tensor bookkeeping on float tensors
+(today's path of `restore_dataset`, kept bit for bit); 8-bit images and the "seg" padding go through the launches of edtr_amd.imageio."""
 from __future__ import annotations
 
 from typing import List, Optional, Sequence, Tuple
@@ -66,11 +67,18 @@ def calculate_psnr_pt(img: torch.Tensor, img2: torch.Tensor, crop_border: int, t
     return 10.0 * torch.log10(1.0 / (mse + 1e-8))
 
 
+def _as_hwc(img):
+    """A uint8 (h, w, 3) image as it is; a float (C, h, w) tensor as its (h, w, C) view (imageio.ingest copies it as fp32)."""
+    from . import imageio
+    return img if imageio.is_u8_image(img) else img.permute(1, 2, 0)
+
+
 @torch.no_grad()
 def restore_dataset(cldm, diffusion, sampler, pre_restored: Sequence[torch.Tensor], gts: Optional[Sequence[torch.Tensor]] = None,
                     img_size: int = 512, batch_size: int = 8, used_timesteps=(50, 100, 150, 200), start_timestep: int = 200,
                     colour_fix: bool = True, swinir=None, pad_mode: str = "batch", multiple: int = 64,
-                    clamp: bool = True, seed: Optional[int] = None) -> Tuple[List[torch.Tensor], Optional[torch.Tensor]]:
+                    clamp: bool = True, *, return_uint8: bool = False,
+                    seed: Optional[int] = None) -> Tuple[List[torch.Tensor], Optional[torch.Tensor]]:
     """The restoration loop of main/det/test_edtr.py:121-135 without accelerate: this rank's shard of the
     (C, h, w <= img_size) pre-restored images is padded, pushed through vae_encode -> q_sample(t) -> spaced sampler ->
     vae_decode (-> wavelet colour fix), cropped back, and — when ground truth is given — scored with PSNR; the scalar
@@ -81,8 +89,14 @@ def restore_dataset(cldm, diffusion, sampler, pre_restored: Sequence[torch.Tenso
     (``clamp=False`` keeps the values the reference hands to `save_image`).  ``seed``: None = the noise comes from torch's generator
     as in the reference; an int = every image gets the seeded stream of its index in the GLOBAL ``pre_restored`` list
     (edtr_amd.rng), so its noise — and, with EDTR_AMD_BATCH_INVARIANT=1, its restoration bit for bit — does not depend on
-    ``batch_size``, ``pad_mode`` or the number of ranks.  Returns (restored images of this shard, mean PSNR or None)."""
+    ``batch_size``, ``pad_mode`` or the number of ranks.  ``pad_mode="seg"`` is the loop of main/seg/test_edtr.py:113-136: every image on
+    its own, replicate-padded at the bottom / right to multiples of ``multiple`` -> (SwinIR) -> the same path -> crop back; its chunking and
+    seeded ids are those of "demo".  Entries of ``pre_restored`` / ``gts`` may also be uint8 (h, w, 3) tensors or arrays — what an image
+    decoder returns: they are turned into v / 255 and padded on the device by `imageio.ingest` (the same bits as the float (C, h, w) form of
+    the same image), and PSNR against uint8 ground truth is `imageio.psnr`.  ``return_uint8=True`` (keyword only, so that ``seed``
+    stays the last parameter) returns `imageio.emit`'s uint8 (h, w, 3) bytes — what `save_image` would write — instead of float tensors.  Returns (restored images of this shard, mean PSNR or None)."""
     import torch.distributed as dist
+    from . import imageio
     from .wavelet import wavelet_reconstruction
     dev = next(cldm.unet.parameters()).device
     world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
@@ -90,14 +104,22 @@ def restore_dataset(cldm, diffusion, sampler, pre_restored: Sequence[torch.Tenso
     sl = shard_slice(rank, world, len(pre_restored))
     mine = list(pre_restored[sl])
     outs: List[torch.Tensor] = []
-    if pad_mode not in ("batch", "demo"):
-        raise ValueError(f"pad_mode must be 'batch' or 'demo', got {pad_mode!r}")
-    step = 1 if pad_mode == "demo" else batch_size
+    if pad_mode not in ("batch", "demo", "seg"):
+        raise ValueError(f"pad_mode must be 'batch', 'demo' or 'seg', got {pad_mode!r}")
+    step = 1 if pad_mode in ("demo", "seg") else batch_size
     chunk_ids = shard_chunk_ids(len(pre_restored), rank, world, batch_size, pad_mode) if seed is not None else None
     for i in range(0, len(mine), step):
         chunk = mine[i:i + step]
         source = NoiseSource(seed, chunk_ids[i // step]) if seed is not None else None
-        if pad_mode == "demo":
+        sizes = None                   # (h, w) per image where imageio.ingest built the batch; None = today's float path
+        if pad_mode == "seg":
+            pre, sizes = imageio.ingest([_as_hwc(chunk[0])], pad="replicate", multiple=multiple, device=dev)
+        elif imageio.is_u8_image(chunk[0]):
+            if pad_mode == "demo":
+                pre, sizes = imageio.ingest(chunk, min_size=img_size, multiple=multiple, device=dev)
+            else:
+                pre, sizes = imageio.ingest(chunk, size=(img_size, img_size), device=dev)
+        elif pad_mode == "demo":
             pre = pad_to_multiples_of(pad_if_smaller(chunk[0][None].to(dev).float(), img_size), multiple)
         else:
             pre = list_to_batch(chunk, img_size, dev).float()
@@ -113,13 +135,23 @@ def restore_dataset(cldm, diffusion, sampler, pre_restored: Sequence[torch.Tenso
         res = (cldm.vae_decode(z) + 1) / 2
         if colour_fix:
             res = wavelet_reconstruction(res, pre)
-        outs.extend(batch_to_list(res.clamp(0, 1) if clamp else res, chunk))
+        if return_uint8:           # (emit clamps: `clamp` has nothing left to decide)
+            outs.extend(imageio.emit(res.float().contiguous(), sizes or [(img.size(1), img.size(2)) for img in chunk]))
+        elif sizes is None:
+            outs.extend(batch_to_list(res.clamp(0, 1) if clamp else res, chunk))
+        else:
+            res = res.clamp(0, 1) if clamp else res
+            outs.extend(res[k][:, :h, :w] for k, (h, w) in enumerate(sizes))
     psnr = None
     if gts is not None:
         mine_gt = list(gts[sl])
         acc = torch.zeros(2, dtype=torch.float64, device=dev)
         for o, g in zip(outs, mine_gt):
-            acc[0] += calculate_psnr_pt(o[None].float(), g[None].to(dev).float(), crop_border=0)[0]
+            if imageio.is_u8_image(g) or return_uint8:
+                a, _ = imageio.ingest([o if return_uint8 else o.permute(1, 2, 0)], device=dev)
+                acc[0] += imageio.psnr(a, imageio.ingest([_as_hwc(g)], device=dev)[0], crop_border=0)[0]
+            else:
+                acc[0] += calculate_psnr_pt(o[None].float(), g[None].to(dev).float(), crop_border=0)[0]
             acc[1] += 1
         if world > 1:
             dist.all_reduce(acc)

@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("EDTR_AMD_LIB") or os.path.join(HERE, "libedtr_hip.so"
 
 BF16, F16, F32_SPLIT, F32_H1, F32_H2, F32_H3 = 0, 1, 2, 3, 4, 5
 ACT_NONE, ACT_GEGLU, ACT_SILU, ACT_GELU, ACT_LRELU = 0, 1, 2, 3, 4
+SQDIFF_BLOCKS = 64          # EDTR_SQDIFF_BLOCKS: fp64 partial sums per image of edtr_image_sqdiff
 
 DECLARED_SYMBOLS = [
     "edtr_abi_version", "edtr_error_string", "edtr_device_info", "edtr_igemm", "edtr_flash_attn64",
@@ -21,6 +22,7 @@ DECLARED_SYMBOLS = [
     "edtr_split_operand", "edtr_sampler_update_indexed", "edtr_gaussian_sample", "edtr_add_mirror", "edtr_igemm_plan", "edtr_flash_attn512",
     "edtr_ffn", "edtr_ffn_plan", "edtr_add_stats", "edtr_lin320", "edtr_lin320_plan",
     "edtr_normal_fill", "edtr_q_sample_rng", "edtr_sampler_update_rng", "edtr_sampler_update_indexed_rng", "edtr_gaussian_sample_rng",
+    "edtr_image_resize_u8", "edtr_image_ingest", "edtr_image_emit", "edtr_image_sqdiff",
 ]
 
 
@@ -249,6 +251,11 @@ def load() -> C.CDLL:
     lib.edtr_sampler_update_rng.argtypes = [vp, vp, f32, f32, f32, f32, f32, vp, vp, i32, i64, u64, vp, i64, i64, vp]
     lib.edtr_sampler_update_indexed_rng.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, i64, u64, vp, i64, vp]
     lib.edtr_gaussian_sample_rng.argtypes = [vp, i32, vp, i32, i32, i64, f32, u64, vp, i64, vp]
+    # the 8-bit image boundary (edtr_hip.h "Images in, images out")
+    lib.edtr_image_resize_u8.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp]
+    lib.edtr_image_ingest.argtypes = [i32, vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp]
+    lib.edtr_image_emit.argtypes = [vp, i32, i32, i32, i32, i32, vp, i32, i32, vp]
+    lib.edtr_image_sqdiff.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp]
     if lib.edtr_abi_version() != 10:
         raise RuntimeError("libedtr_hip.so ABI version mismatch")
     _lib = lib

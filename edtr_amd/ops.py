@@ -713,6 +713,40 @@ def make_gaussian_sample_rng(*, moments, ld, source, out, B, C, HW, scale, name=
     return Rec(L.load().edtr_gaussian_sample_rng, args, (moments, out, ids), name, 0.0, 12.0 * B * C * HW)
 
 
+# -- the 8-bit image boundary (edtr_hip.h "Images in, images out"; the callers and the host restatements are edtr_amd/imageio.py) -----
+def make_image_resize_u8(*, src, dst, h_tab=None, v_tab=None, tmp=None, name="image.resize_u8") -> Rec:
+    """uint8 [in_h, in_w, 3] -> uint8 [out_h, out_w, 3]; ``h_tab`` / ``v_tab`` = (bounds int32 [out, 2], coefs int32 [out, k]) device
+    tensors of the pass (None for an axis that keeps its size); ``tmp`` uint8 [in_h, out_w, 3] when both passes run."""
+    (in_h, in_w, ch), (out_h, out_w, _) = src.shape, dst.shape
+    hb, hc = h_tab if h_tab is not None else (None, None)
+    vb, vc = v_tab if v_tab is not None else (None, None)
+    args = (ptr(src), in_h, in_w, ch, ptr(dst), out_h, out_w, ptr(hb), ptr(hc), hc.shape[1] if hc is not None else 0,
+            ptr(vb), ptr(vc), vc.shape[1] if vc is not None else 0, ptr(tmp))
+    return Rec(L.load().edtr_image_resize_u8, args, (src, dst, hb, hc, vb, vc, tmp), name, 0.0, 3.0 * (in_h * in_w + 2 * in_h * out_w + out_h * out_w))
+
+
+def make_image_ingest(*, src, batch, b: int, replicate: bool, table, name="image.ingest") -> Rec:
+    """``src`` uint8 or fp32 [h, w, 3] -> slot ``b`` of fp32 ``batch`` [B, 3, H, W], zero- or replicate-padded."""
+    h, w, ch = src.shape
+    B, _, H, W = batch.shape
+    args = (int(src.dtype == torch.float32), ptr(src), h, w, ch, ptr(batch), b, B, H, W, int(replicate), ptr(table))
+    return Rec(L.load().edtr_image_ingest, args, (src, batch, table), name, 0.0, float(src.element_size() * 3 * h * w + 12 * H * W))
+
+
+def make_image_emit(*, batch, b: int, dst, name="image.emit") -> Rec:
+    """the top-left [h, w] crop of image ``b`` of fp32 ``batch`` [B, 3, H, W] -> uint8 ``dst`` [h, w, 3]."""
+    B, ch, H, W = batch.shape
+    h, w, _ = dst.shape
+    return Rec(L.load().edtr_image_emit, (ptr(batch), b, B, ch, H, W, ptr(dst), h, w), (batch, dst), name, 0.0, 15.0 * h * w)
+
+
+def make_image_sqdiff(*, a, b, sizes, crop_border: int, y_channel: bool, partials, out, name="image.sqdiff") -> Rec:
+    """fp64 ``out`` [B] = per-image sums of squared differences of fp32 [B, 3, H, W] batches (``sizes``: int32 [B, 2] device or None)."""
+    B, ch, H, W = a.shape
+    args = (ptr(a), ptr(b), B, ch, H, W, ptr(sizes), int(crop_border), int(y_channel), ptr(partials), ptr(out))
+    return Rec(L.load().edtr_image_sqdiff, args, (a, b, sizes, partials, out), name, 0.0, 24.0 * B * H * W)
+
+
 def make_cast16(*, dtype, src: torch.Tensor, rows: int, C: int, dst: torch.Tensor, name="cast16") -> Rec:
     args = (dt_code(dtype), ptr(src), rows, C, src.stride(0), ptr(dst), dst.stride(0))
     return Rec(L.load().edtr_cast16, args, (src, dst), name, 0.0, 6.0 * rows * C)

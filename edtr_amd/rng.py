@@ -89,12 +89,12 @@ def normal_reference(seed: int, image_ids, purpose: int, draw, per_image: int) -
 
 def shard_chunk_ids(n_images: int, rank: int, world: int, batch_size: int, pad_mode: str = "batch") -> List[List[int]]:
     """The global image ids of every chunk that `evalutil.restore_dataset` runs on this rank: its `shard_slice` of the
-    ``n_images`` inputs cut into chunks of ``batch_size`` (of 1 for pad_mode="demo").  Image k of the data set has id k
+    ``n_images`` inputs cut into chunks of ``batch_size`` (of 1 for pad_mode="demo" and "seg").  Image k of the data set has id k
     whatever the rank count and the chunking, which is what makes a seeded restoration independent of both."""
     from .parallel import shard_slice
-    if pad_mode not in ("batch", "demo"):
-        raise ValueError(f"pad_mode must be 'batch' or 'demo', got {pad_mode!r}")
-    step = 1 if pad_mode == "demo" else int(batch_size)
+    if pad_mode not in ("batch", "demo", "seg"):
+        raise ValueError(f"pad_mode must be 'batch', 'demo' or 'seg', got {pad_mode!r}")
+    step = 1 if pad_mode in ("demo", "seg") else int(batch_size)
     if step <= 0:
         raise ValueError(f"batch_size must be positive, got {batch_size}")
     sl = shard_slice(rank, world, n_images)

@@ -705,6 +705,42 @@ int edtr_copy3d_f32(const float* src, int64_t src_plane_stride, int64_t src_row_
 int edtr_wavelet_level(const float* in, float* low, float* high_accum, int planes, int H, int W, int radius,
                        edtr_stream_t stream);
 
+/* ---- Images in, images out: the 8-bit boundary around the fp32 NCHW batches -----------------------------------------------------
+ * The reference's callers start and end with 8-bit images (demo.py:79-90,165; main/seg/test_edtr.py:113-115,136; calculate_psnr_pt
+ * in main/{cls,det,seg}/test_edtr.py).  Images here are interleaved HWC with `channels` == 3 (EDTR_E_UNSUPPORTED otherwise);
+ * batches are fp32 NCHW [B][3][H][W].  Three exactness rules (edtr_amd/imageio.py restates each in numpy):
+ *   resize   = Pillow's Image.resize(size, BICUBIC) bit for bit: 22-bit fixed-point coefficients, int32 accumulation from 1 << 21,
+ *              clamp(acc >> 22, 0, 255), horizontal pass then vertical pass with a uint8 intermediate
+ *   ingest   = float32(float64(v) / 255.0), read from a 256-entry table the host builds that way (no device division)
+ *   emit     = trunc(clamp(x * 255 + 0.5, 0, 255)) with the product and the sum each rounded to fp32 (never an FMA); NaN gives 0
+ * Rows are moved as dwords / float4 where the pitch keeps them aligned (w % 4 == 0, W % 4 == 0) and element by element otherwise:
+ * no extent or pointer needs more than its natural alignment. */
+/* src [in_h][in_w][3] -> dst [out_h][out_w][3], uint8.  Per output column x: h_bounds[2 x] = first source column, h_bounds[2 x + 1]
+ * = n <= h_ksize taps, h_coefs[x * h_ksize + 0 .. n) their int32 coefficients; v_* the same per output row.  A pass whose extent
+ * does not change is skipped and its tables may be NULL.  tmp: [in_h][out_w][3] bytes, needed when both passes run.  The windows
+ * are forced inside the source on the device.  replaces: PIL.Image.resize(..., Image.BICUBIC), demo.py:80-84. */
+int edtr_image_resize_u8(const uint8_t* src, int in_h, int in_w, int channels, uint8_t* dst, int out_h, int out_w,
+                         const int32_t* h_bounds, const int32_t* h_coefs, int h_ksize, const int32_t* v_bounds,
+                         const int32_t* v_coefs, int v_ksize, uint8_t* tmp, edtr_stream_t stream);
+/* One source image [h][w][3] (uint8, or fp32 when src_f32 = 1: copied) into the top-left corner of slot b of batch [B][3][H][W];
+ * the rest of the slot is zero (replicate = 0: F.pad mode 'constant') or repeats the last row / column (replicate = 1: mode
+ * 'replicate').  table: fp32 [256] on the device (uint8 sources).  replaces: np.array(img) / 255.0 -> rearrange -> pad_if_smaller
+ * -> pad_to_multiples_of, demo.py:85-90; F.pad(..., mode='replicate'), main/seg/test_edtr.py:113-115. */
+int edtr_image_ingest(int src_f32, const void* src, int h, int w, int channels, float* batch, int b, int B, int H, int W,
+                      int replicate, const float* table, edtr_stream_t stream);
+/* The top-left h x w crop of image b of batch [B][3][H][W] -> dst [h][w][3] uint8 with the emit rule above.
+ * replaces: res[:, :h0, :w0] -> torchvision save_image's mul(255).add_(0.5).clamp_(0, 255).to(uint8), demo.py:165. */
+int edtr_image_emit(const float* batch, int b, int B, int channels, int H, int W, uint8_t* dst, int h, int w, edtr_stream_t stream);
+/* out[i] (fp64) = the sum of squared differences of images i of a and b ([B][3][H][W] fp32) over rows [crop_border, h_i -
+ * crop_border) and columns [crop_border, w_i - crop_border), (h_i, w_i) = sizes[2 i], sizes[2 i + 1] (device int32, clamped to
+ * H, W; NULL = H, W): over the three planes (y_channel = 0), or over the BT.601 luma (65.481 r + 128.553 g + 24.966 b + 16) / 255
+ * formed in fp64 (y_channel = 1).  Accumulated in fp64 in an order fixed by the shapes: EDTR_SQDIFF_BLOCKS partial sums per image
+ * (partials: fp64 [B][EDTR_SQDIFF_BLOCKS], overwritten), then one finishing workgroup; no atomics, equal bits on every run.  The
+ * caller forms 10 log10(1 / (out / count + 1e-8)).  replaces: calculate_psnr_pt, utils/common.py:219-247. */
+#define EDTR_SQDIFF_BLOCKS 64
+int edtr_image_sqdiff(const float* a, const float* b, int B, int channels, int H, int W, const int32_t* sizes, int crop_border,
+                      int y_channel, double* partials, double* out, edtr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * hipGraph capture of a launch sequence issued on `stream` (one denoise step, or a whole batch).
  * ---------------------------------------------------------------------------------------- */
