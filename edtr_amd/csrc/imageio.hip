@@ -307,7 +307,222 @@ inline unsigned blocks_for(int64_t n) {
     return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
 }
 
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+__host__ __device__ inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+// ---- the ragged batch forms: workgroup column blockIdx.y works on image blockIdx.y of a device array of edtr_image_desc ----------
+// Every choice that a per-image entry point makes on the host (which passes run, the dword forms) is made here per image from its
+// descriptor; it is uniform over a workgroup.  The arithmetic is that of resize_h_kernel / resize_v_kernel / ingest_kernel /
+// emit_kernel, through the same window / clip8 / quant8 and the same table.
+
+// the twelve bytes of pixels 4 g .. 4 g + 3 of one output row of the horizontal pass
+template <bool VEC>
+__device__ __forceinline__ void resize_h_group(const uint8_t* line, uint8_t* o, int x0, int in_w, int out_w, const int32_t* bounds,
+                                               const int32_t* coefs, int ksize) {
+    uint32_t px[4][3];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        int a0 = 1 << (kPrecisionBits - 1), a1 = a0, a2 = a0;
+        if (x0 + j < out_w) {
+            int lo, n;
+            window(bounds, x0 + j, in_w, ksize, lo, n);
+            const int32_t* k = coefs + (int64_t)(x0 + j) * ksize;
+            const uint8_t* p = line + lo * 3;
+            for (int t = 0; t < n; ++t) {
+                const int c = k[t];
+                a0 += (int)p[3 * t] * c;
+                a1 += (int)p[3 * t + 1] * c;
+                a2 += (int)p[3 * t + 2] * c;
+            }
+        }
+        px[j][0] = clip8(a0), px[j][1] = clip8(a1), px[j][2] = clip8(a2);
+    }
+    if (VEC) {
+        uint32_t* o32 = reinterpret_cast<uint32_t*>(o);
+        o32[0] = px[0][0] | px[0][1] << 8 | px[0][2] << 16 | px[1][0] << 24;
+        o32[1] = px[1][1] | px[1][2] << 8 | px[2][0] << 16 | px[2][1] << 24;
+        o32[2] = px[2][2] | px[3][0] << 8 | px[3][1] << 16 | px[3][2] << 24;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (x0 + j < out_w) {
+                o[3 * j] = (uint8_t)px[j][0];
+                o[3 * j + 1] = (uint8_t)px[j][1];
+                o[3 * j + 2] = (uint8_t)px[j][2];
+            }
+    }
+}
+
+// does image d run a horizontal / vertical pass, and does its horizontal result [in_h][out_w][3] lie inside the scratch buffer?
+__device__ __forceinline__ bool desc_horiz(const edtr_image_desc& d) { return d.out_w != d.in_w; }
+__device__ __forceinline__ bool desc_vert(const edtr_image_desc& d) { return d.out_h != d.in_h; }
+__device__ __forceinline__ bool desc_sane(const edtr_image_desc& d, int64_t tmp_bytes, const uint8_t* tmp) {
+    if (!d.src || d.in_h <= 0 || d.in_w <= 0 || d.out_h <= 0 || d.out_w <= 0) return false;
+    if (desc_horiz(d)) {
+        if (!d.h_bounds || !d.h_coefs || d.h_ksize <= 0 || !tmp) return false;
+        if (d.tmp_offset < 0 || d.tmp_offset + (int64_t)d.in_h * d.out_w * 3 > tmp_bytes) return false;
+    }
+    if (desc_vert(d) && (!d.v_bounds || !d.v_coefs || d.v_ksize <= 0)) return false;
+    return true;
+}
+
+// horizontal pass of every image that has one: src [in_h][in_w][3] -> tmp + tmp_offset [in_h][out_w][3]
+__global__ void __launch_bounds__(256) resize_h_batch_kernel(const edtr_image_desc* descs, uint8_t* tmp, int64_t tmp_bytes) {
+    const edtr_image_desc d = descs[blockIdx.y];
+    if (!desc_sane(d, tmp_bytes, tmp) || !desc_horiz(d)) return;
+    uint8_t* dst = tmp + d.tmp_offset;
+    const bool vec = d.out_w % 4 == 0 && aligned4(dst);
+    const int groups = (d.out_w + 3) >> 2;
+    const int64_t total = (int64_t)d.in_h * groups;
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
+        const int y = (int)(g / groups), x0 = (int)(g - (int64_t)y * groups) << 2;
+        const uint8_t* line = d.src + (int64_t)y * d.in_w * 3;
+        uint8_t* o = dst + ((int64_t)y * d.out_w + x0) * 3;
+        if (vec) resize_h_group<true>(line, o, x0, d.in_w, d.out_w, d.h_bounds, d.h_coefs, d.h_ksize);
+        else resize_h_group<false>(line, o, x0, d.in_w, d.out_w, d.h_bounds, d.h_coefs, d.h_ksize);
+    }
+}
+
+// vertical pass (or none) -> table -> slot d.b, padding included: a lane owns pixels 4 g .. 4 g + 3 of one row of the H x W slot in
+// all three planes.  The source S [in_h][out_w][3] is the horizontal result where that pass ran, the image itself otherwise.  A slot
+// position outside the image takes 0 (replicate = 0) or the value of the nearest image pixel (replicate = 1), which is computed again
+// from the same window.  VEC_DST: W % 4 == 0 and a 16-byte aligned batch (per launch); the dword reads of S are chosen per image.
+template <bool VEC_DST>
+__global__ void __launch_bounds__(256) resize_ingest_batch_kernel(const edtr_image_desc* descs, const uint8_t* tmp, int64_t tmp_bytes,
+                                                                  float* batch, int B, int H, int W, int replicate, const float* table) {
+    __shared__ float tab[256];
+    tab[threadIdx.x] = table[threadIdx.x];
+    __syncthreads();
+    const edtr_image_desc d = descs[blockIdx.y];
+    if (!desc_sane(d, tmp_bytes, tmp) || d.b < 0 || d.b >= B || d.out_h > H || d.out_w > W) return;
+    const uint8_t* S = desc_horiz(d) ? tmp + d.tmp_offset : d.src;
+    const bool vert = desc_vert(d);
+    const int h = d.out_h, w = d.out_w, row_bytes = w * 3;
+    const bool vec_src = row_bytes % 4 == 0 && aligned4(S);
+    const int groups = (W + 3) >> 2;
+    const int64_t total = (int64_t)H * groups, plane = (int64_t)H * W;
+    float* slot = batch + (int64_t)d.b * 3 * plane;
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
+        const int y = (int)(g / groups), x0 = (int)(g - (int64_t)y * groups) << 2;
+        const int ys = y < h ? y : h - 1;
+        int lo = ys, n = 1;
+        const int32_t* k = nullptr;
+        if (vert) {
+            window(d.v_bounds, ys, d.in_h, d.v_ksize, lo, n);
+            k = d.v_coefs + (int64_t)ys * d.v_ksize;
+        }
+        uint32_t q[4][3];                               // the bytes of the four pixels
+        const bool whole = x0 + 3 < w;                  // all four pixels inside the image's columns (the row is ys)
+        if (!replicate && (y >= h || x0 >= w)) {        // all four in the zero padding
+#pragma unroll
+            for (int j = 0; j < 4; ++j) q[j][0] = q[j][1] = q[j][2] = 0u;
+        } else if (whole && vec_src) {
+            const uint8_t* p = S + (int64_t)lo * row_bytes + x0 * 3;
+            if (vert) {
+                int a[12];
+#pragma unroll
+                for (int e = 0; e < 12; ++e) a[e] = 1 << (kPrecisionBits - 1);
+                for (int t = 0; t < n; ++t) {
+                    const uint32_t* s = reinterpret_cast<const uint32_t*>(p + (int64_t)t * row_bytes);
+                    const uint32_t v0 = s[0], v1 = s[1], v2 = s[2];
+                    const int c = k[t];
+                    a[0] += (int)(v0 & 255u) * c, a[1] += (int)((v0 >> 8) & 255u) * c, a[2] += (int)((v0 >> 16) & 255u) * c, a[3] += (int)(v0 >> 24) * c;
+                    a[4] += (int)(v1 & 255u) * c, a[5] += (int)((v1 >> 8) & 255u) * c, a[6] += (int)((v1 >> 16) & 255u) * c, a[7] += (int)(v1 >> 24) * c;
+                    a[8] += (int)(v2 & 255u) * c, a[9] += (int)((v2 >> 8) & 255u) * c, a[10] += (int)((v2 >> 16) & 255u) * c, a[11] += (int)(v2 >> 24) * c;
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) q[j][0] = clip8(a[3 * j]), q[j][1] = clip8(a[3 * j + 1]), q[j][2] = clip8(a[3 * j + 2]);
+            } else {
+                const uint32_t* s = reinterpret_cast<const uint32_t*>(p);
+                const uint32_t d0 = s[0], d1 = s[1], d2 = s[2];
+                q[0][0] = d0 & 255u, q[0][1] = (d0 >> 8) & 255u, q[0][2] = (d0 >> 16) & 255u;
+                q[1][0] = d0 >> 24, q[1][1] = d1 & 255u, q[1][2] = (d1 >> 8) & 255u;
+                q[2][0] = (d1 >> 16) & 255u, q[2][1] = d1 >> 24, q[2][2] = d2 & 255u;
+                q[3][0] = (d2 >> 8) & 255u, q[3][1] = (d2 >> 16) & 255u, q[3][2] = d2 >> 24;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int x = x0 + j;
+                const int xs = x < w ? x : w - 1;
+                const uint8_t* p = S + (int64_t)lo * row_bytes + xs * 3;
+                if (vert) {
+                    int a0 = 1 << (kPrecisionBits - 1), a1 = a0, a2 = a0;
+                    for (int t = 0; t < n; ++t) {
+                        const uint8_t* s = p + (int64_t)t * row_bytes;
+                        const int c = k[t];
+                        a0 += (int)s[0] * c;
+                        a1 += (int)s[1] * c;
+                        a2 += (int)s[2] * c;
+                    }
+                    q[j][0] = clip8(a0), q[j][1] = clip8(a1), q[j][2] = clip8(a2);
+                } else {
+                    q[j][0] = p[0], q[j][1] = p[1], q[j][2] = p[2];
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = (replicate || (y < h && x0 + j < w)) ? tab[q[j][c]] : 0.0f;
+            float* o = slot + c * plane + (int64_t)y * W + x0;
+            if (VEC_DST) {
+                *reinterpret_cast<f32x4*>(o) = f32x4{v[0], v[1], v[2], v[3]};
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (x0 + j < W) o[j] = v[j];
+            }
+        }
+    }
+}
+
+// crop i of the table: image b's top-left h x w -> dst + offset, uint8 HWC.  table[i] = (b, h, w, byte offset), int64.
+// VEC_SRC: W % 4 == 0 and a 16-byte aligned batch (per launch); the dword stores are chosen per crop.
+template <bool VEC_SRC>
+__global__ void __launch_bounds__(256) emit_batch_kernel(const float* batch, int B, int H, int W, const int64_t* table, uint8_t* dst,
+                                                         int64_t dst_bytes) {
+    const int64_t* row = table + 4 * (int64_t)blockIdx.y;
+    const int64_t b = row[0], off = row[3];
+    if (b < 0 || b >= B || row[1] <= 0 || row[2] <= 0 || row[1] > H || row[2] > W) return;
+    const int h = (int)row[1], w = (int)row[2];
+    if (off < 0 || off + (int64_t)h * w * 3 > dst_bytes) return;
+    uint8_t* out = dst + off;
+    const bool vec_dst = w % 4 == 0 && aligned4(out);
+    const int groups = (w + 3) >> 2;
+    const int64_t total = (int64_t)h * groups, plane = (int64_t)H * W;
+    const float* slot = batch + b * 3 * plane;
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
+        const int y = (int)(g / groups), x0 = (int)(g - (int64_t)y * groups) << 2;
+        uint32_t q[4][3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float* s = slot + c * plane + (int64_t)y * W + x0;
+            if (VEC_SRC) {      // x0 + 3 < W always: x0 < w <= W and both W and x0 are multiples of 4
+                const f32x4 v = *reinterpret_cast<const f32x4*>(s);
+                q[0][c] = quant8(v.x), q[1][c] = quant8(v.y), q[2][c] = quant8(v.z), q[3][c] = quant8(v.w);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) q[j][c] = x0 + j < w ? quant8(s[j]) : 0u;
+            }
+        }
+        uint8_t* o = out + ((int64_t)y * w + x0) * 3;
+        if (vec_dst) {
+            uint32_t* o32 = reinterpret_cast<uint32_t*>(o);
+            o32[0] = q[0][0] | q[0][1] << 8 | q[0][2] << 16 | q[1][0] << 24;
+            o32[1] = q[1][1] | q[1][2] << 8 | q[2][0] << 16 | q[2][1] << 24;
+            o32[2] = q[2][2] | q[3][0] << 8 | q[3][1] << 16 | q[3][2] << 24;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (x0 + j < w) {
+                    o[3 * j] = (uint8_t)q[j][0];
+                    o[3 * j + 1] = (uint8_t)q[j][1];
+                    o[3 * j + 2] = (uint8_t)q[j][2];
+                }
+        }
+    }
+}
 
 }  // namespace
 
@@ -399,6 +614,93 @@ extern "C" int edtr_image_emit(const float* batch, int b, int B, int channels, i
     else if (vs) hipLaunchKernelGGL((emit_kernel<true, false>), grid, block, 0, st, slot, H, W, dst, h, w);
     else if (vd) hipLaunchKernelGGL((emit_kernel<false, true>), grid, block, 0, st, slot, H, W, dst, h, w);
     else hipLaunchKernelGGL((emit_kernel<false, false>), grid, block, 0, st, slot, H, W, dst, h, w);
+    EDTR_LAUNCH_CHECK();
+    return EDTR_OK;
+}
+
+// the host copy of the descriptors is what the arguments are checked on (and what sizes the grid); the kernels read the device copy
+static int check_descs(const edtr_image_desc* d, int B, const uint8_t* tmp, int64_t tmp_bytes, int64_t* max_h_groups) {
+    int64_t mh = 0;
+    for (int i = 0; i < B; ++i) {
+        if (!d[i].src) return EDTR_E_NULL;
+        if (d[i].in_h <= 0 || d[i].in_w <= 0 || d[i].out_h <= 0 || d[i].out_w <= 0) return EDTR_E_SHAPE;
+        if (d[i].in_h > (1 << 24) || d[i].in_w > (1 << 24) || d[i].out_h > (1 << 24) || d[i].out_w > (1 << 24)) return EDTR_E_UNSUPPORTED;
+        const bool horiz = d[i].out_w != d[i].in_w, vert = d[i].out_h != d[i].in_h;
+        if (horiz && (!d[i].h_bounds || !d[i].h_coefs || !tmp)) return EDTR_E_NULL;
+        if (vert && (!d[i].v_bounds || !d[i].v_coefs)) return EDTR_E_NULL;
+        if ((horiz && d[i].h_ksize <= 0) || (vert && d[i].v_ksize <= 0)) return EDTR_E_SHAPE;
+        if ((reinterpret_cast<uintptr_t>(d[i].h_bounds) | reinterpret_cast<uintptr_t>(d[i].h_coefs) |
+             reinterpret_cast<uintptr_t>(d[i].v_bounds) | reinterpret_cast<uintptr_t>(d[i].v_coefs)) & 3u)
+            return EDTR_E_ALIGN;
+        if (horiz) {
+            const int64_t bytes = (int64_t)d[i].in_h * d[i].out_w * 3;
+            if (d[i].tmp_offset < 0 || d[i].tmp_offset + bytes > tmp_bytes) return EDTR_E_SHAPE;
+            const int64_t groups = (int64_t)d[i].in_h * ((d[i].out_w + 3) / 4);
+            mh = groups > mh ? groups : mh;
+        }
+    }
+    *max_h_groups = mh;
+    return EDTR_OK;
+}
+
+extern "C" int edtr_image_resize_h_batch(const edtr_image_desc* descs_host, const edtr_image_desc* descs, int B, int channels,
+                                         uint8_t* tmp, int64_t tmp_bytes, edtr_stream_t stream) {
+    if (channels != 3) return EDTR_E_UNSUPPORTED;
+    if (!descs_host || !descs) return EDTR_E_NULL;
+    if (B <= 0 || B > 65535 || tmp_bytes < 0) return EDTR_E_SHAPE;
+    if (reinterpret_cast<uintptr_t>(descs) & 7u) return EDTR_E_ALIGN;
+    int64_t groups = 0;
+    const int rc = check_descs(descs_host, B, tmp, tmp_bytes, &groups);
+    if (rc != EDTR_OK) return rc;
+    if (groups == 0) return EDTR_OK;                    // no image has a horizontal pass: nothing to launch
+    hipLaunchKernelGGL(resize_h_batch_kernel, dim3(blocks_for(groups), B), dim3(256), 0, static_cast<hipStream_t>(stream), descs, tmp, tmp_bytes);
+    EDTR_LAUNCH_CHECK();
+    return EDTR_OK;
+}
+
+extern "C" int edtr_image_resize_ingest_batch(const edtr_image_desc* descs_host, const edtr_image_desc* descs, int B, int channels,
+                                              const uint8_t* tmp, int64_t tmp_bytes, float* batch, int slots, int H, int W,
+                                              int replicate, const float* table, edtr_stream_t stream) {
+    if (channels != 3) return EDTR_E_UNSUPPORTED;
+    if (!descs_host || !descs || !batch || !table) return EDTR_E_NULL;
+    if (B <= 0 || B > 65535 || slots <= 0 || H <= 0 || W <= 0 || tmp_bytes < 0) return EDTR_E_SHAPE;
+    if (replicate != 0 && replicate != 1) return EDTR_E_DTYPE;
+    if ((reinterpret_cast<uintptr_t>(descs) & 7u) || (reinterpret_cast<uintptr_t>(batch) & 3u) || (reinterpret_cast<uintptr_t>(table) & 3u))
+        return EDTR_E_ALIGN;
+    int64_t groups = 0;
+    const int rc = check_descs(descs_host, B, tmp, tmp_bytes, &groups);
+    if (rc != EDTR_OK) return rc;
+    for (int i = 0; i < B; ++i)
+        if (descs_host[i].b < 0 || descs_host[i].b >= slots || descs_host[i].out_h > H || descs_host[i].out_w > W) return EDTR_E_SHAPE;
+    const dim3 grid(blocks_for((int64_t)H * ((W + 3) / 4)), B), block(256);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (W % 4 == 0 && aligned16(batch))
+        hipLaunchKernelGGL(resize_ingest_batch_kernel<true>, grid, block, 0, st, descs, tmp, tmp_bytes, batch, slots, H, W, replicate, table);
+    else
+        hipLaunchKernelGGL(resize_ingest_batch_kernel<false>, grid, block, 0, st, descs, tmp, tmp_bytes, batch, slots, H, W, replicate, table);
+    EDTR_LAUNCH_CHECK();
+    return EDTR_OK;
+}
+
+extern "C" int edtr_image_emit_batch(const float* batch, int B, int channels, int H, int W, const int64_t* table_host,
+                                     const int64_t* table, int n, uint8_t* dst, int64_t dst_bytes, edtr_stream_t stream) {
+    if (channels != 3) return EDTR_E_UNSUPPORTED;
+    if (!batch || !table_host || !table || !dst) return EDTR_E_NULL;
+    if (B <= 0 || n <= 0 || n > 65535 || H <= 0 || W <= 0 || dst_bytes < 0) return EDTR_E_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(batch) & 3u) || (reinterpret_cast<uintptr_t>(table) & 7u)) return EDTR_E_ALIGN;
+    int64_t groups = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t b = table_host[4 * i], h = table_host[4 * i + 1], w = table_host[4 * i + 2], off = table_host[4 * i + 3];
+        if (b < 0 || b >= B || h <= 0 || w <= 0 || h > H || w > W) return EDTR_E_SHAPE;
+        if (off < 0 || off + h * w * 3 > dst_bytes) return EDTR_E_SHAPE;
+        if (off & 3) return EDTR_E_ALIGN;
+        const int64_t gi = h * ((w + 3) / 4);
+        groups = gi > groups ? gi : groups;
+    }
+    const dim3 grid(blocks_for(groups), n), block(256);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (W % 4 == 0 && aligned16(batch)) hipLaunchKernelGGL(emit_batch_kernel<true>, grid, block, 0, st, batch, B, H, W, table, dst, dst_bytes);
+    else hipLaunchKernelGGL(emit_batch_kernel<false>, grid, block, 0, st, batch, B, H, W, table, dst, dst_bytes);
     EDTR_LAUNCH_CHECK();
     return EDTR_OK;
 }

@@ -10,7 +10,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from .parallel import shard_slice
-from .rng import NoiseSource, shard_chunk_ids
+from .rng import NoiseSource, shard_bucket_ids, shard_chunk_ids
 
 
 def list_to_batch(img_list: Sequence[torch.Tensor], img_size: int, device) -> torch.Tensor:
@@ -73,6 +73,35 @@ def _as_hwc(img):
     return img if imageio.is_u8_image(img) else img.permute(1, 2, 0)
 
 
+def _image_hw(img) -> Tuple[int, int]:
+    """(h, w) of a uint8 (h, w, 3) image or of a float (C, h, w) tensor"""
+    from . import imageio
+    return (int(img.shape[0]), int(img.shape[1])) if imageio.is_u8_image(img) else (int(img.shape[1]), int(img.shape[2]))
+
+
+@torch.no_grad()
+def restore_batch(cldm, diffusion, sampler, pre: torch.Tensor, source: Optional[NoiseSource] = None,
+                  used_timesteps=(50, 100, 150, 200), start_timestep: int = 200, colour_fix: bool = True, swinir=None) -> torch.Tensor:
+    """One padded fp32 (B, 3, H, W) batch through (SwinIR ->) prepare_condition -> q_sample(start_timestep) -> spaced sampler ->
+    vae_decode (-> wavelet colour fix): what `restore_dataset` runs on every chunk, whatever built the batch.  ``source``: the seeded
+    noise of the batch's images, or None for torch's generator."""
+    from .wavelet import wavelet_reconstruction
+    dev = pre.device
+    if swinir is not None:
+        pre = swinir(pre)
+    cond = cldm.prepare_condition(pre, [""] * pre.size(0))
+    t = torch.full((pre.size(0),), start_timestep, dtype=torch.int64)
+    x_T = diffusion.q_sample(cond["c_img"], t, torch.randn_like(cond["c_img"]) if source is None else source)
+    z = sampler.manual_sample_with_timesteps(model=cldm, device=dev, x_T=x_T, steps=len(used_timesteps),
+                                             used_timesteps=list(used_timesteps), batch_size=pre.size(0), cond=cond,
+                                             uncond=None, cfg_scale=1.0, progress=False,
+                                             **({} if source is None else {"noise_source": source}))
+    res = (cldm.vae_decode(z) + 1) / 2
+    if colour_fix:
+        res = wavelet_reconstruction(res, pre)
+    return res
+
+
 @torch.no_grad()
 def restore_dataset(cldm, diffusion, sampler, pre_restored: Sequence[torch.Tensor], gts: Optional[Sequence[torch.Tensor]] = None,
                     img_size: int = 512, batch_size: int = 8, used_timesteps=(50, 100, 150, 200), start_timestep: int = 200,
@@ -93,55 +122,59 @@ def restore_dataset(cldm, diffusion, sampler, pre_restored: Sequence[torch.Tenso
     its own, replicate-padded at the bottom / right to multiples of ``multiple`` -> (SwinIR) -> the same path -> crop back; its chunking and
     seeded ids are those of "demo".  Entries of ``pre_restored`` / ``gts`` may also be uint8 (h, w, 3) tensors or arrays — what an image
     decoder returns: they are turned into v / 255 and padded on the device by `imageio.ingest` (the same bits as the float (C, h, w) form of
-    the same image), and PSNR against uint8 ground truth is `imageio.psnr`.  ``return_uint8=True`` (keyword only, so that ``seed``
+    the same image), and PSNR against uint8 ground truth is `imageio.psnr`.  ``pad_mode="bucket"`` is "demo"'s padding and crop for every
+    image, run in batches: this rank's shard is grouped by padded extent (`imageio.plan_buckets`, chunks of at most ``batch_size``), the
+    outputs come back in data-set order, ``return_uint8`` goes through `imageio.emit_packed`.  Its noise without ``seed`` is one
+    `torch.randn_like` per chunk, as in "batch": only a SEEDED run is independent of ``batch_size`` (image k carries id k), and only with
+    EDTR_AMD_BATCH_INVARIANT=1 is it "demo" bit for bit.  ``return_uint8=True`` (keyword only, so that ``seed``
     stays the last parameter) returns `imageio.emit`'s uint8 (h, w, 3) bytes — what `save_image` would write — instead of float tensors.  Returns (restored images of this shard, mean PSNR or None)."""
     import torch.distributed as dist
     from . import imageio
-    from .wavelet import wavelet_reconstruction
     dev = next(cldm.unet.parameters()).device
     world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
     rank = dist.get_rank() if world > 1 else 0
     sl = shard_slice(rank, world, len(pre_restored))
     mine = list(pre_restored[sl])
-    outs: List[torch.Tensor] = []
-    if pad_mode not in ("batch", "demo", "seg"):
-        raise ValueError(f"pad_mode must be 'batch', 'demo' or 'seg', got {pad_mode!r}")
-    step = 1 if pad_mode in ("demo", "seg") else batch_size
-    chunk_ids = shard_chunk_ids(len(pre_restored), rank, world, batch_size, pad_mode) if seed is not None else None
-    for i in range(0, len(mine), step):
-        chunk = mine[i:i + step]
-        source = NoiseSource(seed, chunk_ids[i // step]) if seed is not None else None
+    if pad_mode not in ("batch", "demo", "seg", "bucket"):
+        raise ValueError(f"pad_mode must be 'batch', 'demo', 'seg' or 'bucket', got {pad_mode!r}")
+    if pad_mode == "bucket":
+        # chunks of equal padded extent; `where` = the chunk's positions in this shard, the outputs go back to those positions
+        plan = imageio.plan_buckets([_image_hw(img) for img in mine], batch_size, min_size=img_size, multiple=multiple)
+        where = [idx for _, idx in plan]
+        chunk_ids = shard_bucket_ids(len(pre_restored), rank, world, plan) if seed is not None else None
+    else:
+        step = 1 if pad_mode in ("demo", "seg") else batch_size
+        where = [list(range(i, min(i + step, len(mine)))) for i in range(0, len(mine), step)]
+        chunk_ids = shard_chunk_ids(len(pre_restored), rank, world, batch_size, pad_mode) if seed is not None else None
+    outs: List[Optional[torch.Tensor]] = [None] * len(mine)
+    for c, idx in enumerate(where):
+        chunk = [mine[k] for k in idx]
+        source = NoiseSource(seed, chunk_ids[c]) if seed is not None else None
         sizes = None                   # (h, w) per image where imageio.ingest built the batch; None = today's float path
         if pad_mode == "seg":
             pre, sizes = imageio.ingest([_as_hwc(chunk[0])], pad="replicate", multiple=multiple, device=dev)
         elif imageio.is_u8_image(chunk[0]):
-            if pad_mode == "demo":
+            if pad_mode in ("demo", "bucket"):
                 pre, sizes = imageio.ingest(chunk, min_size=img_size, multiple=multiple, device=dev)
             else:
                 pre, sizes = imageio.ingest(chunk, size=(img_size, img_size), device=dev)
         elif pad_mode == "demo":
             pre = pad_to_multiples_of(pad_if_smaller(chunk[0][None].to(dev).float(), img_size), multiple)
+        elif pad_mode == "bucket":
+            pre = torch.cat([pad_to_multiples_of(pad_if_smaller(img[None].to(dev).float(), img_size), multiple) for img in chunk], dim=0)
         else:
             pre = list_to_batch(chunk, img_size, dev).float()
-        if swinir is not None:
-            pre = swinir(pre)
-        cond = cldm.prepare_condition(pre, [""] * pre.size(0))
-        t = torch.full((pre.size(0),), start_timestep, dtype=torch.int64)
-        x_T = diffusion.q_sample(cond["c_img"], t, torch.randn_like(cond["c_img"]) if source is None else source)
-        z = sampler.manual_sample_with_timesteps(model=cldm, device=dev, x_T=x_T, steps=len(used_timesteps),
-                                                 used_timesteps=list(used_timesteps), batch_size=pre.size(0), cond=cond,
-                                                 uncond=None, cfg_scale=1.0, progress=False,
-                                                 **({} if source is None else {"noise_source": source}))
-        res = (cldm.vae_decode(z) + 1) / 2
-        if colour_fix:
-            res = wavelet_reconstruction(res, pre)
+        res = restore_batch(cldm, diffusion, sampler, pre, source, used_timesteps, start_timestep, colour_fix, swinir)
         if return_uint8:           # (emit clamps: `clamp` has nothing left to decide)
-            outs.extend(imageio.emit(res.float().contiguous(), sizes or [(img.size(1), img.size(2)) for img in chunk]))
+            hw = sizes or [(img.size(1), img.size(2)) for img in chunk]
+            got = imageio.emit_packed(res.float().contiguous(), hw)[1] if pad_mode == "bucket" else imageio.emit(res.float().contiguous(), hw)
         elif sizes is None:
-            outs.extend(batch_to_list(res.clamp(0, 1) if clamp else res, chunk))
+            got = batch_to_list(res.clamp(0, 1) if clamp else res, chunk)
         else:
             res = res.clamp(0, 1) if clamp else res
-            outs.extend(res[k][:, :h, :w] for k, (h, w) in enumerate(sizes))
+            got = [res[k][:, :h, :w] for k, (h, w) in enumerate(sizes)]
+        for k, o in zip(idx, got):
+            outs[k] = o
     psnr = None
     if gts is not None:
         mine_gt = list(gts[sl])

@@ -11,6 +11,9 @@ images.  Three rules make the device results a bit-exact function of the bytes, 
   emit     trunc(clamp(x * 255 + 0.5, 0, 255)), the product and the sum each rounded to fp32 (never an FMA); NaN gives 0
            (`emit_reference`)
 
+A whole ragged batch crosses the boundary in a fixed number of launches (`ingest_resized`: at most two, `emit_packed`: one; the same bits
+as `resize_u8` -> `ingest` and `emit` per image), and `plan_buckets` groups images of one padded extent so that such batches exist.
+
 Host side: numpy.  Device side: torch owns the buffers; every computation is a libedtr_hip launch (a missing library is an error)."""
 from __future__ import annotations
 
@@ -103,6 +106,55 @@ def emit_reference(x: np.ndarray) -> np.ndarray:
     t = (x * np.float32(255.0)).astype(np.float32) + np.float32(0.5)
     t = np.where(np.isnan(t), np.float32(0.0), np.clip(t, np.float32(0.0), np.float32(255.0)))
     return t.astype(np.uint8)
+
+
+def _packed_offsets(sizes: Sequence[Tuple[int, int]]) -> Tuple[List[int], int]:
+    """(byte offset of every [h, w, 3] crop in the packed buffer, total bytes): back to back, each start raised to a multiple of 4."""
+    offs, at = [], 0
+    for h, w in sizes:
+        offs.append(at)
+        at = _round_up(at + int(h) * int(w) * 3, 4)
+    return offs, at
+
+
+def ingest_resized_reference(images, out_sizes, size=None, pad: str = "zero", multiple: Optional[int] = None, min_size: Optional[int] = None):
+    """numpy restatement of `ingest_resized`: `resize_u8_reference` -> `INGEST_TABLE` (v / 255) -> CHW -> padding, per image.
+    Returns (float32 [B, 3, H, W], [(h, w), ...])."""
+    if pad not in ("zero", "replicate"):
+        raise ValueError(f"pad must be 'zero' or 'replicate', got {pad!r}")
+    small = [resize_u8_reference(np.asarray(im), int(ow), int(oh)) for im, (ow, oh) in zip(images, out_sizes)]
+    sizes = [(a.shape[0], a.shape[1]) for a in small]
+    H, W = batch_extent(sizes, size, multiple, min_size)
+    batch = np.empty((len(small), 3, H, W), dtype=np.float32)
+    for b, a in enumerate(small):
+        chw = INGEST_TABLE[a].transpose(2, 0, 1)
+        batch[b] = np.pad(chw, ((0, 0), (0, H - a.shape[0]), (0, W - a.shape[1])), mode="edge" if pad == "replicate" else "constant")
+    return batch, sizes
+
+
+def emit_packed_reference(batch: np.ndarray, sizes: Sequence[Tuple[int, int]]):
+    """numpy restatement of `emit_packed`: (packed uint8 buffer, byte offsets); crop i = `emit_reference` of batch[i, :, :h, :w] as HWC at
+    offsets[i].  Bytes between the crops are zero here (the device leaves them as they were)."""
+    offs, total = _packed_offsets(sizes)
+    out = np.zeros(total, dtype=np.uint8)
+    for i, ((h, w), o) in enumerate(zip(sizes, offs)):
+        out[o:o + h * w * 3] = emit_reference(np.asarray(batch[i])[:, :h, :w].transpose(1, 2, 0)).reshape(-1)
+    return out, offs
+
+
+def plan_buckets(sizes: Sequence[Tuple[int, int]], batch_size: int, min_size: Optional[int] = None,
+                 multiple: Optional[int] = None) -> List[Tuple[Tuple[int, int], List[int]]]:
+    """Group images by padded extent: ``sizes`` are the images' (h, w) after any resize; image k belongs to the bucket
+    `batch_extent([sizes[k]], multiple=multiple, min_size=min_size)`.  Buckets are opened in the order their first image appears, the
+    indices of a bucket keep data-set order, and a bucket is cut into chunks of at most ``batch_size``.  Returns the chunks as
+    [((H, W), [indices]), ...]: a partition of range(len(sizes)) that depends on nothing but the arguments.  Pure Python."""
+    batch_size = int(batch_size)
+    if batch_size <= 0:
+        raise ValueError(f"batch_size must be positive, got {batch_size}")
+    buckets: dict = {}                          # (dicts keep insertion order)
+    for k, (h, w) in enumerate(sizes):
+        buckets.setdefault(batch_extent([(int(h), int(w))], multiple=multiple, min_size=min_size), []).append(k)
+    return [(hw, idx[i:i + batch_size]) for hw, idx in buckets.items() for i in range(0, len(idx), batch_size)]
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
@@ -241,6 +293,91 @@ def emit(batch, sizes: Sequence[Tuple[int, int]]) -> List:
         ops.launch(ops.make_image_emit(batch=batch, b=b, dst=dst))
         outs.append(dst)
     return outs
+
+
+def ingest_resized(images, out_sizes, size=None, pad: str = "zero", multiple: Optional[int] = None, min_size: Optional[int] = None, device=None):
+    """`resize_u8` of every uint8 [h, w, 3] image to its (out_w, out_h) of ``out_sizes`` and `ingest` of the results, for the whole
+    list in at most two launches (edtr_image_resize_h_batch, edtr_image_resize_ingest_batch): host images travel in one upload, the
+    horizontal results share one scratch allocation, the resized uint8 images are never written.  Returns (batch, sizes) like
+    `ingest`, bit for bit what `ingest([resize_u8(im, ow, oh) for ...], size, pad, multiple, min_size)` returns."""
+    import torch
+    from . import lib as L
+    from . import ops
+    if pad not in ("zero", "replicate"):
+        raise ValueError(f"pad must be 'zero' or 'replicate', got {pad!r}")
+    images, out_sizes = list(images), [(int(ow), int(oh)) for ow, oh in out_sizes]
+    if not images or len(images) != len(out_sizes):
+        raise ValueError(f"ingest_resized needs as many output sizes as images, got {len(out_sizes)} for {len(images)}")
+    first = images[0]
+    dev = first.device if isinstance(first, torch.Tensor) and first.is_cuda and device is None else _device(device)
+    hosts = []                                  # (index, contiguous uint8 host tensor): packed into one upload
+    srcs: list = [None] * len(images)
+    for i, im in enumerate(images):
+        t = torch.from_numpy(np.ascontiguousarray(im)) if isinstance(im, np.ndarray) else im
+        if t.dtype != torch.uint8 or t.ndim != 3 or t.shape[-1] != 3:
+            raise TypeError("ingest_resized takes uint8 [h, w, 3] images")
+        if t.is_cuda:
+            srcs[i] = t.to(dev).contiguous()
+        else:
+            hosts.append((i, t.contiguous()))
+    if hosts:
+        offs, total = _packed_offsets([(t.shape[0], t.shape[1]) for _, t in hosts])
+        stage = torch.empty((total,), dtype=torch.uint8, pin_memory=True)
+        for (_, t), o in zip(hosts, offs):
+            stage[o:o + t.numel()].copy_(t.reshape(-1))
+        up = stage.to(dev, non_blocking=True)
+        for (i, t), o in zip(hosts, offs):
+            srcs[i] = up[o:o + t.numel()].view(t.shape)
+    for ow, oh in out_sizes:
+        if ow <= 0 or oh <= 0:
+            raise ValueError(f"output size must be positive, got {ow} x {oh}")
+    sizes = [(oh, ow) for ow, oh in out_sizes]
+    H, W = batch_extent(sizes, size, multiple, min_size)
+    descs = (L.ImageDesc * len(srcs))()
+    keep, tmp_bytes = [], 0
+    for b, (s, (ow, oh)) in enumerate(zip(srcs, out_sizes)):
+        h, w = int(s.shape[0]), int(s.shape[1])
+        d = descs[b]
+        d.src, d.in_h, d.in_w, d.out_h, d.out_w, d.b = s.data_ptr(), h, w, oh, ow, b
+        if ow != w:
+            hb, hc = _resize_tables(w, ow, dev)
+            d.h_bounds, d.h_coefs, d.h_ksize, d.tmp_offset = hb.data_ptr(), hc.data_ptr(), hc.shape[1], tmp_bytes
+            tmp_bytes = _round_up(tmp_bytes + h * ow * 3, 4)
+            keep += [hb, hc]
+        if oh != h:
+            vb, vc = _resize_tables(h, oh, dev)
+            d.v_bounds, d.v_coefs, d.v_ksize = vb.data_ptr(), vc.data_ptr(), vc.shape[1]
+            keep += [vb, vc]
+    keep += srcs
+    ddescs = torch.frombuffer(descs, dtype=torch.uint8).to(dev)
+    tmp = torch.empty((tmp_bytes,), dtype=torch.uint8, device=dev) if tmp_bytes else None
+    batch = torch.empty((len(srcs), 3, H, W), dtype=torch.float32, device=dev)
+    if tmp is not None:
+        ops.launch(ops.make_image_resize_h_batch(descs_host=descs, descs=ddescs, tmp=tmp, keep=keep))
+    ops.launch(ops.make_image_resize_ingest_batch(descs_host=descs, descs=ddescs, tmp=tmp, batch=batch, replicate=pad == "replicate",
+                                                  table=_ingest_table(dev), keep=keep))
+    return batch, sizes
+
+
+def emit_packed(batch, sizes: Sequence[Tuple[int, int]]):
+    """`emit` of a whole batch in one launch (edtr_image_emit_batch) into ONE uint8 device buffer: returns (packed, views), views[i] the
+    uint8 [h, w, 3] view of image i's bytes at its 4-byte aligned offset (`_packed_offsets`) — the bytes `emit` gives.  A caller
+    brings the batch to the host with one copy of ``packed``."""
+    import ctypes
+    import torch
+    from . import ops
+    if batch.ndim != 4 or batch.dtype != torch.float32 or not batch.is_contiguous():
+        raise TypeError("emit_packed takes a contiguous fp32 [B, 3, H, W] batch")
+    if len(sizes) != batch.shape[0]:
+        raise ValueError(f"{len(sizes)} sizes for a batch of {batch.shape[0]}")
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    offs, total = _packed_offsets(sizes)
+    rows = [v for b, ((h, w), o) in enumerate(zip(sizes, offs)) for v in (b, h, w, o)]
+    table_host = (ctypes.c_int64 * len(rows))(*rows)
+    table = torch.tensor(rows, dtype=torch.int64).to(batch.device)
+    packed = torch.empty((total,), dtype=torch.uint8, device=batch.device)
+    ops.launch(ops.make_image_emit_batch(batch=batch, table_host=table_host, table=table, dst=packed))
+    return packed, [packed[o:o + h * w * 3].view(h, w, 3) for (h, w), o in zip(sizes, offs)]
 
 
 def sqdiff(a, b, sizes=None, crop_border: int = 0, test_y_channel: bool = False):

@@ -23,6 +23,7 @@ DECLARED_SYMBOLS = [
     "edtr_ffn", "edtr_ffn_plan", "edtr_add_stats", "edtr_lin320", "edtr_lin320_plan",
     "edtr_normal_fill", "edtr_q_sample_rng", "edtr_sampler_update_rng", "edtr_sampler_update_indexed_rng", "edtr_gaussian_sample_rng",
     "edtr_image_resize_u8", "edtr_image_ingest", "edtr_image_emit", "edtr_image_sqdiff",
+    "edtr_image_resize_h_batch", "edtr_image_resize_ingest_batch", "edtr_image_emit_batch",
 ]
 
 
@@ -173,6 +174,19 @@ class GnParams(C.Structure):
     ]
 
 
+class ImageDesc(C.Structure):
+    """edtr_image_desc: one image of a ragged batch (80 bytes; the header documents every offset)."""
+    _fields_ = [
+        ("src", C.c_void_p),
+        ("h_bounds", C.c_void_p), ("h_coefs", C.c_void_p),
+        ("v_bounds", C.c_void_p), ("v_coefs", C.c_void_p),
+        ("tmp_offset", C.c_int64),
+        ("in_h", C.c_int32), ("in_w", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32),
+        ("h_ksize", C.c_int32), ("v_ksize", C.c_int32),
+        ("b", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -256,6 +270,9 @@ def load() -> C.CDLL:
     lib.edtr_image_ingest.argtypes = [i32, vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp]
     lib.edtr_image_emit.argtypes = [vp, i32, i32, i32, i32, i32, vp, i32, i32, vp]
     lib.edtr_image_sqdiff.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp]
+    lib.edtr_image_resize_h_batch.argtypes = [C.POINTER(ImageDesc), vp, i32, i32, vp, i64, vp]
+    lib.edtr_image_resize_ingest_batch.argtypes = [C.POINTER(ImageDesc), vp, i32, i32, vp, i64, vp, i32, i32, i32, i32, vp, vp]
+    lib.edtr_image_emit_batch.argtypes = [vp, i32, i32, i32, i32, C.POINTER(i64), vp, i32, vp, i64, vp]
     if lib.edtr_abi_version() != 10:
         raise RuntimeError("libedtr_hip.so ABI version mismatch")
     _lib = lib

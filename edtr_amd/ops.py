@@ -740,6 +740,34 @@ def make_image_emit(*, batch, b: int, dst, name="image.emit") -> Rec:
     return Rec(L.load().edtr_image_emit, (ptr(batch), b, B, ch, H, W, ptr(dst), h, w), (batch, dst), name, 0.0, 15.0 * h * w)
 
 
+def make_image_resize_h_batch(*, descs_host, descs, tmp, keep=(), name="image.resize_h_batch") -> Rec:
+    """the horizontal pass of every image of a ragged batch in one launch: ``descs_host`` a ctypes array of `lib.ImageDesc`, ``descs`` its
+    copy on the device (a uint8 tensor), ``tmp`` the shared uint8 scratch buffer; ``keep``: the tensors the descriptors point at."""
+    B = len(descs_host)
+    args = (descs_host, ptr(descs), B, 3, ptr(tmp), 0 if tmp is None else tmp.numel())
+    nbytes = sum(3.0 * d.in_h * (d.in_w + d.out_w) for d in descs_host if d.in_w != d.out_w)
+    return Rec(L.load().edtr_image_resize_h_batch, args, (descs_host, descs, tmp) + tuple(keep), name, 0.0, nbytes)
+
+
+def make_image_resize_ingest_batch(*, descs_host, descs, tmp, batch, replicate: bool, table, keep=(), name="image.resize_ingest_batch") -> Rec:
+    """every image's vertical pass -> v / 255 -> its padded slot of fp32 ``batch`` [slots, 3, H, W], in one launch."""
+    B = len(descs_host)
+    slots, _, H, W = batch.shape
+    args = (descs_host, ptr(descs), B, 3, ptr(tmp), 0 if tmp is None else tmp.numel(), ptr(batch), slots, H, W, int(replicate), ptr(table))
+    nbytes = sum(3.0 * d.in_h * d.out_w for d in descs_host) + 12.0 * B * H * W
+    return Rec(L.load().edtr_image_resize_ingest_batch, args, (descs_host, descs, tmp, batch, table) + tuple(keep), name, 0.0, nbytes)
+
+
+def make_image_emit_batch(*, batch, table_host, table, dst, name="image.emit_batch") -> Rec:
+    """crop i = the top-left [h, w] of image b of fp32 ``batch`` -> uint8 HWC at byte ``offset`` of ``dst``, (b, h, w, offset) = row i of the
+    int64 [n, 4] table (``table_host``: a ctypes int64 array, ``table``: its device copy), in one launch."""
+    B, ch, H, W = batch.shape
+    n = len(table_host) // 4
+    args = (ptr(batch), B, ch, H, W, table_host, ptr(table), n, ptr(dst), dst.numel())
+    nbytes = sum(15.0 * table_host[4 * i + 1] * table_host[4 * i + 2] for i in range(n))
+    return Rec(L.load().edtr_image_emit_batch, args, (batch, table_host, table, dst), name, 0.0, nbytes)
+
+
 def make_image_sqdiff(*, a, b, sizes, crop_border: int, y_channel: bool, partials, out, name="image.sqdiff") -> Rec:
     """fp64 ``out`` [B] = per-image sums of squared differences of fp32 [B, 3, H, W] batches (``sizes``: int32 [B, 2] device or None)."""
     B, ch, H, W = a.shape

@@ -2,7 +2,11 @@
 and encodes on the host and does nothing else; the resize to `imageio.demo_size`, the /255, the padding, the crop and save_image's
 quantisation are launches of edtr_amd.imageio on the uploaded bytes.
 
-    python -m edtr_amd.restore --input DIR --output DIR --config YAML-or-"tiny" [--seed N] [--scale S]
+    python -m edtr_amd.restore --input DIR --output DIR --config YAML-or-"tiny" [--seed N] [--scale S] [--batch-size N] [--workers N]
+
+``--batch-size N`` restores images of one padded extent N at a time (`imageio.plan_buckets`; the whole batch crosses the 8-bit boundary in
+three launches and one copy to the host), ``--workers N`` decodes and encodes in N threads while the GPU works.  With ``--seed`` and
+EDTR_AMD_BATCH_INVARIANT=1 the files written are the same bytes whatever the two say.
 
 ``--config tiny`` builds the synthetic tiny model of edtr_amd.synth (no checkpoints: a way to see the tool run); a YAML file in the
 reference's layout (configs/det/demo.yaml) is instantiated through edtr_amd.shim and loaded with the strict loaders of INTEGRATION.md §1
@@ -33,11 +37,122 @@ def list_images(folder: str) -> List[str]:
     return sorted(sum([glob(os.path.join(folder, f"*.{e}")) for e in EXTENSIONS], []))
 
 
+MAX_WORKERS = 16            # decode / encode threads at the most, whatever is asked for (never sized by the machine's CPU count)
+_BATCHED_KEYWORDS = ("img_size", "multiple", "used_timesteps", "start_timestep", "colour_fix")
+
+
+def _out_name(out_dir: str, path: str) -> str:
+    return os.path.join(out_dir, os.path.splitext(os.path.basename(path))[0] + ".png")
+
+
+def _restore_files_batched(cldm, diffusion, sampler, paths, out_dir, swinir, scale, seed, batch_size, workers, img_size=512,
+                           multiple=64, used_timesteps=(50, 100, 150, 200), start_timestep=200, colour_fix=True) -> List[str]:
+    """`restore_files` for batch_size > 1 or workers > 0: the shard's files are grouped by the padded extent of their resized size and
+    every chunk runs `imageio.ingest_resized` -> `evalutil.restore_batch` -> `imageio.emit_packed` -> one copy into a pinned buffer.
+    All GPU work is issued from the calling thread; with ``workers`` the next chunk is decoded and the previous one encoded by a thread
+    pool meanwhile.  A worker's exception is raised here."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    from concurrent.futures import ThreadPoolExecutor
+    from . import evalutil, imageio
+    from .parallel import shard_slice
+    from .rng import NoiseSource, shard_bucket_ids
+    Image = _pillow()
+    dev = next(cldm.unet.parameters()).device
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    rank = dist.get_rank() if world > 1 else 0
+    sl = shard_slice(rank, world, len(paths))
+    mine = paths[sl]
+    os.makedirs(out_dir, exist_ok=True)
+    names = [_out_name(out_dir, p) for p in mine]
+
+    def header(path):                           # (w, h) from the file's header: the plan needs every size before anything is decoded
+        with Image.open(path) as im:
+            return im.size
+
+    def decode(path, size):
+        with Image.open(path) as im:
+            raw = np.array(im.convert("RGB"), dtype=np.uint8)
+        if (raw.shape[1], raw.shape[0]) != tuple(size):
+            raise ValueError(f"{path} decodes to {raw.shape[1]} x {raw.shape[0]}, its header says {size[0]} x {size[1]}")
+        return raw
+
+    def encode(view, name):
+        Image.fromarray(view).save(name)        # (uint8 [h, w, 3]: Pillow infers RGB)
+
+    pool = ThreadPoolExecutor(max_workers=min(int(workers), MAX_WORKERS)) if workers > 0 else None
+
+    class _Done:                                # what `submit` returns without a pool: the work already ran on the calling thread
+        def __init__(self, value):
+            self.value = value
+
+        def result(self):
+            return self.value
+
+    def submit(fn, *args):
+        return pool.submit(fn, *args) if pool is not None else _Done(fn(*args))
+
+    try:
+        in_sizes = [f.result() for f in [submit(header, p) for p in mine]]
+        out_sizes = [imageio.demo_size(w, h, scale) for w, h in in_sizes]
+        plan = imageio.plan_buckets([(oh, ow) for ow, oh in out_sizes], batch_size, min_size=img_size, multiple=multiple)
+        ids = shard_bucket_ids(len(paths), rank, world, plan) if seed is not None else None
+        encodes = []
+
+        def finish(done):                       # a chunk whose copy to the host was queued: wait for it, hand its images to the encoders
+            event, host, views, idx = done
+            event.synchronize()
+            flat = host.numpy()
+            for k, (o, h, w) in zip(idx, views):
+                encodes.append(submit(encode, flat[o:o + h * w * 3].reshape(h, w, 3), names[k]))
+
+        decodes = [submit(decode, mine[k], in_sizes[k]) for k in plan[0][1]] if plan else []
+        pending = None
+        for c, (_, idx) in enumerate(plan):
+            raws = [f.result() for f in decodes]
+            decodes = [submit(decode, mine[k], in_sizes[k]) for k in plan[c + 1][1]] if c + 1 < len(plan) else []
+            if pending is not None:             # (before this chunk's launches, so that its encoding runs beside them)
+                finish(pending)
+            pre, sizes = imageio.ingest_resized(raws, [out_sizes[k] for k in idx], min_size=img_size, multiple=multiple, device=dev)
+            source = NoiseSource(seed, ids[c]) if seed is not None else None
+            res = evalutil.restore_batch(cldm, diffusion, sampler, pre, source, used_timesteps, start_timestep, colour_fix, swinir)
+            packed, views = imageio.emit_packed(res.float().contiguous(), sizes)
+            host = torch.empty((packed.numel(),), dtype=torch.uint8, pin_memory=True)
+            host.copy_(packed, non_blocking=True)
+            event = torch.cuda.Event()
+            event.record()
+            base = packed.data_ptr()
+            pending = (event, host, [(v.data_ptr() - base, v.shape[0], v.shape[1]) for v in views], idx)
+        if pending is not None:
+            finish(pending)
+        for f in encodes:
+            f.result()
+    finally:
+        if pool is not None:
+            pool.shutdown(wait=True, cancel_futures=True)
+    return names
+
+
 def restore_files(cldm, diffusion, sampler, paths: Sequence[str], out_dir: str, swinir=None, scale: float = -1.0,
-                  seed: Optional[int] = None, **kwargs) -> List[str]:
+                  seed: Optional[int] = None, batch_size: int = 1, workers: int = 0, **kwargs) -> List[str]:
     """Decode every file of ``paths`` (Pillow, RGB), upload its bytes, resize them on the device to `imageio.demo_size(w, h, scale)`
     (Image.BICUBIC's bits), run `evalutil.restore_dataset(..., pad_mode="demo", return_uint8=True)` (``kwargs`` are its keywords)
-    and write this rank's restored images to ``out_dir`` as <stem>.png.  Returns the written paths."""
+    and write this rank's restored images to ``out_dir`` as <stem>.png.  Returns the written paths, in the order of ``paths``.
+    ``batch_size`` > 1: images whose resized size pads to the same extent are restored together, ``batch_size`` at a time (the flow of
+    `restore_dataset(pad_mode="bucket")`; ``kwargs`` may then be img_size, multiple, used_timesteps, start_timestep, colour_fix);
+    ``workers`` > 0: that many threads (16 at the most) decode and encode while the calling thread drives the GPU.  Only a run with
+    ``seed`` (and, for equal bits, EDTR_AMD_BATCH_INVARIANT=1) writes the same files whatever ``batch_size`` is."""
+    if int(batch_size) <= 0 or int(workers) < 0:
+        raise ValueError(f"batch_size must be positive and workers non-negative, got {batch_size} and {workers}")
+    if int(batch_size) > 1 or int(workers) > 0:
+        if kwargs.get("pad_mode", "bucket") not in ("demo", "bucket"):
+            raise TypeError("restore_files in batches is the demo flow: pad_mode must be 'demo' or 'bucket'")
+        extra = sorted(set(kwargs) - set(_BATCHED_KEYWORDS) - {"pad_mode"})
+        if extra:
+            raise TypeError(f"restore_files in batches takes {', '.join(_BATCHED_KEYWORDS)}; got {', '.join(extra)}")
+        kw = {k: v for k, v in kwargs.items() if k != "pad_mode"}
+        return _restore_files_batched(cldm, diffusion, sampler, list(paths), out_dir, swinir, scale, seed, int(batch_size), int(workers), **kw)
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -112,6 +227,8 @@ def main(argv=None) -> int:
     ap.add_argument("--config", required=True, help='a YAML file in the layout of configs/det/demo.yaml, or "tiny" (synthetic tiny model)')
     ap.add_argument("--seed", type=int, default=None, help="seeded per-image noise (edtr_amd.rng); default: torch's generator")
     ap.add_argument("--scale", type=float, default=-1.0, help="resize factor; -1 (default) brings the longer side to 512")
+    ap.add_argument("--batch-size", type=int, default=1, help="restore images of one padded extent this many at a time (default 1)")
+    ap.add_argument("--workers", type=int, default=0, help="threads that decode and encode beside the GPU work (default 0, at most 16)")
     ap.add_argument("--sd-weight", default=None, help="Stable Diffusion 2.1 checkpoint (YAML configs)")
     ap.add_argument("--edtr-weight", default=None, help="EDTR checkpoint with swinir / cldm / decoder entries (YAML configs)")
     args = ap.parse_args(argv)
@@ -124,7 +241,8 @@ def main(argv=None) -> int:
         raise SystemExit(f"no image files in {args.input}")
     build = _build_tiny(device) if args.config == "tiny" else _build_from_yaml(args.config, args.sd_weight, args.edtr_weight, device)
     cldm, swinir, diffusion, sampler, kw = build
-    written = restore_files(cldm, diffusion, sampler, paths, args.output, swinir=swinir, scale=args.scale, seed=args.seed, **kw)
+    written = restore_files(cldm, diffusion, sampler, paths, args.output, swinir=swinir, scale=args.scale, seed=args.seed,
+                            batch_size=args.batch_size, workers=args.workers, **kw)
     for name in written:
         print(name)
     return 0

@@ -102,6 +102,22 @@ def shard_chunk_ids(n_images: int, rank: int, world: int, batch_size: int, pad_m
     return [mine[i:i + step] for i in range(0, len(mine), step)]
 
 
+def shard_bucket_ids(n_images: int, rank: int, world: int, plan) -> List[List[int]]:
+    """The global image ids of every chunk of `evalutil.restore_dataset(pad_mode="bucket")` on this rank: ``plan`` is
+    `imageio.plan_buckets` of the sizes of this rank's `shard_slice` (indices inside the shard); image k of the data set keeps id k
+    whatever bucket it lands in."""
+    from .parallel import shard_slice
+    sl = shard_slice(rank, world, n_images)
+    count = sl.stop - sl.start
+    out = []
+    for _, idx in plan:
+        for i in idx:
+            if not 0 <= int(i) < count:
+                raise ValueError(f"index {i} of the plan is outside this rank's shard of {count} images")
+        out.append([sl.start + int(i) for i in idx])
+    return out
+
+
 class NoiseSource:
     """Whose noise: the 64-bit ``seed`` and the GLOBAL ids (data-set indices, not batch positions) of the images of this
     batch, in batch order.  Immutable; owns the device copy of the ids that the kernels read (built on first use, per device)."""

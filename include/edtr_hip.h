@@ -731,6 +731,46 @@ int edtr_image_ingest(int src_f32, const void* src, int h, int w, int channels, 
 /* The top-left h x w crop of image b of batch [B][3][H][W] -> dst [h][w][3] uint8 with the emit rule above.
  * replaces: res[:, :h0, :w0] -> torchvision save_image's mul(255).add_(0.5).clamp_(0, 255).to(uint8), demo.py:165. */
 int edtr_image_emit(const float* batch, int b, int B, int channels, int H, int W, uint8_t* dst, int h, int w, edtr_stream_t stream);
+/* ---- The same boundary for a whole ragged batch in a fixed number of launches --------------------------------------------------
+ * One edtr_image_desc per image, B of them in a DEVICE array that the kernels read, and the same B in a HOST array that the entry
+ * point checks its arguments on (and sizes the grid from) before anything is launched.  Layout (80 bytes, 8-byte aligned):
+ *    0 src        uint8 [in_h][in_w][3] on the device, any byte alignment
+ *    8 h_bounds  16 h_coefs   the horizontal pass's tables as edtr_image_resize_u8 takes them; NULL (both) when out_w == in_w
+ *   24 v_bounds  32 v_coefs   the vertical pass's tables; NULL (both) when out_h == in_h
+ *   40 tmp_offset  int64: where this image's horizontal result [in_h][out_w][3] starts in the shared scratch buffer `tmp`
+ *   48 in_h  52 in_w  56 out_h  60 out_w  64 h_ksize  68 v_ksize  72 b (slot of the batch)  76 reserved (0)       all int32
+ * The bits are those of the per-image entry points: slot b after edtr_image_resize_h_batch + edtr_image_resize_ingest_batch equals
+ * edtr_image_resize_u8 followed by edtr_image_ingest, and edtr_image_emit_batch writes the bytes of edtr_image_emit.  Which passes
+ * run and whether rows move as dwords is decided per image on the device (pitch and pointer alignment of that image); windows are
+ * forced inside the source, and an image whose descriptor does not fit the slot / the scratch buffer is left alone by the kernels.
+ * Errors (nothing is launched): channels != 3 EDTR_E_UNSUPPORTED; a NULL array, src, batch, table, a NULL table of a pass that is
+ * needed or a NULL tmp with a horizontal pass EDTR_E_NULL; B <= 0 or > 65535, a non-positive extent or ksize, b outside [0, slots),
+ * out_h > H, out_w > W, a horizontal result outside [0, tmp_bytes) EDTR_E_SHAPE; misaligned tables / batch EDTR_E_ALIGN. */
+typedef struct edtr_image_desc {
+    const uint8_t* src;
+    const int32_t* h_bounds; const int32_t* h_coefs;
+    const int32_t* v_bounds; const int32_t* v_coefs;
+    int64_t tmp_offset;
+    int32_t in_h; int32_t in_w; int32_t out_h; int32_t out_w;
+    int32_t h_ksize; int32_t v_ksize;
+    int32_t b; int32_t reserved;
+} edtr_image_desc;
+/* One launch: the horizontal pass of every image with out_w != in_w, src -> tmp + tmp_offset.  No launch when no image has one. */
+int edtr_image_resize_h_batch(const edtr_image_desc* descs_host, const edtr_image_desc* descs, int B, int channels, uint8_t* tmp,
+                              int64_t tmp_bytes, edtr_stream_t stream);
+/* One launch: every image's vertical pass (from its horizontal result, or from src where none ran; no pass at all = a plain ingest)
+ * -> the float32(v / 255.0) table -> slot b of batch [slots][3][H][W], the rest of the slot zero (replicate = 0) or the last row /
+ * column repeated (replicate = 1), written by the same launch: no uint8 [out_h][out_w][3] intermediate and no memset.  Three float4
+ * per lane where W % 4 == 0 and batch is 16-byte aligned, element by element otherwise. */
+int edtr_image_resize_ingest_batch(const edtr_image_desc* descs_host, const edtr_image_desc* descs, int B, int channels,
+                                   const uint8_t* tmp, int64_t tmp_bytes, float* batch, int slots, int H, int W, int replicate,
+                                   const float* table, edtr_stream_t stream);
+/* One launch: for i < n, the top-left h x w crop of image b of batch [B][3][H][W] -> dst + offset as uint8 [h][w][3] with the emit
+ * rule; (b, h, w, offset) = table[4 i .. 4 i + 3], int64, on the device (table) and on the host (table_host: checked here).  Offsets
+ * are the caller's, multiples of 4 (EDTR_E_ALIGN), crops inside [0, dst_bytes) and the slot (EDTR_E_SHAPE); bytes of dst that no
+ * crop covers are not written. */
+int edtr_image_emit_batch(const float* batch, int B, int channels, int H, int W, const int64_t* table_host, const int64_t* table,
+                          int n, uint8_t* dst, int64_t dst_bytes, edtr_stream_t stream);
 /* out[i] (fp64) = the sum of squared differences of images i of a and b ([B][3][H][W] fp32) over rows [crop_border, h_i -
  * crop_border) and columns [crop_border, w_i - crop_border), (h_i, w_i) = sizes[2 i], sizes[2 i + 1] (device int32, clamped to
  * H, W; NULL = H, W): over the three planes (y_channel = 0), or over the BT.601 luma (65.481 r + 128.553 g + 24.966 b + 16) / 255
