@@ -707,7 +707,8 @@ def test_sampler_kernels():
     assert rel(p0, rp0) < 1e-6
     assert rel(xp, coefs[2] * rp0 + coefs[3] * x + coefs[4] * noise) < 1e-6
     assert rel(o, 0.86815441 * x + 0.49629423 * noise) < 1e-6
-    # tile accumulate + divide
+    # tile accumulate: one window into zeroed planes (overlap-add onto non-zero values, every plane of count, edtr_divide and the
+    # element bounds of all the kernels above: tests/test_gpu_glue.py)
     out = torch.zeros((1, 4, 16, 24), device=d)
     cnt = torch.zeros_like(out)
     tile = rnd((1, 4, 8, 8), 83)
