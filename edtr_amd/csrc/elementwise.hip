@@ -2,6 +2,8 @@
 #include "common.h"
 #include "noise_elem.h"
 #include <string.h>
+#include <algorithm>
+#include <vector>
 
 namespace {
 
@@ -652,6 +654,159 @@ extern "C" int edtr_tile_accumulate(const float* tile, const float* wts, float* 
     const int64_t n = (int64_t)B * C * th * tw;
     hipLaunchKernelGGL(tile_acc_kernel, dim3(blocks_for(n)), dim3(256), 0, static_cast<hipStream_t>(stream), tile, wts, out,
                        count, B * C, H, W, th, tw, hi, wi);
+    EDTR_LAUNCH_CHECK();
+    return EDTR_OK;
+}
+
+// ---- window table forms of the tiled path: every window cut in one launch, every window blended in one launch -----------------
+namespace {
+// unit = four consecutive elements of one window row (the last unit of a row is shorter when tw % 4 != 0).  `vec_ok`: tw % 4 == 0,
+// W % 4 == 0 and both planes 16-byte aligned, so that a window moves as float4 exactly when its own wi % 4 == 0 (decided here).
+__global__ void __launch_bounds__(256) tile_gather_kernel(const float* __restrict__ src, const int32_t* __restrict__ table,
+                                                         float* __restrict__ dst, int BC, int H, int W, int th, int tw, int n,
+                                                         int vec_ok) {
+    const int q = (tw + 3) >> 2;
+    const int64_t units = (int64_t)n * BC * th * q;
+    for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < units; u += (int64_t)gridDim.x * 256) {
+        const int x = (int)(u % q) << 2;
+        int64_t r = u / q;
+        const int y = (int)(r % th);
+        r /= th;
+        const int64_t bc = r % BC, k = r / BC;
+        const int hi = table[2 * k], wi = table[2 * k + 1];
+        const float* s = src + (bc * H + hi + y) * W + wi + x;
+        float* d = dst + ((k * BC + bc) * th + y) * tw + x;
+        if (vec_ok && (wi & 3) == 0) {
+            *reinterpret_cast<f32x4*>(d) = *reinterpret_cast<const f32x4*>(s);
+        } else {
+            const int m = tw - x < 4 ? tw - x : 4;
+            for (int j = 0; j < m; ++j) d[j] = s[j];
+        }
+    }
+}
+
+// gather form of the overlap-add: one lane owns V adjacent pixels of one row, walks the windows in table order and writes the
+// quotient once.  The numerator is __builtin_fmaf(tile, w, acc) from acc = 0 and the denominator cnt + w from cnt = 0: the very
+// operations tile_acc_kernel performs per window on zeroed planes (its `out[o] += tile[i] * w` is contracted to one fma), and the
+// division is divide_kernel's, so the bits are those of that sequence.  V = 4 needs every wi, tw and W to be multiples of 4: the
+// four pixels of a lane are then inside or outside a window together.
+template <int V>
+__global__ void __launch_bounds__(256) tile_blend_kernel(const float* __restrict__ tiles, const float* __restrict__ wts,
+                                                        const int32_t* __restrict__ table, float* __restrict__ out, int BC, int H,
+                                                        int W, int th, int tw, int n) {
+    const int q = W / V;
+    const int64_t units = (int64_t)BC * H * q;
+    for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < units; u += (int64_t)gridDim.x * 256) {
+        const int x = (int)(u % q) * V;
+        const int64_t r = u / q;
+        const int y = (int)(r % H);
+        const int64_t bc = r / H;
+        float acc[V], cnt[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) acc[j] = 0.0f, cnt[j] = 0.0f;
+        for (int k = 0; k < n; ++k) {
+            const int ty = y - table[2 * k], tx = x - table[2 * k + 1];
+            if ((unsigned)ty >= (unsigned)th || (unsigned)tx >= (unsigned)tw) continue;
+            const float* t = tiles + (((int64_t)k * BC + bc) * th + ty) * tw + tx;
+            const float* w = wts + ty * tw + tx;
+            if (V == 4) {
+                const f32x4 tv = *reinterpret_cast<const f32x4*>(t), wv = *reinterpret_cast<const f32x4*>(w);
+#pragma unroll
+                for (int j = 0; j < V; ++j) acc[j] = __builtin_fmaf(tv[j], wv[j], acc[j]), cnt[j] += wv[j];
+            } else {
+                acc[0] = __builtin_fmaf(t[0], w[0], acc[0]);
+                cnt[0] += w[0];
+            }
+        }
+        float* o = out + (bc * H + y) * W + x;
+        if (V == 4) {
+            f32x4 v;
+#pragma unroll
+            for (int j = 0; j < V; ++j) v[j] = acc[j] / cnt[j];
+            *reinterpret_cast<f32x4*>(o) = v;
+        } else {
+            o[0] = acc[0] / cnt[0];
+        }
+    }
+}
+
+inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+// the table's host copy: n windows of th x tw inside the H x W plane.  *all_wi4: every wi is a multiple of 4.
+int check_windows(const int32_t* t, int n, int th, int tw, int H, int W, bool* all_wi4) {
+    bool a = true;
+    for (int k = 0; k < n; ++k) {
+        const int hi = t[2 * k], wi = t[2 * k + 1];
+        if (hi < 0 || wi < 0 || hi > H - th || wi > W - tw) return EDTR_E_SHAPE;
+        a = a && (wi & 3) == 0;
+    }
+    *all_wi4 = a;
+    return EDTR_OK;
+}
+
+// every pixel of the plane lies in a window: per band of rows between two window edges, the columns [wi, wi + tw) of the windows
+// over that band, sorted, must leave no gap in [0, W)
+bool windows_cover(const int32_t* t, int n, int th, int tw, int H, int W) {
+    std::vector<int> edges;
+    edges.reserve(2 * (size_t)n + 2);
+    edges.push_back(0);
+    for (int k = 0; k < n; ++k) edges.push_back(t[2 * k]), edges.push_back(t[2 * k] + th);
+    std::sort(edges.begin(), edges.end());
+    edges.erase(std::unique(edges.begin(), edges.end()), edges.end());
+    if (edges.back() < H) return false;
+    std::vector<int> cols;
+    for (size_t e = 0; e + 1 < edges.size(); ++e) {
+        const int y = edges[e];                      // no window starts or ends inside [y, edges[e + 1]): one row stands for the band
+        cols.clear();
+        for (int k = 0; k < n; ++k)
+            if (t[2 * k] <= y && y < t[2 * k] + th) cols.push_back(t[2 * k + 1]);
+        std::sort(cols.begin(), cols.end());
+        int reach = 0;
+        for (int wi : cols) {
+            if (wi > reach) return false;
+            reach = wi + tw > reach ? wi + tw : reach;
+        }
+        if (reach < W) return false;
+    }
+    return true;
+}
+}  // namespace
+
+extern "C" int edtr_tile_gather(const float* src, int B, int C, int H, int W, const int32_t* table_host, const int32_t* table, int n,
+                                int th, int tw, float* dst, edtr_stream_t stream) {
+    if (!src || !table_host || !table || !dst) return EDTR_E_NULL;
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || n <= 0 || n > EDTR_TILE_WINDOWS_MAX || th <= 0 || tw <= 0 || th > H || tw > W)
+        return EDTR_E_SHAPE;
+    if (!aligned4(src) || !aligned4(dst) || !aligned4(table)) return EDTR_E_ALIGN;
+    bool all_wi4 = false;
+    const int rc = check_windows(table_host, n, th, tw, H, W, &all_wi4);
+    if (rc != EDTR_OK) return rc;
+    const int vec_ok = tw % 4 == 0 && W % 4 == 0 && aligned16(src) && aligned16(dst);
+    const int64_t units = (int64_t)n * B * C * th * ((tw + 3) / 4);
+    hipLaunchKernelGGL(tile_gather_kernel, dim3(blocks_for(units)), dim3(256), 0, static_cast<hipStream_t>(stream), src, table, dst,
+                       B * C, H, W, th, tw, n, vec_ok);
+    EDTR_LAUNCH_CHECK();
+    return EDTR_OK;
+}
+
+extern "C" int edtr_tile_blend(const float* tiles, const float* wts, const int32_t* table_host, const int32_t* table, int n, int th,
+                               int tw, float* out, int B, int C, int H, int W, edtr_stream_t stream) {
+    if (!tiles || !wts || !table_host || !table || !out) return EDTR_E_NULL;
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || n <= 0 || n > EDTR_TILE_WINDOWS_MAX || th <= 0 || tw <= 0 || th > H || tw > W)
+        return EDTR_E_SHAPE;
+    if (!aligned4(tiles) || !aligned4(wts) || !aligned4(out) || !aligned4(table)) return EDTR_E_ALIGN;
+    bool all_wi4 = false;
+    const int rc = check_windows(table_host, n, th, tw, H, W, &all_wi4);
+    if (rc != EDTR_OK) return rc;
+    if (!windows_cover(table_host, n, th, tw, H, W)) return EDTR_E_SHAPE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int BC = B * C;
+    if (all_wi4 && tw % 4 == 0 && W % 4 == 0 && aligned16(tiles) && aligned16(wts) && aligned16(out))
+        hipLaunchKernelGGL(tile_blend_kernel<4>, dim3(blocks_for((int64_t)BC * H * (W / 4))), dim3(256), 0, st, tiles, wts, table, out, BC,
+                           H, W, th, tw, n);
+    else
+        hipLaunchKernelGGL(tile_blend_kernel<1>, dim3(blocks_for((int64_t)BC * H * W)), dim3(256), 0, st, tiles, wts, table, out, BC, H, W,
+                           th, tw, n);
     EDTR_LAUNCH_CHECK();
     return EDTR_OK;
 }

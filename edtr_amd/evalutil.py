@@ -5,6 +5,7 @@ edtr_amd path on each shard and reports PSNR.  The helpers up to `calculate_psnr
 (today's path of `restore_dataset`, kept bit for bit); 8-bit images and the "seg" padding go through the launches of edtr_amd.imageio."""
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -79,24 +80,80 @@ def _image_hw(img) -> Tuple[int, int]:
     return (int(img.shape[0]), int(img.shape[1])) if imageio.is_u8_image(img) else (int(img.shape[1]), int(img.shape[2]))
 
 
+@dataclass(frozen=True)
+class TilingOptions:
+    """The four tiling switches of demo.py:183-192 and their six sizes, in the demo's units and with its defaults: ``pre_res_*`` and
+    ``vae_encoder_size`` in image pixels, ``cldm_*`` in image pixels (the sampler gets them // 8, demo.py:114,120), ``vae_decoder_size``
+    handed to `vae_decode` as it is (demo.py:123: latent pixels).  A stage whose switch is off runs untiled whatever its sizes say."""
+    pre_res: bool = False
+    pre_res_size: int = 512
+    pre_res_stride: int = 256
+    vae_encoder: bool = False
+    vae_encoder_size: int = 256
+    vae_decoder: bool = False
+    vae_decoder_size: int = 256
+    cldm: bool = False
+    cldm_size: int = 512
+    cldm_stride: int = 256
+
+    def pre_res_tiled(self, H: int, W: int) -> bool:
+        """SwinIR runs per window when the switch is on and a window fits on both axes (the demo's "tiny and unnecessary to tile")."""
+        return bool(self.pre_res) and min(H, W) >= self.pre_res_size
+
+    def cldm_tiled(self, h: int, w: int) -> bool:
+        """demo.py:113-116 on the latent's (h, w): untiled unless the latent is larger than the tile on both axes."""
+        return bool(self.cldm) and not (h <= self.cldm_size // 8 or w <= self.cldm_size // 8)
+
+    def sampler_kwargs(self, h: int, w: int) -> dict:
+        """What `SpacedSampler.manual_sample_with_timesteps` gets for a latent of (h, w) (demo.py:120)."""
+        return dict(tiled=self.cldm_tiled(h, w), tile_size=self.cldm_size // 8, tile_stride=self.cldm_stride // 8)
+
+    def encoder_kwargs(self) -> dict:
+        return dict(tiled=bool(self.vae_encoder), tile_size=self.vae_encoder_size)
+
+    def decoder_kwargs(self) -> dict:
+        return dict(tiled=bool(self.vae_decoder), tile_size=self.vae_decoder_size)
+
+
+def _tiled_swinir(swinir, tiling: TilingOptions):
+    """SwinIR per sliding window with the windows stacked on the batch axis (demo.py:98 with the options' sizes)."""
+    from .tiling import make_tiled_fn
+    return make_tiled_fn(swinir, tiling.pre_res_size, tiling.pre_res_stride, batched_fn=lambda tiles, windows: swinir(tiles))
+
+
 @torch.no_grad()
 def restore_batch(cldm, diffusion, sampler, pre: torch.Tensor, source: Optional[NoiseSource] = None,
-                  used_timesteps=(50, 100, 150, 200), start_timestep: int = 200, colour_fix: bool = True, swinir=None) -> torch.Tensor:
+                  used_timesteps=(50, 100, 150, 200), start_timestep: int = 200, colour_fix: bool = True, swinir=None,
+                  tiling: Optional[TilingOptions] = None) -> torch.Tensor:
     """One padded fp32 (B, 3, H, W) batch through (SwinIR ->) prepare_condition -> q_sample(start_timestep) -> spaced sampler ->
     vae_decode (-> wavelet colour fix): what `restore_dataset` runs on every chunk, whatever built the batch.  ``source``: the seeded
-    noise of the batch's images, or None for torch's generator."""
+    noise of the batch's images, or None for torch's generator.  ``tiling`` (a `TilingOptions`): the stages whose switch is on run
+    tiled as in demo.py:94-123 — SwinIR per window, `vae_encode(tiled=)`, the latent-tiled sampler, `vae_decode(tiled=)`; a stage too
+    small for its tile runs untiled.  The sampler's patch of ``cldm.forward`` is taken back before this returns."""
     from .wavelet import wavelet_reconstruction
     dev = pre.device
     if swinir is not None:
-        pre = swinir(pre)
-    cond = cldm.prepare_condition(pre, [""] * pre.size(0))
+        pre = (_tiled_swinir(swinir, tiling) if tiling is not None and tiling.pre_res_tiled(pre.size(2), pre.size(3)) else swinir)(pre)
+    if tiling is not None and tiling.vae_encoder:   # prepare_condition does not expose the encoder's tiling: its two calls, as demo.py:102-104
+        cldm.clip.compute_dtype = cldm.compute_dtype
+        cond = dict(c_txt=cldm.clip.encode([""] * pre.size(0)), c_img=cldm.vae_encode(pre * 2 - 1, sample=False, **tiling.encoder_kwargs()))
+    else:
+        cond = cldm.prepare_condition(pre, [""] * pre.size(0))
     t = torch.full((pre.size(0),), start_timestep, dtype=torch.int64)
     x_T = diffusion.q_sample(cond["c_img"], t, torch.randn_like(cond["c_img"]) if source is None else source)
-    z = sampler.manual_sample_with_timesteps(model=cldm, device=dev, x_T=x_T, steps=len(used_timesteps),
-                                             used_timesteps=list(used_timesteps), batch_size=pre.size(0), cond=cond,
-                                             uncond=None, cfg_scale=1.0, progress=False,
-                                             **({} if source is None else {"noise_source": source}))
-    res = (cldm.vae_decode(z) + 1) / 2
+    tiled = {} if tiling is None else tiling.sampler_kwargs(x_T.size(2), x_T.size(3))
+    had, saved = "forward" in vars(cldm), vars(cldm).get("forward")
+    try:
+        z = sampler.manual_sample_with_timesteps(model=cldm, device=dev, x_T=x_T, steps=len(used_timesteps),
+                                                 used_timesteps=list(used_timesteps), batch_size=pre.size(0), cond=cond,
+                                                 uncond=None, cfg_scale=1.0, progress=False, **tiled,
+                                                 **({} if source is None else {"noise_source": source}))
+    finally:                                # the sampler never restores the forward it patches (reference utils/sampler.py:288-303)
+        if had:
+            cldm.forward = saved
+        elif "forward" in vars(cldm):
+            del cldm.forward
+    res = (cldm.vae_decode(z, **({} if tiling is None else tiling.decoder_kwargs())) + 1) / 2
     if colour_fix:
         res = wavelet_reconstruction(res, pre)
     return res
@@ -106,7 +163,7 @@ def restore_batch(cldm, diffusion, sampler, pre: torch.Tensor, source: Optional[
 def restore_dataset(cldm, diffusion, sampler, pre_restored: Sequence[torch.Tensor], gts: Optional[Sequence[torch.Tensor]] = None,
                     img_size: int = 512, batch_size: int = 8, used_timesteps=(50, 100, 150, 200), start_timestep: int = 200,
                     colour_fix: bool = True, swinir=None, pad_mode: str = "batch", multiple: int = 64,
-                    clamp: bool = True, *, return_uint8: bool = False,
+                    clamp: bool = True, *, return_uint8: bool = False, tiling: Optional[TilingOptions] = None,
                     seed: Optional[int] = None) -> Tuple[List[torch.Tensor], Optional[torch.Tensor]]:
     """The restoration loop of main/det/test_edtr.py:121-135 without accelerate: this rank's shard of the
     (C, h, w <= img_size) pre-restored images is padded, pushed through vae_encode -> q_sample(t) -> spaced sampler ->
@@ -127,7 +184,9 @@ def restore_dataset(cldm, diffusion, sampler, pre_restored: Sequence[torch.Tenso
     outputs come back in data-set order, ``return_uint8`` goes through `imageio.emit_packed`.  Its noise without ``seed`` is one
     `torch.randn_like` per chunk, as in "batch": only a SEEDED run is independent of ``batch_size`` (image k carries id k), and only with
     EDTR_AMD_BATCH_INVARIANT=1 is it "demo" bit for bit.  ``return_uint8=True`` (keyword only, so that ``seed``
-    stays the last parameter) returns `imageio.emit`'s uint8 (h, w, 3) bytes — what `save_image` would write — instead of float tensors.  Returns (restored images of this shard, mean PSNR or None)."""
+    stays the last parameter) returns `imageio.emit`'s uint8 (h, w, 3) bytes — what `save_image` would write — instead of float tensors.
+    ``tiling`` (keyword only, a `TilingOptions`): handed to `restore_batch` for every chunk in all four pad modes; the noise is drawn on
+    the whole latent, so a seeded tiled run keeps the guarantee above (EDTR_AMD_BATCH_INVARIANT=1: equal bits whatever ``batch_size``).  Returns (restored images of this shard, mean PSNR or None)."""
     import torch.distributed as dist
     from . import imageio
     dev = next(cldm.unet.parameters()).device
@@ -164,7 +223,7 @@ def restore_dataset(cldm, diffusion, sampler, pre_restored: Sequence[torch.Tenso
             pre = torch.cat([pad_to_multiples_of(pad_if_smaller(img[None].to(dev).float(), img_size), multiple) for img in chunk], dim=0)
         else:
             pre = list_to_batch(chunk, img_size, dev).float()
-        res = restore_batch(cldm, diffusion, sampler, pre, source, used_timesteps, start_timestep, colour_fix, swinir)
+        res = restore_batch(cldm, diffusion, sampler, pre, source, used_timesteps, start_timestep, colour_fix, swinir, tiling)
         if return_uint8:           # (emit clamps: `clamp` has nothing left to decide)
             hw = sizes or [(img.size(1), img.size(2)) for img in chunk]
             got = imageio.emit_packed(res.float().contiguous(), hw)[1] if pad_mode == "bucket" else imageio.emit(res.float().contiguous(), hw)

@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("EDTR_AMD_LIB") or os.path.join(HERE, "libedtr_hip.so"
 BF16, F16, F32_SPLIT, F32_H1, F32_H2, F32_H3 = 0, 1, 2, 3, 4, 5
 ACT_NONE, ACT_GEGLU, ACT_SILU, ACT_GELU, ACT_LRELU = 0, 1, 2, 3, 4
 SQDIFF_BLOCKS = 64          # EDTR_SQDIFF_BLOCKS: fp64 partial sums per image of edtr_image_sqdiff
+TILE_WINDOWS_MAX = 4096     # EDTR_TILE_WINDOWS_MAX: windows per table of edtr_tile_gather / edtr_tile_blend
 
 DECLARED_SYMBOLS = [
     "edtr_abi_version", "edtr_error_string", "edtr_device_info", "edtr_igemm", "edtr_flash_attn64",
@@ -24,6 +25,7 @@ DECLARED_SYMBOLS = [
     "edtr_normal_fill", "edtr_q_sample_rng", "edtr_sampler_update_rng", "edtr_sampler_update_indexed_rng", "edtr_gaussian_sample_rng",
     "edtr_image_resize_u8", "edtr_image_ingest", "edtr_image_emit", "edtr_image_sqdiff",
     "edtr_image_resize_h_batch", "edtr_image_resize_ingest_batch", "edtr_image_emit_batch",
+    "edtr_tile_gather", "edtr_tile_blend",
 ]
 
 
@@ -273,6 +275,9 @@ def load() -> C.CDLL:
     lib.edtr_image_resize_h_batch.argtypes = [C.POINTER(ImageDesc), vp, i32, i32, vp, i64, vp]
     lib.edtr_image_resize_ingest_batch.argtypes = [C.POINTER(ImageDesc), vp, i32, i32, vp, i64, vp, i32, i32, i32, i32, vp, vp]
     lib.edtr_image_emit_batch.argtypes = [vp, i32, i32, i32, i32, C.POINTER(i64), vp, i32, vp, i64, vp]
+    # the window-table forms of the tiled path (edtr_hip.h "The same overlap-add for ALL windows"): table_host is a ctypes int32 array
+    lib.edtr_tile_gather.argtypes = [vp, i32, i32, i32, i32, C.POINTER(i32), vp, i32, i32, i32, vp, vp]
+    lib.edtr_tile_blend.argtypes = [vp, vp, C.POINTER(i32), vp, i32, i32, i32, vp, i32, i32, i32, i32, vp]
     if lib.edtr_abi_version() != 10:
         raise RuntimeError("libedtr_hip.so ABI version mismatch")
     _lib = lib

@@ -789,6 +789,24 @@ def make_divide(*, num, den, out, n, name="divide") -> Rec:
     return Rec(L.load().edtr_divide, (ptr(num), ptr(den), ptr(out), n), (num, den, out), name)
 
 
+def make_tile_gather(*, src, table_host, table, th, tw, dst, name="tile_gather") -> Rec:
+    """every th x tw window of fp32 ``src`` [B, C, H, W] -> ``dst`` [n B, C, th, tw], window-major, in one launch; ``table_host``: a ctypes
+    int32 array of n (hi, wi) pairs, ``table``: its device copy (an int32 tensor)."""
+    B, C, H, W = src.shape
+    n = len(table_host) // 2
+    args = (ptr(src), B, C, H, W, table_host, ptr(table), n, th, tw, ptr(dst))
+    return Rec(L.load().edtr_tile_gather, args, (src, table_host, table, dst), name, 0.0, 8.0 * n * B * C * th * tw)
+
+
+def make_tile_blend(*, tiles, wts, table_host, table, th, tw, out, name="tile_blend") -> Rec:
+    """``out`` [B, C, H, W] = the ``wts``-weighted mean of the window-major ``tiles`` [n B, C, th, tw] over the windows covering each pixel,
+    in one launch (the bits of zeroed planes -> make_tile_accumulate per window in table order -> make_divide)."""
+    B, C, H, W = out.shape
+    n = len(table_host) // 2
+    args = (ptr(tiles), ptr(wts), table_host, ptr(table), n, th, tw, ptr(out), B, C, H, W)
+    return Rec(L.load().edtr_tile_blend, args, (tiles, wts, table_host, table, out), name, 0.0, 4.0 * B * C * (n * th * tw + H * W))
+
+
 def make_gn_pool(*, sums, weights, counts, T, BG, name="gn_pool") -> Rec:
     return Rec(L.load().edtr_gn_pool, (ptr(sums), ptr(weights), ptr(counts), T, BG), (sums, weights, counts), name)
 

@@ -3,10 +3,14 @@ and encodes on the host and does nothing else; the resize to `imageio.demo_size`
 quantisation are launches of edtr_amd.imageio on the uploaded bytes.
 
     python -m edtr_amd.restore --input DIR --output DIR --config YAML-or-"tiny" [--seed N] [--scale S] [--batch-size N] [--workers N]
+                               [--pre-res-tiled] [--vae-encoder-tiled] [--vae-decoder-tiled] [--cldm-tiled] [--*-tile-size N] [--*-tile-stride N]
 
 ``--batch-size N`` restores images of one padded extent N at a time (`imageio.plan_buckets`; the whole batch crosses the 8-bit boundary in
 three launches and one copy to the host), ``--workers N`` decodes and encodes in N threads while the GPU works.  With ``--seed`` and
 EDTR_AMD_BATCH_INVARIANT=1 the files written are the same bytes whatever the two say.
+
+The four ``--*-tiled`` switches and their sizes are demo.py's (:183-192, same spellings, units and defaults): they become one
+`evalutil.TilingOptions` that every image of the folder is restored with; a stage too small for its tile runs untiled.
 
 ``--config tiny`` builds the synthetic tiny model of edtr_amd.synth (no checkpoints: a way to see the tool run); a YAML file in the
 reference's layout (configs/det/demo.yaml) is instantiated through edtr_amd.shim and loaded with the strict loaders of INTEGRATION.md §1
@@ -38,7 +42,7 @@ def list_images(folder: str) -> List[str]:
 
 
 MAX_WORKERS = 16            # decode / encode threads at the most, whatever is asked for (never sized by the machine's CPU count)
-_BATCHED_KEYWORDS = ("img_size", "multiple", "used_timesteps", "start_timestep", "colour_fix")
+_BATCHED_KEYWORDS = ("img_size", "multiple", "used_timesteps", "start_timestep", "colour_fix", "tiling")
 
 
 def _out_name(out_dir: str, path: str) -> str:
@@ -46,7 +50,7 @@ def _out_name(out_dir: str, path: str) -> str:
 
 
 def _restore_files_batched(cldm, diffusion, sampler, paths, out_dir, swinir, scale, seed, batch_size, workers, img_size=512,
-                           multiple=64, used_timesteps=(50, 100, 150, 200), start_timestep=200, colour_fix=True) -> List[str]:
+                           multiple=64, used_timesteps=(50, 100, 150, 200), start_timestep=200, colour_fix=True, tiling=None) -> List[str]:
     """`restore_files` for batch_size > 1 or workers > 0: the shard's files are grouped by the padded extent of their resized size and
     every chunk runs `imageio.ingest_resized` -> `evalutil.restore_batch` -> `imageio.emit_packed` -> one copy into a pinned buffer.
     All GPU work is issued from the calling thread; with ``workers`` the next chunk is decoded and the previous one encoded by a thread
@@ -116,7 +120,7 @@ def _restore_files_batched(cldm, diffusion, sampler, paths, out_dir, swinir, sca
                 finish(pending)
             pre, sizes = imageio.ingest_resized(raws, [out_sizes[k] for k in idx], min_size=img_size, multiple=multiple, device=dev)
             source = NoiseSource(seed, ids[c]) if seed is not None else None
-            res = evalutil.restore_batch(cldm, diffusion, sampler, pre, source, used_timesteps, start_timestep, colour_fix, swinir)
+            res = evalutil.restore_batch(cldm, diffusion, sampler, pre, source, used_timesteps, start_timestep, colour_fix, swinir, tiling)
             packed, views = imageio.emit_packed(res.float().contiguous(), sizes)
             host = torch.empty((packed.numel(),), dtype=torch.uint8, pin_memory=True)
             host.copy_(packed, non_blocking=True)
@@ -140,7 +144,7 @@ def restore_files(cldm, diffusion, sampler, paths: Sequence[str], out_dir: str, 
     (Image.BICUBIC's bits), run `evalutil.restore_dataset(..., pad_mode="demo", return_uint8=True)` (``kwargs`` are its keywords)
     and write this rank's restored images to ``out_dir`` as <stem>.png.  Returns the written paths, in the order of ``paths``.
     ``batch_size`` > 1: images whose resized size pads to the same extent are restored together, ``batch_size`` at a time (the flow of
-    `restore_dataset(pad_mode="bucket")`; ``kwargs`` may then be img_size, multiple, used_timesteps, start_timestep, colour_fix);
+    `restore_dataset(pad_mode="bucket")`; ``kwargs`` may then be img_size, multiple, used_timesteps, start_timestep, colour_fix, tiling);
     ``workers`` > 0: that many threads (16 at the most) decode and encode while the calling thread drives the GPU.  Only a run with
     ``seed`` (and, for equal bits, EDTR_AMD_BATCH_INVARIANT=1) writes the same files whatever ``batch_size`` is."""
     if int(batch_size) <= 0 or int(workers) < 0:
@@ -220,7 +224,17 @@ def _build_from_yaml(path: str, sd_weight: str, edtr_weight: str, device):
             dict(used_timesteps=used, start_timestep=ts))
 
 
-def main(argv=None) -> int:
+def tiling_from_args(args):
+    """The `evalutil.TilingOptions` of the parsed ``--*-tiled`` flags; None when no switch is on (the untiled flow)."""
+    from .evalutil import TilingOptions
+    opt = TilingOptions(pre_res=args.pre_res_tiled, pre_res_size=args.pre_res_tile_size, pre_res_stride=args.pre_res_tile_stride,
+                        vae_encoder=args.vae_encoder_tiled, vae_encoder_size=args.vae_encoder_tile_size,
+                        vae_decoder=args.vae_decoder_tiled, vae_decoder_size=args.vae_decoder_tile_size,
+                        cldm=args.cldm_tiled, cldm_size=args.cldm_tile_size, cldm_stride=args.cldm_tile_stride)
+    return opt if (opt.pre_res or opt.vae_encoder or opt.vae_decoder or opt.cldm) else None
+
+
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m edtr_amd.restore", description="Restore every image of a folder on the GPU.")
     ap.add_argument("--input", required=True, help="folder of png / jpg / jpeg files")
     ap.add_argument("--output", required=True, help="folder the restored <stem>.png files are written to")
@@ -231,7 +245,22 @@ def main(argv=None) -> int:
     ap.add_argument("--workers", type=int, default=0, help="threads that decode and encode beside the GPU work (default 0, at most 16)")
     ap.add_argument("--sd-weight", default=None, help="Stable Diffusion 2.1 checkpoint (YAML configs)")
     ap.add_argument("--edtr-weight", default=None, help="EDTR checkpoint with swinir / cldm / decoder entries (YAML configs)")
-    args = ap.parse_args(argv)
+    # the tiling switches of demo.py:183-192
+    ap.add_argument("--pre-res-tiled", action="store_true", help="SwinIR per sliding window")
+    ap.add_argument("--pre-res-tile-size", type=int, default=512)
+    ap.add_argument("--pre-res-tile-stride", type=int, default=256)
+    ap.add_argument("--vae-encoder-tiled", action="store_true")
+    ap.add_argument("--vae-encoder-tile-size", type=int, default=256)
+    ap.add_argument("--vae-decoder-tiled", action="store_true")
+    ap.add_argument("--vae-decoder-tile-size", type=int, default=256)
+    ap.add_argument("--cldm-tiled", action="store_true", help="latent-tiled denoiser")
+    ap.add_argument("--cldm-tile-size", type=int, default=512, help="image pixels (the sampler gets it // 8)")
+    ap.add_argument("--cldm-tile-stride", type=int, default=256)
+    return ap
+
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("edtr_amd.restore needs a GPU: the restoration path has no CPU fallback")
@@ -241,6 +270,9 @@ def main(argv=None) -> int:
         raise SystemExit(f"no image files in {args.input}")
     build = _build_tiny(device) if args.config == "tiny" else _build_from_yaml(args.config, args.sd_weight, args.edtr_weight, device)
     cldm, swinir, diffusion, sampler, kw = build
+    tiling = tiling_from_args(args)
+    if tiling is not None:
+        kw = dict(kw, tiling=tiling)
     written = restore_files(cldm, diffusion, sampler, paths, args.output, swinir=swinir, scale=args.scale, seed=args.seed,
                             batch_size=args.batch_size, workers=args.workers, **kw)
     for name in written:

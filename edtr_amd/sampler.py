@@ -10,7 +10,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .tiling import make_tiled_fn
+from .tiling import device_windows, gather_windows, make_tiled_fn
 
 
 def space_timesteps(num_timesteps: int, section_counts) -> set:
@@ -172,11 +172,19 @@ class SpacedSampler(nn.Module):
         forward = model.forward
         ctx_rep = {}      # (n) -> (source c_txt, its version, repeated copy): the SAME tensor object goes to every step, so the
         #                   engine's context cache (keyed on tensor identity) hits instead of re-projecting K / V^T per step
+        img_win = []      # [(source c_img, its version, every window of it, window-major)]: the condition does not change between the
+        #                   steps, so its windows are cut once (edtr_tile_gather) and every step's groups take their slices
 
         def batched(x_tiles, windows, t, cond):
             # the windows of one latent stacked on the batch axis (window-major, like torch.cat of the per-window batches)
             n = len(windows)
-            c_img = torch.cat([cond["c_img"][..., hi:he, wi:we] for hi, he, wi, we in windows], dim=0)
+            src = cond["c_img"]
+            b = src.shape[0]
+            tab = device_windows(src.shape[2], src.shape[3], tile_size, tile_stride, src.device)
+            if not img_win or img_win[0][0] is not src or img_win[0][1] != src._version:
+                img_win[:] = [(src, src._version, gather_windows(src, tab, tile_size))]
+            g0 = tab.index[tuple(windows[0])]
+            c_img = img_win[0][2][g0 * b:(g0 + n) * b]
             c_txt = cond["c_txt"]
             hit = ctx_rep.get(n)
             if hit is None or hit[0] is not c_txt or hit[1] != c_txt._version:

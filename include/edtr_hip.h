@@ -687,6 +687,26 @@ int edtr_tile_accumulate(const float* tile, const float* wts, float* out, float*
                          int C, int H, int W, int th, int tw, int hi, int wi, edtr_stream_t stream);
 /* out = num / den elementwise (fp32).  replaces: utils/common.py:425. */
 int edtr_divide(const float* num, const float* den, float* out, int64_t n, edtr_stream_t stream);
+/* ---- The same overlap-add for ALL windows of a plane in one launch each (additive to ABI 10) --------------------------------------
+ * Window table: n pairs (hi, wi), int32, table[2 k] = first row and table[2 k + 1] = first column of window k; every window is
+ * th x tw.  As with edtr_image_desc the table comes twice: a HOST array the entry point checks everything on before anything is
+ * launched, and a DEVICE array with the same values that the kernel reads.  Errors (nothing is launched): a NULL pointer
+ * EDTR_E_NULL; a non-positive extent, n <= 0 or n > EDTR_TILE_WINDOWS_MAX, th > H, tw > W, a window outside the plane and — for the
+ * blend — a pixel of the plane that no window covers EDTR_E_SHAPE; a pointer that is not 4-byte aligned EDTR_E_ALIGN.  Nothing needs
+ * more than that: rows move as float4 where pitch, window start and pointers keep both sides 16-byte aligned, else element-wise. */
+#define EDTR_TILE_WINDOWS_MAX 4096
+/* dst [n * B][C][th][tw], window-major: entry k * B + b = src[b][:, hi_k : hi_k + th, wi_k : wi_k + tw] of src [B][C][H][W] (fp32):
+ * the bytes of torch.cat of the window slices along dim 0.  float4 or scalar is decided per window on the device (wi_k % 4).
+ * replaces: the per-window slicing x[..., hi:hi_end, wi:wi_end], utils/common.py:411. */
+int edtr_tile_gather(const float* src, int B, int C, int H, int W, const int32_t* table_host, const int32_t* table, int n, int th,
+                     int tw, float* dst, edtr_stream_t stream);
+/* out [B][C][H][W] = sum_k tiles[k * B + b][c][y - hi_k][x - wi_k] * wts[y - hi_k][x - wi_k] / sum_k wts[...] over the windows k that
+ * cover (y, x), walked in table order; tiles [n * B][C][th][tw] window-major, wts [th][tw].  Every output element is written once:
+ * no count plane, no zero fill, no read-modify-write, no atomics.  The bits are those of zeroed out / count planes ->
+ * edtr_tile_accumulate for k = 0 .. n - 1 -> edtr_divide (one fma per window onto a +0 numerator, one addition per window onto a
+ * +0 denominator, one division).  replaces: utils/common.py:415-425. */
+int edtr_tile_blend(const float* tiles, const float* wts, const int32_t* table_host, const int32_t* table, int n, int th, int tw,
+                    float* out, int B, int C, int H, int W, edtr_stream_t stream);
 
 /* Tiled VAE (reference utils/tilevae/tilevae.py:232-304, GroupNormParam): sums is [T][BG][2] fp64 holding, per tile,
  * the edtr_gn_stats result of each (image, group).  Replaces them IN PLACE by the pair that makes edtr_gn_apply use the

@@ -450,6 +450,43 @@ def gen_demo():
     print("demo_flow.npz written: padded", tuple(x.shape), "restored", tuple(out["res"].shape), "range", float(res.min()), float(res.max()))
 
 
+def gen_demotiled():
+    """`gen_demo` with all four stages tiled (demo.py:94-123 with --pre-res-tiled --vae-encoder-tiled --cldm-tiled --vae-decoder-tiled)
+    through the REFERENCE's own functions, at the smallest sizes that give more than one window on both axes at every stage: a 136 x 200
+    image -> pad_if_smaller(128) -> pad_to_multiples_of(64) = 192 x 256 -> make_tiled_fn(SwinIR, 128, 64) (six windows) ->
+    vae_encode(tiled, tile 64: six tiles) -> q_sample(200) -> 4 steps, latent 24 x 32 tiled 16 / 8 (six windows) -> vae_decode(tiled,
+    tile 8) -> wavelet_reconstruction -> crop.  The golden of restore_dataset(pad_mode="demo", tiling=...)."""
+    ControlLDM, Diffusion, SpacedSampler, ref_common = ref_import.import_reference()
+    cldm, cfg = build_reference_cldm("tiny")
+    swinir = build_reference_swinir("small", synth.swinir_small_config())
+    diffusion = Diffusion(linear_start=0.00085, linear_end=0.0120, timesteps=1000)
+    sampler = SpacedSampler(diffusion.betas)
+    img = synth.synth_input("demotiled:lq", (1, 3, 136, 200), 0.0, 1.0)
+    h0, w0 = img.shape[2:]
+    x = ref_common.pad_to_multiples_of(ref_common.pad_if_smaller(img, size=128), multiple=64)
+    c_txt = synth.synth_input("demo:c_txt", (1, 77, cfg["unet_cfg"]["context_dim"]), -1.0, 1.0)
+    out = {"padded_shape": np.array(x.shape), "input_name": np.array("demotiled:lq"), "input": img[0].numpy().astype(np.float16),
+           "sizes": np.array([128, 64, 64, 8, 128, 64]),      # pre_res size / stride, encoder tile, decoder tile, cldm size / stride
+           "noise_names": np.array([f"demotiled:noise{i}" for i in range(5)])}
+    assert len(ref_common.sliding_windows(192, 256, 128, 64)) == 6 and len(ref_common.sliding_windows(24, 32, 16, 8)) == 6
+    with torch.no_grad(), contextlib.redirect_stdout(io.StringIO()), contextlib.redirect_stderr(io.StringIO()):
+        pre = ref_common.make_tiled_fn(swinir, size=128, stride=64)(x)
+        z_pre = cldm.vae_encode(pre * 2 - 1, sample=False, tiled=True, tile_size=64)
+        noises = [synth.synth_normal(str(n), tuple(z_pre.shape)) for n in out["noise_names"]]
+        with injected_noise(noises):
+            noise = torch.randn_like(z_pre)
+            z_partial = diffusion.q_sample(x_start=z_pre, t=torch.tensor([200], dtype=torch.int64), noise=noise)
+            z = sampler.manual_sample_with_timesteps(model=cldm, device="cpu", x_T=z_partial, steps=4, used_timesteps=USED_TIMESTEPS,
+                                                     batch_size=1, cond=dict(c_txt=c_txt, c_img=z_pre), uncond=None, cfg_scale=1.0,
+                                                     tiled=True, tile_size=128 // 8, tile_stride=64 // 8, progress=False)
+        res = (cldm.vae_decode(z, tiled=True, tile_size=8) + 1) / 2
+        res = ref_common.wavelet_reconstruction(res, pre)[0]
+    out.update(pre_res=pre.numpy().astype(np.float16), z_pre=z_pre.numpy(), z=z.numpy(), res=res[:, :h0, :w0].numpy())
+    np.savez_compressed(os.path.join(GOLD, "demo_tiled.npz"), **out)
+    print("demo_tiled.npz written: padded", tuple(x.shape), "latent", tuple(z.shape), "restored", tuple(out["res"].shape),
+          "range", float(res.min()), float(res.max()))
+
+
 TOKEN_PROMPTS = [
     "", "a cat", "A photo of a DOG, running fast!", "remove dense noise", "high quality, 8k, ultra-detailed",
     "it's the artist's best work; they've said so", "  multiple   spaces\tand\nnewlines  ", "naïve café — déjà vu",
@@ -598,7 +635,7 @@ def main():
     todo = args.only.split(",")
     for name in todo:
         {"schedule": gen_schedule, "tiny": gen_tiny, "sd21": gen_sd21, "tiled": gen_tiled, "tiledvae": gen_tiledvae,
-         "vaesample": gen_vaesample, "heavy": gen_heavy, "wavelet": gen_wavelet, "clip": gen_clip, "psnr": gen_psnr, "swinir": gen_swinir, "full": gen_full, "tokens": gen_tokens, "bpe": gen_bpe, "demo": gen_demo, "moderate": gen_moderate}[name]()
+         "vaesample": gen_vaesample, "heavy": gen_heavy, "wavelet": gen_wavelet, "clip": gen_clip, "psnr": gen_psnr, "swinir": gen_swinir, "full": gen_full, "tokens": gen_tokens, "bpe": gen_bpe, "demo": gen_demo, "demotiled": gen_demotiled, "moderate": gen_moderate}[name]()
 
 
 if __name__ == "__main__":
