@@ -13,6 +13,7 @@ BF16, F16, F32_SPLIT, F32_H1, F32_H2, F32_H3 = 0, 1, 2, 3, 4, 5
 ACT_NONE, ACT_GEGLU, ACT_SILU, ACT_GELU, ACT_LRELU = 0, 1, 2, 3, 4
 SQDIFF_BLOCKS = 64          # EDTR_SQDIFF_BLOCKS: fp64 partial sums per image of edtr_image_sqdiff
 TILE_WINDOWS_MAX = 4096     # EDTR_TILE_WINDOWS_MAX: windows per table of edtr_tile_gather / edtr_tile_blend
+RESIZE_BILINEAR, RESIZE_BICUBIC, RESIZE_AREA = 0, 1, 2      # EDTR_RESIZE_*: modes of edtr_degrade_resize
 
 DECLARED_SYMBOLS = [
     "edtr_abi_version", "edtr_error_string", "edtr_device_info", "edtr_igemm", "edtr_flash_attn64",
@@ -26,6 +27,7 @@ DECLARED_SYMBOLS = [
     "edtr_image_resize_u8", "edtr_image_ingest", "edtr_image_emit", "edtr_image_sqdiff",
     "edtr_image_resize_h_batch", "edtr_image_resize_ingest_batch", "edtr_image_emit_batch",
     "edtr_tile_gather", "edtr_tile_blend",
+    "edtr_degrade_filter2d", "edtr_degrade_resize", "edtr_degrade_gaussian_noise", "edtr_degrade_jpeg",
 ]
 
 
@@ -278,6 +280,11 @@ def load() -> C.CDLL:
     # the window-table forms of the tiled path (edtr_hip.h "The same overlap-add for ALL windows"): table_host is a ctypes int32 array
     lib.edtr_tile_gather.argtypes = [vp, i32, i32, i32, i32, C.POINTER(i32), vp, i32, i32, i32, vp, vp]
     lib.edtr_tile_blend.argtypes = [vp, vp, C.POINTER(i32), vp, i32, i32, i32, vp, i32, i32, i32, i32, vp]
+    # the degradation stage (edtr_hip.h "Low-quality inputs"): per-image host arrays are ctypes float / int32 arrays
+    lib.edtr_degrade_filter2d.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, vp]
+    lib.edtr_degrade_resize.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
+    lib.edtr_degrade_gaussian_noise.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.POINTER(f32), vp, C.POINTER(i32), vp, u64, vp, i64, i64, i32, vp]
+    lib.edtr_degrade_jpeg.argtypes = [vp, vp, i32, i32, i32, i32, C.POINTER(f32), vp, vp, vp, vp]
     if lib.edtr_abi_version() != 10:
         raise RuntimeError("libedtr_hip.so ABI version mismatch")
     _lib = lib

@@ -775,6 +775,44 @@ def make_image_sqdiff(*, a, b, sizes, crop_border: int, y_channel: bool, partial
     return Rec(L.load().edtr_image_sqdiff, args, (a, b, sizes, partials, out), name, 0.0, 24.0 * B * H * W)
 
 
+# -- the degradation stage (edtr_hip.h "Low-quality inputs"; the callers and the host restatements are edtr_amd/degrade.py) -----------
+def make_degrade_filter2d(*, x, kernels, out, name="degrade.filter2d") -> Rec:
+    """fp32 ``x`` [B, 3, H, W] blurred with fp32 ``kernels`` [B or 1, k, k] (correlation, reflect borders) -> ``out``."""
+    B, ch, H, W = x.shape
+    n, k, _ = kernels.shape
+    args = (ptr(x), ptr(out), B, ch, H, W, ptr(kernels), n, k)
+    return Rec(L.load().edtr_degrade_filter2d, args, (x, kernels, out), name, 2.0 * x.numel() * k * k, 8.0 * x.numel())
+
+
+def make_degrade_resize(*, x, out, mode: int, name="degrade.resize") -> Rec:
+    """fp32 ``x`` [B, 3, ih, iw] -> ``out`` [B, 3, oh, ow] as F.interpolate(size=, mode=lib.RESIZE_*)."""
+    B, ch, ih, iw = x.shape
+    args = (ptr(x), ptr(out), B, ch, ih, iw, out.shape[2], out.shape[3], int(mode))
+    return Rec(L.load().edtr_degrade_resize, args, (x, out), name, 0.0, 4.0 * (x.numel() + out.numel()))
+
+
+def make_degrade_gaussian_noise(*, x, out, noise_out, sigma, gray, source, draw: int, rounds: bool, name="degrade.gaussian_noise") -> Rec:
+    """``out`` = clamp(``x`` + n * sigma[b] / 255) with n from ``source``'s stream; ``sigma`` / ``gray``: one Python value per image
+    (uploaded here, and handed to the entry point as host arrays as well); ``noise_out``: None or a tensor that receives n."""
+    B, ch, H, W = x.shape
+    sig_host, gray_host = (ct.c_float * B)(*sigma), (ct.c_int32 * B)(*gray)
+    sig = torch.tensor(list(sig_host), dtype=torch.float32).to(x.device)
+    gry = torch.tensor(list(gray_host), dtype=torch.int32).to(x.device)
+    seed, ids_p, base, ids = _noise_args(source, B, x.device, name)
+    args = (ptr(x), ptr(out), ptr(noise_out), B, ch, H, W, sig_host, ptr(sig), gray_host, ptr(gry), seed, ids_p, base, int(draw), int(rounds))
+    return Rec(L.load().edtr_degrade_gaussian_noise, args, (x, out, noise_out, sig_host, sig, gray_host, gry, ids), name, 0.0, 8.0 * x.numel())
+
+
+def make_degrade_jpeg(*, x, out, quality, factor, dct, coefs=None, name="degrade.jpeg") -> Rec:
+    """DiffJPEG of ``x`` -> ``out``; ``quality``: one Python float per image (checked by the entry point), ``factor``: fp32 [B] device
+    tensor of their quality_to_factor, ``dct``: the fp32 [64, 64] table on the device, ``coefs``: None or fp32 [B, 6 mcus, 64]."""
+    B, ch, H, W = x.shape
+    q_host = (ct.c_float * B)(*quality)
+    args = (ptr(x), ptr(out), B, ch, H, W, q_host, ptr(factor), ptr(dct), ptr(coefs))
+    mcus = ((H + 15) // 16) * ((W + 15) // 16)
+    return Rec(L.load().edtr_degrade_jpeg, args, (x, out, q_host, factor, dct, coefs), name, 4.0 * B * mcus * 6 * 4096, 8.0 * x.numel())
+
+
 def make_cast16(*, dtype, src: torch.Tensor, rows: int, C: int, dst: torch.Tensor, name="cast16") -> Rec:
     args = (dt_code(dtype), ptr(src), rows, C, src.stride(0), ptr(dst), dst.stride(0))
     return Rec(L.load().edtr_cast16, args, (src, dst), name, 0.0, 6.0 * rows * C)

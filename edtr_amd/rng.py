@@ -21,6 +21,10 @@ import numpy as np
 
 PURPOSE_Q_SAMPLE, PURPOSE_STEP, PURPOSE_X_T, PURPOSE_VAE = 0, 1, 2, 3
 PURPOSES = (PURPOSE_Q_SAMPLE, PURPOSE_STEP, PURPOSE_X_T, PURPOSE_VAE)
+# colour / grey noise of edtr_degrade_gaussian_noise (draw = the degradation stage): the same stream, but drawn by that kernel alone —
+# edtr_normal_fill and `normal_reference` keep refusing them, `stream_reference` evaluates them
+PURPOSE_DEGRADE, PURPOSE_DEGRADE_GRAY = 4, 5
+DEGRADE_PURPOSES = (PURPOSE_DEGRADE, PURPOSE_DEGRADE_GRAY)
 Z_MAX = float(np.sqrt(48.0 * np.log(2.0)))      # u1 >= 2^-24: no value of the stream is larger in magnitude
 
 _M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
@@ -63,9 +67,16 @@ def _check_ids(image_ids) -> List[int]:
 def normal_reference(seed: int, image_ids, purpose: int, draw, per_image: int) -> np.ndarray:
     """float64 [B][per_image]: the stream of the module docstring, evaluated in double precision from the exact uniforms.
     ``draw`` is one int for the whole batch or one per image (the device-index sampler form reads it per image)."""
-    seed, ids = _check_seed(seed), _check_ids(image_ids)
     if purpose not in PURPOSES:
         raise ValueError(f"purpose must be one of {PURPOSES}, got {purpose}")
+    return stream_reference(seed, image_ids, purpose, draw, per_image)
+
+
+def stream_reference(seed: int, image_ids, purpose: int, draw, per_image: int) -> np.ndarray:
+    """`normal_reference` for every purpose of the header, the two of the degradation stage (`DEGRADE_PURPOSES`) included."""
+    seed, ids = _check_seed(seed), _check_ids(image_ids)
+    if purpose not in PURPOSES + DEGRADE_PURPOSES:
+        raise ValueError(f"purpose must be one of {PURPOSES + DEGRADE_PURPOSES}, got {purpose}")
     if per_image <= 0 or per_image % 4:
         raise ValueError(f"per_image must be a positive multiple of 4, got {per_image}")
     B, G = len(ids), per_image // 4

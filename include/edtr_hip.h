@@ -801,6 +801,71 @@ int edtr_image_emit_batch(const float* batch, int B, int channels, int H, int W,
 int edtr_image_sqdiff(const float* a, const float* b, int B, int channels, int H, int W, const int32_t* sizes, int crop_border,
                       int y_channel, double* partials, double* out, edtr_stream_t stream);
 
+/* ---- Low-quality inputs: blur -> resize -> Gaussian noise -> JPEG on the device (additive to ABI 10) -----------------------------
+ * One stage of the reference's synthetic degradation (datasets/detection_cocov2.py:426-460; with a second resize back to the input
+ * extent, datasets/detection.py:155-181) as four launches on fp32 NCHW batches [B][3][H][W] (`channels` == 3, EDTR_E_UNSUPPORTED
+ * otherwise) — the layout edtr_image_ingest writes and edtr_image_emit reads.  Every result is a bit-exact function of its inputs:
+ * each product, sum and quotient named below is ONE correctly rounded fp32 operation (fmul, fadd, fdiv; never an FMA) in the order
+ * given, and edtr_amd/degrade.py repeats every kernel in numpy.  Common errors (nothing is launched): a NULL tensor EDTR_E_NULL; B
+ * <= 0 or > 65535 or a non-positive extent EDTR_E_SHAPE; an extent above 2^24 EDTR_E_UNSUPPORTED; a tensor that is not 4-byte
+ * aligned EDTR_E_ALIGN.  Per-image parameters come twice, as the image descriptors do: a HOST array that is checked here and a
+ * DEVICE array with the same values that the kernel reads.  Poisson noise, the sinc filter and USM sharpening are not provided. */
+/* out[b][c][y][x] = sum over (ky, kx), ky major, of fmul(x[b][c][R(y + ky - k/2)][R(x + kx - k/2)], kernels[b][ky][kx]), accumulated
+ * with fadd from 0.0f: a correlation (no flip, as F.conv2d) over F.pad(mode="reflect") borders, R(i) = -i below 0 and 2 (n - 1) - i
+ * from n on (the edge sample is not repeated).  kernels: fp32 [n_kernels][k][k] on the device, n_kernels == B, or 1 = one kernel for
+ * every image.  k odd, 3 <= k <= 41, k / 2 < min(H, W) (EDTR_E_SHAPE otherwise); out must not alias x (EDTR_E_UNSUPPORTED).  The
+ * input tile with its halo and the taps are staged in LDS once per 32 x 32 output tile.  replaces: filter2D, datasets/utils.py:71-96. */
+int edtr_degrade_filter2d(const float* x, float* out, int B, int channels, int H, int W, const float* kernels, int n_kernels, int k,
+                          edtr_stream_t stream);
+/* F.interpolate(x, size=(out_h, out_w), mode=..., align_corners=False, antialias=False) for the three modes the reference draws from.
+ * Coordinates are ATen's area_pixel_compute_source_index in fp32: scale = fdiv((float)in, (float)out) (formed on the host),
+ *   src(dst) = fadd(fmul(scale, fadd((float)dst, 0.5f)), -0.5f);   idx = min(floor(src), in - 1);   t = clamp(fadd(src, -idx), 0, 1)
+ * NOTE F.interpolate(scale_factor=s) maps with 1/s instead of in/out unless recompute_scale_factor is set: the two differ whenever
+ * in * s is not an integer, so this entry (and the Python layer) takes explicit output extents only.
+ *   bilinear: src is first raised to 0; i1 = idx + (idx < in - 1); w0 = fadd(1, -t), w1 = t; per row r: fadd(fmul(w0x, p[r][x0]),
+ *             fmul(w1x, p[r][x1])); out = fadd(fmul(w0y, row0), fmul(w1y, row1))
+ *   bicubic:  A = -0.75; taps idx - 1 .. idx + 2, each clamped into [0, in - 1]; weights c2(t + 1), c1(t), c1(u), c2(u + 1) with
+ *             u = fadd(1, -t), c1(v) = ((1.25 v - 2.25) v) v + 1, c2(v) = ((-0.75 v + 3.75) v - 6) v + 3 evaluated left to right;
+ *             per row the four products are added left to right, then the four rows the same way
+ *   area:     adaptive_avg_pool2d: rows [floor(oy in_h / out_h), ceil((oy + 1) in_h / out_h)), columns alike (integers); the window
+ *             is added row-major from 0.0f and divided (fdiv) by its element count
+ * mode outside EDTR_RESIZE_* EDTR_E_DTYPE; out must not alias x. */
+#define EDTR_RESIZE_BILINEAR 0
+#define EDTR_RESIZE_BICUBIC 1
+#define EDTR_RESIZE_AREA 2
+int edtr_degrade_resize(const float* x, float* out, int B, int channels, int in_h, int in_w, int out_h, int out_w, int mode,
+                        edtr_stream_t stream);
+/* out = clamp(fadd(x, fdiv(fmul(n, sigma[b]), 255)), 0, 1), or with rounds = 1 fdiv(clamp(rint(fmul(that sum, 255)), 0, 255), 255)
+ * (rint: half to even, as torch.round), n from the stream of "Reproducible noise" with two further purposes: colour noise (gray[b] == 0)
+ * is EDTR_NOISE_DEGRADE with per_image = 3 H W and e = (c H + y) W + x; grey noise (gray[b] == 1) is EDTR_NOISE_DEGRADE_GRAY with
+ * per_image = H W and e = y W + x, one plane shared by the three channels.  `draw` = the number of the degradation stage; key, image
+ * id and the ids' two forms as for every stream consumer.  H W % 4 != 0, or x / out / noise_out not 16-byte aligned: EDTR_E_ALIGN.
+ * sigma (fp32 [B], in units of 1/255; finite and >= 0, EDTR_E_SHAPE) and gray (int32 [B]; 0 or 1, EDTR_E_DTYPE) come as host and device
+ * arrays.  noise_out (optional, fp32 [B][3][H][W]) receives n itself.  out may alias x.  edtr_normal_fill does not serve these two
+ * purposes.  replaces: add_gaussian_noise_pt with torch.randn, datasets/degradation.py:461-512. */
+#define EDTR_NOISE_DEGRADE 4        /* colour noise of edtr_degrade_gaussian_noise (draw = stage) */
+#define EDTR_NOISE_DEGRADE_GRAY 5   /* grey noise of edtr_degrade_gaussian_noise (draw = stage) */
+int edtr_degrade_gaussian_noise(const float* x, float* out, float* noise_out, int B, int channels, int H, int W, const float* sigma_host,
+                                const float* sigma, const int32_t* gray_host, const int32_t* gray, uint64_t seed, const int64_t* image_ids,
+                                int64_t image_id_base, int64_t draw, int rounds, edtr_stream_t stream);
+/* DiffJPEG(differentiable=False) with one quality per image, in one launch; a workgroup owns whole 16 x 16 MCUs (four luma and two
+ * chroma blocks) and no intermediate plane reaches memory.  With p = fmul(x, 255) inside the image and 0 in the padding to multiples
+ * of 16, m = the float32 values of the file's matrices, and every three-term sum added left to right:
+ *   Y = r m00 + g m01 + b m02;  Cb = (r m10 + g m11 + b m12) + 128;  Cr alike;  chroma 2 x 2 mean = fmul(((a00 + a01) + a10) + a11, 0.25)
+ *   d = sample - 128;  F[u][v] = fmul(scale[u][v], sum over (x, y), x major, of fmul(d[x][y], T[x][y][u][v])) from 0.0f, x = row
+ *   q = rint(fdiv(F, tq)), tq = fmul(table[u][v], factor[b]): the TRANSPOSED luminance table for Y (as the file builds it), the
+ *       chrominance table for Cb / Cr;   back: c = fmul(fmul(q, tq), alpha[u][v])
+ *   sample' = fadd(fmul(0.25, sum over (u, v), u major, of fmul(c[u][v], T[p][q][u][v])), 128);  chroma repeated 2 x 2
+ *   R = Y' 1 + (Cb' - 128) 0 + (Cr' - 128) 1.402, G and B with their rows;  out = fdiv(min(255, max(0, .)), 255), cropped to H x W
+ * dct: fp32 [64][64] on the device, dct[x 8 + y][u 8 + v] = float32(cos((2 x + 1) u pi / 16) cos((2 y + 1) v pi / 16)) with the
+ * product formed in fp64 (the caller builds it: no device cosine decides a bit); scale = float32(alpha alpha^T / 4), alpha = (1/sqrt 2,
+ * 1, ..., 1).  quality_host: fp32 [B], each in (0, 100] (EDTR_E_SHAPE); factor: fp32 [B] on the device, quality_to_factor of it
+ * evaluated in fp32 (5000 / q / 100 below 50, (200 - 2 q) / 100 from 50 on; quality 100 gives factor 0 and, as in the file, no finite
+ * result).  coefs (optional): fp32 [B][ny + 2 nc][8][8] receives q — the ny = Hp/8 Wp/8 luma blocks in raster order, then the nc =
+ * Hp/16 Wp/16 Cb blocks, then Cr (Hp, Wp the padded extents).  out may alias x.  replaces: DiffJPEG.forward, datasets/diffjpeg.py:450-492. */
+int edtr_degrade_jpeg(const float* x, float* out, int B, int channels, int H, int W, const float* quality_host, const float* factor,
+                      const float* dct, float* coefs, edtr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * hipGraph capture of a launch sequence issued on `stream` (one denoise step, or a whole batch).
  * ---------------------------------------------------------------------------------------- */

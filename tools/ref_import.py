@@ -1,6 +1,6 @@
 """Make the read-only reference tree at /root/reference importable on CPU in THIS container.
 
-Only used by tools/make_goldens.py (fixture generation) — never by tests, bench or the
+Only used by tools/make_goldens.py and tools/make_degrade_goldens.py (fixture generation) — never by tests, bench or the
 product.  The reference needs four packages the image lacks (torchvision, omegaconf, ftfy,
 timm); none of them is touched by the restoration hot path, so inert
 stand-in modules are registered before the import.
@@ -58,6 +58,27 @@ def install_stubs() -> None:
     if "omegaconf" not in sys.modules:
         _module("omegaconf")
         _module("omegaconf.listconfig", ListConfig=type("ListConfig", (list,), {}))
+
+
+def install_degrade_stubs() -> None:
+    """Stand-ins for what datasets/utils.py and datasets/degradation.py import at module level and the degradation functions
+    that tools/make_degrade_goldens.py calls never touch: cv2 and torchvision's rgb_to_grayscale."""
+    if "cv2" not in sys.modules:
+        _module("cv2")
+    install_stubs()
+    if "torchvision.transforms._functional_tensor" not in sys.modules:
+        _module("torchvision.transforms._functional_tensor", rgb_to_grayscale=lambda x, *a, **k: x)
+
+
+def import_reference_file(name: str, relpath: str):
+    """One source file of the reference as a module of its own (its package's __init__ is not run)."""
+    import importlib.util
+    import os
+    sys.dont_write_bytecode = True
+    spec = importlib.util.spec_from_file_location(name, os.path.join(REFERENCE_ROOT, relpath))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
 
 
 def import_reference():
