@@ -1,24 +1,31 @@
-"""Low-quality inputs from high-quality ones, on the device: the blur -> resize -> Gaussian noise -> JPEG chain that the reference
-applies on the CPU before every evaluation (one stage of RealESRGANBatchTransform, datasets/detection_cocov2.py:426-460; with a final
-resize back to the input extent, the CodeFormer-style chain of datasets/detection.py:155-181).  Four launches of
-include/edtr_hip.h "Low-quality inputs" (five with the resize back) on the fp32 NCHW batches that `imageio.ingest` writes.
+"""Low-quality inputs from high-quality ones, on the device: the blur -> resize -> noise -> JPEG chain that the reference applies on the
+CPU before every evaluation.  One stage of it (`degrade_batch`: datasets/detection_cocov2.py:426-460; with a final resize back to the
+input extent, the CodeFormer-style chain of datasets/detection.py:155-181) is four launches of include/edtr_hip.h "Low-quality inputs"
+(five with the resize back); the whole second-order Real-ESRGAN chain (`degrade_batch2`: RealESRGANBatchTransform.__call__, :413-539 —
+USM sharpening, two stages with Gaussian or Poisson noise, the final sinc filter, the resize back) adds the launches of "Low-quality
+inputs, second order".  All on the fp32 NCHW batches that `imageio.ingest` writes.
 
-    python -m edtr_amd.degrade --input DIR --output DIR --config YAML|codeformer|realesrgan-stage1 --seed N [--batch-size N --workers N]
+    python -m edtr_amd.degrade --input DIR --output DIR --config YAML|codeformer|realesrgan-stage1|realesrgan --seed N [--batch-size N --workers N]
 
-writes ``gt/<stem>.png`` and ``lq/<stem>.png`` under the output folder, as the reference's generators do.
+writes ``gt/<stem>.png`` and ``lq/<stem>.png`` under the output folder, as the reference's generators do (``gt/`` is the sharpened
+image where the configuration sharpens, as the reference's GT is).
 
 Three layers:
-  * `filter2d`, `resize`, `add_gaussian_noise`, `jpeg`: thin wrappers over the launches (torch tensors on the device);
+  * `filter2d`, `resize`, `add_gaussian_noise`, `jpeg`, `add_poisson_noise`, `sepblur`, `usm_sharpen`: thin wrappers over the launches
+    (torch tensors on the device);
   * `*_reference`: the numpy restatement of each, operation for operation in fp32.  They are the NORMATIVE definition: the kernels are
-    tested against them by equality, and they against the reference's own functions within its fp32 error (tests/golden/degrade.npz);
+    tested against them by equality, and they against the reference's own functions within its fp32 error (tests/golden/degrade.npz,
+    tests/golden/degrade2.npz);
   * host-side parameter synthesis in numpy: the isotropic / anisotropic Gaussian, generalized Gaussian and plateau blur kernels and
-    their mixture draw (our restatement of datasets/degradation.py:17-387), `DegradeConfig` with the reference's YAML keys, and
-    `draw_params(cfg, seed, image_id)`, which draws one image's parameters from ``numpy.random.default_rng([seed, image_id])``.
+    their mixture draw (our restatement of datasets/degradation.py:17-387), the sinc kernel (`circular_lowpass_kernel`, with a Bessel J1
+    of its own), the Poisson inversion tables (`poisson_table`), `DegradeConfig` / `RealESRGANConfig` with the reference's YAML keys,
+    and `draw_params` / `draw_params2`, which draw one image's parameters from ``numpy.random.default_rng([seed, image_id])``.
     An image's low-quality version therefore depends on its bytes, the seed and its data-set index alone — not on the batch it
     travels in, the order, or the number of ranks: the promise `rng.NoiseSource` makes for the sampler's noise.
 
-Left out: Poisson noise (torch.poisson has no stream that could be restated), the sinc filter, and USM sharpening (its kernel comes
-from cv2).  The noise here is always Gaussian."""
+Poisson noise is not torch.poisson (which has no stream that could be restated) but table inversion on the seeded Philox stream:
+integer-only and loop-free, so kernel and numpy agree by construction.  Left out: the training pair pool (`queue_size` > 0), which
+mixes images across batches and would break that promise."""
 from __future__ import annotations
 
 import argparse
@@ -30,7 +37,8 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .rng import PURPOSE_DEGRADE, PURPOSE_DEGRADE_GRAY, stream_reference
+from .rng import (PURPOSE_DEGRADE, PURPOSE_DEGRADE_GRAY, PURPOSE_DEGRADE_POISSON, PURPOSE_DEGRADE_POISSON_GRAY, stream_reference,
+                  uniform_words_reference)
 
 F32 = np.float32
 MODES = ("bilinear", "bicubic", "area")                  # EDTR_RESIZE_BILINEAR / _BICUBIC / _AREA, in that order
@@ -409,20 +417,26 @@ PRESETS = {
 }
 
 
-def load_config(spec) -> DegradeConfig:
-    """A `DegradeConfig`, the name of a preset, or the path of a YAML file with the keys."""
-    if isinstance(spec, DegradeConfig):
+def load_config(spec):
+    """A `DegradeConfig` / `RealESRGANConfig`, the name of a preset, or the path of a YAML file with the keys.  "realesrgan", or a YAML
+    that carries a `batch_transform` node (the reference's layout of the second-order chain), gives a `RealESRGANConfig`."""
+    if isinstance(spec, (DegradeConfig, RealESRGANConfig)):
         return spec
+    if spec == "realesrgan":
+        return RealESRGANConfig()
     if spec in PRESETS:
         return DegradeConfig(**PRESETS[spec])
     if not os.path.exists(spec):
-        raise ValueError(f"--config must be one of {sorted(PRESETS)} or a YAML file, got {spec!r}")
+        raise ValueError(f"--config must be one of {sorted(PRESETS) + ['realesrgan']} or a YAML file, got {spec!r}")
     try:
         import yaml
     except ImportError as e:
         raise RuntimeError("reading a YAML configuration needs PyYAML (`import yaml` failed); the presets need nothing") from e
     with open(spec) as fh:
-        return DegradeConfig.from_dict(yaml.safe_load(fh))
+        d = yaml.safe_load(fh)
+    if isinstance(d, dict) and ("batch_transform" in d or (isinstance(d.get("dataset"), dict) and "batch_transform" in d["dataset"])):
+        return RealESRGANConfig.from_dict(d)
+    return DegradeConfig.from_dict(d)
 
 
 @dataclass
@@ -465,6 +479,573 @@ def draw_params(cfg: DegradeConfig, seed: int, image_id: int) -> DegradeParams:
         if quality >= 100.0:                # (the factor of quality 100 is 0: the reference's uniform draw never reaches its upper end either)
             quality = float(np.nextafter(F32(100.0), F32(0.0)))
     return DegradeParams(kernel, scale, mode, sigma, bool(u_gray < cfg.gray_noise_prob), quality, bool(cfg.resize_back))
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# second order: Poisson noise by table inversion (numpy restatement, normative; edtr_hip.h "Low-quality inputs, second order")
+# ----------------------------------------------------------------------------------------------------------------------------------
+POISSON_VALS = tuple(1 << t for t in range(9))                    # the 9 values 2^ceil(log2(count)) can take for count in 1..256
+GRAY_WEIGHTS = (F32(0.2989), F32(0.587), F32(0.114))              # torchvision's rgb_to_grayscale
+_POISSON_TABLES: dict = {}
+
+
+def poisson_table(vals: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(T uint32 [256][256], lo int32 [256]) for ``vals``: row k inverts the CDF of Poisson(lambda_k) on a 32-bit uniform, n = lo[k] +
+    #{j < 255 : T[k][j] <= u}.  fp64 with + * / alone, every sum in index order (edtr_hip.h states each step): the same bits on every
+    host.  Cached."""
+    vals = int(vals)
+    if vals not in POISSON_VALS:
+        raise ValueError(f"vals must be one of {POISSON_VALS}, got {vals}")
+    if vals not in _POISSON_TABLES:
+        lam = ((np.arange(256, dtype=F32) / F32(255.0)) * F32(vals)).astype(np.float64)
+        fl = np.floor(lam).astype(np.int64)
+        lo = np.maximum(0, np.ceil(lam).astype(np.int64) - 128)
+        J = 128 + 256 + 1                                       # indices 0 .. lo + 256 with lo <= 128; floor(lambda) <= 256 lies inside
+        rows = np.arange(256)
+        w = np.zeros((256, J), dtype=np.float64)
+        w[rows, fl] = 1.0
+        for j in range(1, J):
+            w[:, j] = np.where(j > fl, (w[:, j - 1] * lam) / np.float64(j), w[:, j])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            for j in range(J - 2, -1, -1):
+                w[:, j] = np.where(j < fl, (w[:, j + 1] * np.float64(j + 1)) / lam, w[:, j])
+        w = np.where(np.arange(J)[None, :] <= (lo + 256)[:, None], w, 0.0)
+        c = np.add.accumulate(w, axis=1)                        # strictly sequential: c[j] = c[j - 1] + w[j]
+        total = c[rows, lo + 256]
+        cdf = c[rows[:, None], lo[:, None] + np.arange(256)[None, :]] / total[:, None]
+        T = np.minimum(np.floor(cdf * 4294967296.0), 4294967295.0).astype(np.uint64).astype(np.uint32)
+        _POISSON_TABLES[vals] = (np.ascontiguousarray(T), lo.astype(np.int32))
+    return _POISSON_TABLES[vals]
+
+
+def poisson_tables() -> Tuple[np.ndarray, np.ndarray]:
+    """(uint32 [9][256][256], int32 [9][256]): `poisson_table` of 1, 2, ..., 256 — what edtr_degrade_poisson_noise reads."""
+    pairs = [poisson_table(v) for v in POISSON_VALS]
+    return np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
+
+
+def vals_of(count: int) -> int:
+    """2^ceil(log2(count)) in integers"""
+    count = int(count)
+    if not 1 <= count <= 256:
+        raise ValueError(f"a level count lies in [1, 256], got {count}")
+    return 1 << (count - 1).bit_length()
+
+
+def _level(v: np.ndarray) -> np.ndarray:
+    return np.clip(np.rint(v * F32(255.0)), F32(0), F32(255)).astype(np.int64)
+
+
+def _gray_plane(x: np.ndarray) -> np.ndarray:
+    return (GRAY_WEIGHTS[0] * x[:, 0] + GRAY_WEIGHTS[1] * x[:, 1]) + GRAY_WEIGHTS[2] * x[:, 2]
+
+
+def poisson_levels(x) -> Tuple[np.ndarray, np.ndarray]:
+    """(int64 [B][3][H][W] colour levels, int64 [B][H][W] grey levels) of a batch"""
+    x = _batch(x)
+    return _level(x), _level(_gray_plane(x))
+
+
+def level_counts(x) -> np.ndarray:
+    """int32 [B][2]: the number of distinct colour levels of each image, and of distinct grey levels"""
+    kc, kg = poisson_levels(x)
+    return np.array([[len(np.unique(kc[b])), len(np.unique(kg[b]))] for b in range(kc.shape[0])], dtype=np.int32).reshape(-1, 2)
+
+
+def poisson_reference(seed: int, image_ids, purpose: int, draw, levels, vals) -> np.ndarray:
+    """int64 [B][per_image]: the Poisson draws n of elements whose levels are ``levels`` (int [B][per_image]) under ``vals`` (one per
+    image): table inversion of the raw stream words, by the kernel's 8-step search."""
+    levels = np.asarray(levels, dtype=np.int64)
+    B, per = levels.shape
+    vals = np.broadcast_to(np.asarray(vals, dtype=np.int64).reshape(-1), (B,))
+    u = uniform_words_reference(seed, image_ids, purpose, draw, per)
+    out = np.empty((B, per), dtype=np.int64)
+    for b in range(B):
+        T, lo = poisson_table(int(vals[b]))
+        k = levels[b]
+        pos = np.zeros(per, dtype=np.int64)
+        for step in (128, 64, 32, 16, 8, 4, 2, 1):
+            pos = pos + step * (T[k, pos + step - 1] <= u[b])
+        out[b] = lo[k] + pos
+    return out
+
+
+def poisson_noise_reference(x, gray, seed: int = 0, image_ids=None, draw: int = 0) -> np.ndarray:
+    """fp32 [B][3][H][W]: n / vals - q per element (colour), or per pixel of the grey plane repeated over the channels"""
+    x = _batch(x)
+    B, _, H, W = x.shape
+    if (H * W) % 4:
+        raise ValueError(f"H * W must be a multiple of 4 (the stream is drawn four elements at a time), got {H} x {W}")
+    gray = np.broadcast_to(np.asarray(gray, dtype=np.int32).reshape(-1), (B,))
+    ids = _ids_list(image_ids, B)
+    kc, kg = poisson_levels(x)
+    counts = level_counts(x)
+    noise = np.empty_like(x)
+    for b in range(B):
+        if gray[b]:
+            k, vals, purpose = kg[b].reshape(1, -1), vals_of(counts[b, 1]), PURPOSE_DEGRADE_POISSON_GRAY
+        else:
+            k, vals, purpose = kc[b].reshape(1, -1), vals_of(counts[b, 0]), PURPOSE_DEGRADE_POISSON
+        n = poisson_reference(seed, [ids[b]], purpose, draw, k, [vals])
+        nz = (n.astype(F32) / F32(vals) - k.astype(F32) / F32(255.0)).astype(F32)
+        noise[b] = nz.reshape((1, H, W) if gray[b] else (3, H, W))
+    return noise
+
+
+def _ids_list(image_ids, B: int) -> List[int]:
+    ids = list(range(B)) if image_ids is None else list(image_ids.tolist() if hasattr(image_ids, "tolist") else image_ids)
+    if len(ids) != B:
+        raise ValueError(f"{len(ids)} image ids for a batch of {B}")
+    return [int(i) for i in ids]
+
+
+def add_poisson_noise_reference(x, scale, gray, seed: int = 0, image_ids=None, draw: int = 0, rounds: bool = False, return_noise: bool = False):
+    """add_poisson_noise_pt(clip=True) with torch.poisson replaced by `poisson_reference`: clamp(x + noise * scale, 0, 1), or
+    clamp(round(. * 255), 0, 255) / 255 with ``rounds``."""
+    x = _batch(x)
+    B = x.shape[0]
+    scale = np.broadcast_to(np.asarray(scale, dtype=F32).reshape(-1), (B,)).reshape(B, 1, 1, 1)
+    if not np.isfinite(scale).all() or (scale < 0).any():
+        raise ValueError("scale must be finite and non-negative")
+    noise = poisson_noise_reference(x, gray, seed, image_ids, draw)
+    out = x + noise * scale
+    if rounds:
+        out = (np.clip(np.rint(out * F32(255.0)), F32(0), F32(255)) / F32(255.0)).astype(F32)
+    else:
+        out = np.clip(out, F32(0), F32(1)).astype(F32)
+    return (out, noise) if return_noise else out
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# second order: USM sharpening and the sinc kernels
+# ----------------------------------------------------------------------------------------------------------------------------------
+SEP_K_MIN, SEP_K_MAX = 3, 63
+
+
+def gaussian_taps(k: int, sigma: float = 0.0) -> np.ndarray:
+    """float64 [k]: cv2.getGaussianKernel(k, sigma) by its formula — with a non-positive sigma, sigma = 0.3 ((k - 1) 0.5 - 1) + 0.8 (8.0
+    at k = 51); g_i proportional to exp(-(i - (k - 1)/2)^2 / (2 sigma^2)), normalised in fp64.  cv2 answers k <= 7 with a non-positive
+    sigma from fixed tables instead, so that case is refused."""
+    k = int(k)
+    if k % 2 == 0 or k < 1:
+        raise ValueError(f"the tap count must be odd and positive, got {k}")
+    if sigma <= 0:
+        if k <= 7:
+            raise ValueError("cv2 takes the taps of k <= 7 with a non-positive sigma from fixed tables; give a sigma")
+        sigma = 0.3 * ((k - 1) * 0.5 - 1) + 0.8
+    i = np.arange(k, dtype=np.float64) - (k - 1) * 0.5
+    g = np.exp(-(i * i) / (2.0 * sigma * sigma))
+    return g / g.sum()
+
+
+def _check_taps(taps, H: int, W: int) -> np.ndarray:
+    g = np.ascontiguousarray(taps, dtype=F32).reshape(-1)
+    k = g.shape[0]
+    if k % 2 == 0 or not SEP_K_MIN <= k <= SEP_K_MAX:
+        raise ValueError(f"the tap count must be odd and in [{SEP_K_MIN}, {SEP_K_MAX}], got {k}")
+    if k // 2 >= min(H, W):
+        raise ValueError(f"{k} taps need reflect padding of {k // 2}, more than a {H} x {W} image allows")
+    return g
+
+
+def sepblur_reference(x, taps, threshold: Optional[float] = None):
+    """Separable correlation over reflect-padded borders: along rows, t = t + p * g[kx] from 0 in tap order for every padded row, then
+    along columns the same over t.  With ``threshold`` also the mask (|x - out| * 255 > threshold) as fp32 0 / 1."""
+    x = _batch(x)
+    H, W = x.shape[2:]
+    g = _check_taps(taps, H, W)
+    k = g.shape[0]
+    r = k // 2
+    pad = np.pad(x, ((0, 0), (0, 0), (r, r), (r, r)), mode="reflect")
+    t = np.zeros(pad.shape[:3] + (W,), dtype=F32)
+    for kx in range(k):
+        t = t + pad[:, :, :, kx:kx + W] * g[kx]
+    out = np.zeros_like(x)
+    for ky in range(k):
+        out = out + t[:, :, ky:ky + H] * g[ky]
+    if threshold is None:
+        return out
+    return out, (np.abs(x - out) * F32(255.0) > F32(threshold)).astype(F32)
+
+
+def usm_apply_reference(x, blur, soft, weight: float) -> np.ndarray:
+    x = _batch(x)
+    sharp = np.clip(x + F32(weight) * (x - blur), F32(0), F32(1))
+    return (soft * sharp + (F32(1.0) - soft) * x).astype(F32)
+
+
+def _usm_taps(radius: int) -> np.ndarray:
+    k = int(radius) + (1 if int(radius) % 2 == 0 else 0)
+    if not SEP_K_MIN <= k <= SEP_K_MAX:
+        raise ValueError(f"the USM radius must give a tap count in [{SEP_K_MIN}, {SEP_K_MAX}], got {k}")
+    return gaussian_taps(k).astype(F32)
+
+
+def usm_sharpen_reference(x, weight: float = 0.5, threshold: float = 10, radius: int = 50) -> np.ndarray:
+    """USMSharp(radius)(x, weight, threshold) with the 2-D kernel g g^T applied as two 1-D passes of float32(g)."""
+    g = _usm_taps(radius)
+    blur, mask = sepblur_reference(x, g, threshold)
+    return usm_apply_reference(x, blur, sepblur_reference(mask, g), weight)
+
+
+def bessel_j1(x) -> np.ndarray:
+    """J1(x) = (1 / pi) * integral over [0, pi] of cos(theta - x sin(theta)), by the midpoint rule with 128 points: no scipy.  Exact to
+    1e-15 for |x| <= 45 (the integrand is periodic and analytic); the chain's largest argument is pi * sqrt(200) = 44.4."""
+    x = np.asarray(x, dtype=np.float64)
+    theta = (np.arange(128, dtype=np.float64) + 0.5) * (np.pi / 128.0)
+    return np.cos(theta - x[..., None] * np.sin(theta)).sum(axis=-1) / 128.0
+
+
+def circular_lowpass_kernel(cutoff: float, kernel_size: int, pad_to: int = 0) -> np.ndarray:
+    """The 2-D sinc filter of datasets/degradation.py:390-410 (float64 [k, k], or [pad_to, pad_to] zero-padded)."""
+    kernel_size = int(kernel_size)
+    if kernel_size % 2 != 1:
+        raise ValueError("Kernel size must be an odd number.")
+    c = (kernel_size - 1) / 2
+    ax = np.arange(kernel_size, dtype=np.float64) - c
+    rad = np.sqrt(ax[:, None] ** 2 + ax[None, :] ** 2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        kernel = cutoff * bessel_j1(cutoff * rad) / (2 * np.pi * rad)
+    kernel[(kernel_size - 1) // 2, (kernel_size - 1) // 2] = cutoff ** 2 / (4 * np.pi)
+    kernel = kernel / np.sum(kernel)
+    if pad_to > kernel_size:
+        p = (int(pad_to) - kernel_size) // 2
+        kernel = np.pad(kernel, ((p, p), (p, p)))
+    return kernel
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# second order: configuration and per-image parameters
+# ----------------------------------------------------------------------------------------------------------------------------------
+KERNEL_RANGE = tuple(range(7, 22, 2))           # datasets/detection_cocov2.py:100
+KERNEL_PAD = 21                                 # every kernel is zero-padded to 21 x 21 (:218, :243, :250)
+NOISE_TYPES = ("gaussian", "poisson")
+
+
+def _range(name: str, v, lo: float, hi: float = math.inf) -> Tuple[float, float]:
+    try:
+        a, b = float(v[0]), float(v[1])
+        ok = len(v) == 2
+    except (TypeError, IndexError, ValueError):
+        ok, a, b = False, 0.0, 0.0
+    if not ok or not lo <= a <= b <= hi:
+        raise ValueError(f"{name} must be [a, b] with {lo:g} <= a <= b <= {hi:g}, got {v!r}")
+    return a, b
+
+
+def _prob(name: str, v) -> float:
+    if not 0.0 <= float(v) <= 1.0:
+        raise ValueError(f"{name} must be in [0, 1], got {v}")
+    return float(v)
+
+
+@dataclass
+class RealESRGANConfig:
+    """The reference's keys of the second-order chain: the data set's (`dataset.val.params` / `dataset.params`: the kernels) and the
+    batch transform's (`batch_transform.params`: everything else).  The defaults are configs' coco-deg-realesrgan.yaml."""
+    blur_kernel_size: int = 21
+    kernel_list: Sequence[str] = KERNEL_TYPES
+    kernel_prob: Sequence[float] = (0.45, 0.25, 0.12, 0.03, 0.12, 0.03)
+    sinc_prob: float = 0.1
+    blur_sigma: Sequence[float] = (0.2, 3.0)
+    betag_range: Sequence[float] = (0.5, 4.0)
+    betap_range: Sequence[float] = (1.0, 2.0)
+    blur_kernel_size2: int = 21
+    kernel_list2: Sequence[str] = KERNEL_TYPES
+    kernel_prob2: Sequence[float] = (0.45, 0.25, 0.12, 0.03, 0.12, 0.03)
+    sinc_prob2: float = 0.1
+    blur_sigma2: Sequence[float] = (0.2, 1.5)
+    betag_range2: Sequence[float] = (0.5, 4.0)
+    betap_range2: Sequence[float] = (1.0, 2.0)
+    final_sinc_prob: float = 0.8
+    use_sharpener: bool = True
+    queue_size: int = 0
+    resize_prob: Sequence[float] = (0.2, 0.7, 0.1)
+    resize_range: Sequence[float] = (0.15, 1.5)
+    gray_noise_prob: float = 0.4
+    gaussian_noise_prob: float = 0.5
+    noise_range: Sequence[float] = (1.0, 30.0)
+    poisson_scale_range: Sequence[float] = (0.05, 3.0)
+    jpeg_range: Sequence[float] = (30.0, 95.0)
+    second_blur_prob: float = 0.8
+    stage2_scale: object = 4                    # a number, or a range [a, b] that the scale is drawn from
+    resize_prob2: Sequence[float] = (0.3, 0.4, 0.3)
+    resize_range2: Sequence[float] = (0.3, 1.2)
+    gray_noise_prob2: float = 0.4
+    gaussian_noise_prob2: float = 0.5
+    noise_range2: Sequence[float] = (1.0, 25.0)
+    poisson_scale_range2: Sequence[float] = (0.05, 2.5)
+    jpeg_range2: Sequence[float] = (30.0, 95.0)
+    resize_back: bool = True
+
+    DATASET_KEYS = ("blur_kernel_size", "kernel_list", "kernel_prob", "sinc_prob", "blur_sigma", "betag_range", "betap_range",
+                    "blur_kernel_size2", "kernel_list2", "kernel_prob2", "sinc_prob2", "blur_sigma2", "betag_range2", "betap_range2",
+                    "final_sinc_prob")
+    TRANSFORM_KEYS = ("use_sharpener", "queue_size", "resize_prob", "resize_range", "gray_noise_prob", "gaussian_noise_prob", "noise_range",
+                      "poisson_scale_range", "jpeg_range", "second_blur_prob", "stage2_scale", "resize_prob2", "resize_range2",
+                      "gray_noise_prob2", "gaussian_noise_prob2", "noise_range2", "poisson_scale_range2", "jpeg_range2", "resize_back")
+
+    def __post_init__(self):
+        if int(self.queue_size) > 0:
+            raise ValueError("queue_size > 0 (the training pair pool) is not provided: it mixes images across batches, so an image's "
+                             "low-quality version would no longer depend on the image, the seed and its index alone")
+        for s in ("", "2"):
+            names, probs = getattr(self, "kernel_list" + s), getattr(self, "kernel_prob" + s)
+            if len(names) != len(probs) or not names or min(float(p) for p in probs) < 0 or sum(float(p) for p in probs) <= 0:
+                raise ValueError(f"kernel_list{s} and kernel_prob{s} must have the same, positive length and non-negative weights")
+            for name in names:
+                if name not in KERNEL_TYPES:
+                    raise ValueError(f"kernel type must be one of {KERNEL_TYPES}, got {name!r}")
+            _range("blur_sigma" + s, getattr(self, "blur_sigma" + s), 1e-6)
+            _range("betag_range" + s, getattr(self, "betag_range" + s), 1e-6)
+            _range("betap_range" + s, getattr(self, "betap_range" + s), 1e-6)
+            _prob("sinc_prob" + s, getattr(self, "sinc_prob" + s))
+            _prob("gray_noise_prob" + s, getattr(self, "gray_noise_prob" + s))
+            _prob("gaussian_noise_prob" + s, getattr(self, "gaussian_noise_prob" + s))
+            _range("noise_range" + s, getattr(self, "noise_range" + s), 0.0, 3.0e38)
+            _range("poisson_scale_range" + s, getattr(self, "poisson_scale_range" + s), 0.0, 3.0e38)
+            lo, hi = _range("jpeg_range" + s, getattr(self, "jpeg_range" + s), 0.0, 100.0)
+            if lo <= 0:
+                raise ValueError(f"jpeg_range{s} must lie in (0, 100], got {list(getattr(self, 'jpeg_range' + s))}")
+            rr = getattr(self, "resize_range" + s)
+            _range("resize_range" + s, rr, 1e-6)
+            if float(rr[0]) > 1.0 or float(rr[1]) < 1.0:
+                raise ValueError(f"resize_range{s} must be [a, b] with a <= 1 <= b, got {list(rr)}")
+            rp = getattr(self, "resize_prob" + s)
+            if len(rp) != 3 or min(float(p) for p in rp) < 0 or sum(float(p) for p in rp) <= 0:
+                raise ValueError(f"resize_prob{s} must be three non-negative weights (up, down, keep), got {list(rp)}")
+        _prob("final_sinc_prob", self.final_sinc_prob)
+        _prob("second_blur_prob", self.second_blur_prob)
+        if isinstance(self.stage2_scale, (int, float)):
+            if not self.stage2_scale >= 1e-6:
+                raise ValueError(f"stage2_scale must be positive, got {self.stage2_scale}")
+        else:
+            _range("stage2_scale", self.stage2_scale, 1e-6)
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "RealESRGANConfig":
+        """From the reference's layout: the kernel keys under dataset.val.params or dataset.params, the others under batch_transform.params
+        (at the top level or under dataset), or all keys flat at the top level.  Keys of neither group are ignored."""
+        ds = d.get("dataset", d) if isinstance(d, dict) else {}
+        bt = d.get("batch_transform") or (ds.get("batch_transform") if isinstance(ds, dict) else None) or d
+        node = ds
+        for key in ("val", "params"):
+            if isinstance(node, dict) and isinstance(node.get(key), dict):
+                node = node[key]
+        bt = bt.get("params", bt) if isinstance(bt, dict) else {}
+        kw = {k: node[k] for k in cls.DATASET_KEYS if isinstance(node, dict) and k in node}
+        kw.update({k: bt[k] for k in cls.TRANSFORM_KEYS if k in bt})
+        return cls(**kw)
+
+
+@dataclass
+class Degrade2Params:
+    """What `draw_params2` drew for one image.  Extents are formed from the image's own by `sizes`."""
+    kernel1: np.ndarray                 # fp32 [21, 21]
+    kernel2: Optional[np.ndarray]       # fp32 [21, 21], or None: second_blur_prob decided against the second blur
+    sinc_kernel: Optional[np.ndarray]   # fp32 [21, 21], or None: the pulse (identity), which is not launched
+    scale1: float
+    mode1: str
+    noise1: str                         # "gaussian" | "poisson"
+    level1: float                       # sigma (gaussian, in 1/255) or scale (poisson)
+    gray1: bool
+    quality1: float
+    stage2_scale: float
+    scale2: float
+    mode2: str
+    noise2: str
+    level2: float
+    gray2: bool
+    sinc_first: bool                    # [resize + sinc] then JPEG; otherwise JPEG first
+    back_mode: str
+    quality2: float
+    use_sharpener: bool
+    resize_back: bool
+    kernel_size1: int = 0               # what was decided on the way (for statistics; the chain does not read them)
+    kernel_size2: int = 0
+    sinc1: bool = False
+    sinc2: bool = False
+
+    def sizes(self, h: int, w: int):
+        """((h1, w1), (h2, w2), (hs, ws), (hf, wf)): the extents after the first resize, after the second, of stage 2 (int(h / s2)), and
+        of the result.  Intermediate extents are int(.) as the reference forms them, lowered to even numbers, 2 at the least: the
+        noise stream is drawn four elements at a time."""
+        even = lambda v: max(2, int(v) - int(v) % 2)
+        s1 = (even(h * self.scale1), even(w * self.scale1))
+        ss = (even(h / self.stage2_scale), even(w / self.stage2_scale))
+        s2 = (even(ss[0] * self.scale2), even(ss[1] * self.scale2))
+        final = (int(h), int(w)) if self.resize_back and self.stage2_scale != 1 else ss
+        return s1, s2, ss, final
+
+
+def _quality(lo: float, hi: float, u: float) -> float:
+    q = float(F32(lo + u * (hi - lo)))
+    return float(np.nextafter(F32(100.0), F32(0.0))) if q >= 100.0 else q
+
+
+def _mixed_kernel_fixed(gen: np.random.Generator, kernel_list, kernel_prob, kernel_size, sigma_range, betag_range, betap_range) -> np.ndarray:
+    """`random_mixed_kernel` with a FIXED number of draws (six uniforms: kind, sigma x, sigma y, rotation, beta branch, beta), each
+    made whether or not the kind needs it."""
+    u_kind, u_sx, u_sy, u_th, u_branch, u_beta = (float(v) for v in gen.uniform(size=6))
+    prob = np.cumsum(np.asarray(kernel_prob, dtype=np.float64))
+    kind = kernel_list[min(int(np.searchsorted(prob / prob[-1], u_kind, side="right")), len(kernel_list) - 1)]
+    iso = kind.endswith("iso") and not kind.endswith("aniso")
+    lo, hi = float(sigma_range[0]), float(sigma_range[1])
+    sig_x = lo + u_sx * (hi - lo)
+    sig_y = sig_x if iso else lo + u_sy * (hi - lo)
+    theta = 0.0 if iso else -math.pi + u_th * 2.0 * math.pi
+    if kind in ("iso", "aniso"):
+        return bivariate_gaussian(kernel_size, sig_x, sig_y, theta, iso)
+    blo, bhi = (float(v) for v in (betag_range if kind.startswith("generalized") else betap_range))
+    if u_branch < 0.5 and blo < 1.0:            # (random_mixed_kernels: half of the draws below 1, half above)
+        beta = blo + u_beta * (1.0 - blo)
+    else:
+        beta = max(blo, 1.0) + u_beta * (bhi - max(blo, 1.0))
+    fn = bivariate_generalized_gaussian if kind.startswith("generalized") else bivariate_plateau
+    return fn(kernel_size, sig_x, sig_y, theta, beta, iso)
+
+
+def _pad_kernel(k: np.ndarray) -> np.ndarray:
+    p = (KERNEL_PAD - k.shape[0]) // 2
+    return np.pad(k, ((p, p), (p, p))).astype(F32)
+
+
+def draw_params2(cfg: RealESRGANConfig, seed: int, image_id: int) -> Degrade2Params:
+    """One image's decisions of datasets/detection_cocov2.py:197-253 and :426-532 from ``numpy.random.default_rng([seed, image_id])``.
+    Every draw is made whether or not it is used, in this order (u: uniform(), i(n): integers(n)):
+      stage-1 kernel   i(8) size of KERNEL_RANGE, u sinc?, u omega_c, then the six uniforms of `_mixed_kernel_fixed`
+      stage-2 kernel   the same nine
+      final sinc       u sinc?, i(8) size, u omega_c
+      stage 1          u up / down / keep, u scale, i(3) resize mode, u gaussian?, u sigma or scale, u grey?, u JPEG quality
+      stage 2          u second blur?, u stage2_scale, u up / down / keep, u scale, i(3) mode, u gaussian?, u sigma or scale, u grey?
+      the end          u order, i(3) mode of the resize to the stage-2 extent, u JPEG quality
+    so that no decision shifts another."""
+    seed, image_id = int(seed), int(image_id)
+    if not 0 <= seed < 1 << 64 or not 0 <= image_id < 1 << 32:
+        raise ValueError(f"seed must be in [0, 2^64) and image_id in [0, 2^32), got {seed} and {image_id}")
+    gen = np.random.default_rng([seed, image_id])
+    modes = ("area", "bilinear", "bicubic")
+
+    def blur_kernel(s: str):
+        size = KERNEL_RANGE[int(gen.integers(len(KERNEL_RANGE)))]
+        u_sinc, u_omega = float(gen.uniform()), float(gen.uniform())
+        mixed = _mixed_kernel_fixed(gen, list(getattr(cfg, "kernel_list" + s)), list(getattr(cfg, "kernel_prob" + s)), size,
+                                    getattr(cfg, "blur_sigma" + s), getattr(cfg, "betag_range" + s), getattr(cfg, "betap_range" + s))
+        sinc = u_sinc < float(getattr(cfg, "sinc_prob" + s))
+        if sinc:
+            lo = np.pi / 3 if size < 13 else np.pi / 5
+            mixed = circular_lowpass_kernel(lo + u_omega * (np.pi - lo), size)
+        return _pad_kernel(mixed), size, sinc
+
+    def updown(s: str):
+        u_type, u_scale = float(gen.uniform()), float(gen.uniform())
+        p = np.cumsum(np.asarray(getattr(cfg, "resize_prob" + s), dtype=np.float64))
+        which = min(int(np.searchsorted(p / p[-1], u_type, side="right")), 2)
+        lo, hi = (float(v) for v in getattr(cfg, "resize_range" + s))
+        return (1.0 + u_scale * (hi - 1.0), lo + u_scale * (1.0 - lo), 1.0)[which]
+
+    def noise(s: str):
+        u_type, u_level, u_gray = float(gen.uniform()), float(gen.uniform()), float(gen.uniform())
+        kind = "gaussian" if u_type < float(getattr(cfg, "gaussian_noise_prob" + s)) else "poisson"
+        lo, hi = (float(v) for v in getattr(cfg, ("noise_range" if kind == "gaussian" else "poisson_scale_range") + s))
+        return kind, lo + u_level * (hi - lo), bool(u_gray < float(getattr(cfg, "gray_noise_prob" + s)))
+
+    kernel1, size1, sinc1 = blur_kernel("")
+    kernel2, size2, sinc2 = blur_kernel("2")
+    u_final, i_final, u_omega = float(gen.uniform()), int(gen.integers(len(KERNEL_RANGE))), float(gen.uniform())
+    sinc_kernel = None
+    if u_final < float(cfg.final_sinc_prob):
+        sinc_kernel = circular_lowpass_kernel(np.pi / 3 + u_omega * (np.pi - np.pi / 3), KERNEL_RANGE[i_final], pad_to=KERNEL_PAD).astype(F32)
+    scale1 = updown("")
+    mode1 = modes[int(gen.integers(3))]
+    noise1, level1, gray1 = noise("")
+    quality1 = _quality(float(cfg.jpeg_range[0]), float(cfg.jpeg_range[1]), float(gen.uniform()))
+    u_blur2, u_s2 = float(gen.uniform()), float(gen.uniform())
+    if isinstance(cfg.stage2_scale, (int, float)):
+        s2 = float(cfg.stage2_scale)
+    else:
+        s2 = float(cfg.stage2_scale[0]) + u_s2 * (float(cfg.stage2_scale[1]) - float(cfg.stage2_scale[0]))
+    scale2 = updown("2")
+    mode2 = modes[int(gen.integers(3))]
+    noise2, level2, gray2 = noise("2")
+    u_order, i_back, u_q2 = float(gen.uniform()), int(gen.integers(3)), float(gen.uniform())
+    return Degrade2Params(kernel1=kernel1, kernel2=kernel2 if u_blur2 < float(cfg.second_blur_prob) else None, sinc_kernel=sinc_kernel,
+                          scale1=scale1, mode1=mode1, noise1=noise1, level1=level1, gray1=gray1, quality1=quality1, stage2_scale=s2,
+                          scale2=scale2, mode2=mode2, noise2=noise2, level2=level2, gray2=gray2, sinc_first=bool(u_order < 0.5),
+                          back_mode=modes[i_back], quality2=_quality(float(cfg.jpeg_range2[0]), float(cfg.jpeg_range2[1]), u_q2),
+                          use_sharpener=bool(cfg.use_sharpener), resize_back=bool(cfg.resize_back), kernel_size1=size1, kernel_size2=size2,
+                          sinc1=sinc1, sinc2=sinc2)
+
+
+def _chain2(x, p: Degrade2Params, ops2: dict, noise_args):
+    """The second-order chain on ONE group of images that share every extent and launch-level choice; ``ops2`` maps the step names to
+    the device wrappers or to the numpy restatements, so that both walk the same code.  Returns (lq, gt)."""
+    h, w = x.shape[2:]
+    s1, s2, ss, final = p[0].sizes(h, w)
+    f2d, rs, gn, pn, jp, usm = (ops2[k] for k in ("filter2d", "resize", "gaussian", "poisson", "jpeg", "usm"))
+
+    def blur(x, kernels, what):
+        if KERNEL_PAD // 2 >= min(x.shape[2:]):
+            raise ValueError(f"{what}: a {KERNEL_PAD} x {KERNEL_PAD} kernel needs reflect padding of {KERNEL_PAD // 2}, more than the "
+                             f"{x.shape[2]} x {x.shape[3]} extent of this step allows; the step is not skipped silently — narrow the resize ranges or use larger images")
+        return f2d(x, np.stack(kernels))
+
+    def noise(x, kind, levels, grays, draw):
+        return (gn if kind == "gaussian" else pn)(x, levels, grays, noise_args, draw)
+
+    if p[0].use_sharpener:
+        x = usm(x)
+    gt = x
+    x = blur(x, [q.kernel1 for q in p], "the first blur")
+    x = rs(x, s1, p[0].mode1)
+    x = noise(x, p[0].noise1, [q.level1 for q in p], [q.gray1 for q in p], 0)
+    x = jp(x, [q.quality1 for q in p])
+    if p[0].kernel2 is not None:
+        x = blur(x, [q.kernel2 for q in p], "the second blur")
+    x = rs(x, s2, p[0].mode2)
+    x = noise(x, p[0].noise2, [q.level2 for q in p], [q.gray2 for q in p], 1)
+
+    def back_and_sinc(x):
+        x = rs(x, ss, p[0].back_mode)
+        if p[0].sinc_kernel is not None:
+            x = blur(x, [q.sinc_kernel for q in p], "the final sinc filter")
+        return x
+
+    if p[0].sinc_first:
+        # (the clamp to [0, 1] before the JPEG step, :518: a noise launch with sigma 0, as `degrade_batch` does)
+        x = jp(gn(back_and_sinc(x), [0.0] * len(p), [False] * len(p), noise_args, 0), [q.quality2 for q in p])
+    else:
+        x = back_and_sinc(jp(x, [q.quality2 for q in p]))
+    if final != ss:
+        x = rs(x, final, "bicubic")
+    if (final[0] * final[1]) % 4:
+        raise ValueError(f"the final rounding is a noise launch and needs H * W % 4 == 0, got {final[0]} x {final[1]}")
+    return gn(x, [0.0] * len(p), [False] * len(p), noise_args, 0, True), gt
+
+
+def _group_key2(size, p: Degrade2Params):
+    """what the launches of one `_chain2` call have to share: every extent, the resize modes, the noise types, which steps run"""
+    return (tuple(size), p.sizes(*size), p.mode1, p.mode2, p.back_mode, p.noise1, p.noise2, p.kernel2 is None, p.sinc_kernel is None,
+            p.sinc_first, p.use_sharpener)
+
+
+def degrade2_reference(hq, params: Sequence[Degrade2Params], seed: int, image_ids: Sequence[int], return_gt: bool = False):
+    """The second-order chain in numpy, image by image: ``hq`` a list of fp32 [3, h, w] arrays (or one [B, 3, H, W] batch).  Returns one
+    fp32 [3, h', w'] array per image (and the sharpened inputs with ``return_gt``).  With Gaussian noise the stream values are the host's
+    (`degrade_noise_reference`), which the device meets only to rng's tolerance; with Poisson noise every bit is the device's."""
+    def gn(x, sigma, gray, ids, draw, rounds=False):
+        return add_gaussian_noise_reference(x, sigma, gray, seed, ids, draw, rounds)
+
+    def pn(x, scale, gray, ids, draw):
+        return add_poisson_noise_reference(x, scale, gray, seed, ids, draw)
+
+    ops2 = dict(filter2d=filter2d_reference, resize=resize_reference, gaussian=gn, poisson=pn, jpeg=jpeg_reference, usm=usm_sharpen_reference)
+    lqs, gts = [], []
+    for b, p in enumerate(params):
+        lq, gt = _chain2(np.ascontiguousarray(hq[b], dtype=F32)[None], [p], ops2, [int(image_ids[b])])
+        lqs.append(lq[0])
+        gts.append(gt[0])
+    return (lqs, gts) if return_gt else lqs
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
@@ -592,10 +1173,111 @@ def degrade_batch(hq, params: Sequence[DegradeParams], seed: int, image_ids: Seq
     return [c[0] for c in cur]
 
 
+# ----------------------------------------------------------------------------------------------------------------------------------
+# second order: device side
+# ----------------------------------------------------------------------------------------------------------------------------------
+_POISSON_ON: dict = {}
+
+
+def poisson_tables_on(device):
+    """(uint32-as-int32 [9, 256, 256], int32 [9, 256]) tensors of `poisson_tables` on ``device``: built once, uploaded once per device"""
+    import torch
+    from .imageio import _device_key
+    key = _device_key(device)
+    if key not in _POISSON_ON:
+        T, lo = poisson_tables()
+        _POISSON_ON[key] = (torch.from_numpy(T.view(np.int32)).to(device), torch.from_numpy(lo).to(device))
+    return _POISSON_ON[key]
+
+
+def add_poisson_noise(x, scale, gray, source, draw: int = 0, rounds: bool = False, return_noise: bool = False, return_counts: bool = False):
+    """`add_poisson_noise_reference` on the device with the stream of ``source`` (a `rng.NoiseSource`).  ``scale`` / ``gray``: one value
+    per image (or one for all).  ``return_noise``: also the fp32 noise tensor; ``return_counts``: also the int32 [B, 2] level counts."""
+    import torch
+    from . import ops
+    _check_device_batch(x, "add_poisson_noise")
+    B = x.shape[0]
+    scale = [float(v) for v in np.broadcast_to(np.asarray(scale, dtype=np.float64).reshape(-1), (B,))]
+    gray = [int(bool(v)) for v in np.broadcast_to(np.asarray(gray).reshape(-1), (B,))]
+    tables, lows = poisson_tables_on(x.device)
+    out = torch.empty_like(x)
+    noise = torch.empty_like(x) if return_noise else None
+    levels = torch.empty((B, 16), dtype=torch.int32, device=x.device)
+    counts = torch.empty((B, 2), dtype=torch.int32, device=x.device) if return_counts else None
+    ops.launch(ops.make_degrade_poisson_noise(x=x, out=out, noise_out=noise, scale=scale, gray=gray, tables=tables, lows=lows, levels=levels,
+                                              counts_out=counts, source=source, draw=draw, rounds=rounds))
+    res = (out,) + ((noise,) if return_noise else ()) + ((counts,) if return_counts else ())
+    return res[0] if len(res) == 1 else res
+
+
+def sepblur(x, taps, threshold: Optional[float] = None):
+    """`sepblur_reference` on the device: ``taps`` fp32 [k]; with ``threshold`` also the 0 / 1 mask."""
+    import torch
+    from . import ops
+    _check_device_batch(x, "sepblur")
+    g = torch.as_tensor(np.ascontiguousarray(taps, dtype=F32).reshape(-1)).to(x.device)
+    out = torch.empty_like(x)
+    mask = torch.empty_like(x) if threshold is not None else None
+    ops.launch(ops.make_degrade_sepblur(x=x, taps=g, out=out, mask_out=mask, threshold=0.0 if threshold is None else float(threshold)))
+    return out if threshold is None else (out, mask)
+
+
+def usm_sharpen(x, weight: float = 0.5, threshold: float = 10, radius: int = 50):
+    """`usm_sharpen_reference` on the device, three launches: the blur with its mask, the blur of the mask, the blend."""
+    import torch
+    from . import ops
+    _check_device_batch(x, "usm_sharpen")
+    g = _usm_taps(radius)
+    blur, mask = sepblur(x, g, threshold)
+    soft = sepblur(mask, g)
+    out = torch.empty_like(x)
+    ops.launch(ops.make_degrade_usm_apply(x=x, blur=blur, soft=soft, out=out, weight=float(weight)))
+    return out
+
+
+def degrade_batch2(hq, params: Sequence[Degrade2Params], seed: int, image_ids: Sequence[int], sizes: Optional[Sequence[Tuple[int, int]]] = None,
+                   return_gt: bool = False):
+    """The second-order chain on a batch: ``hq`` fp32 [B, 3, H, W] on the device (image b in the top-left ``sizes[b]`` of its slot), one
+    `Degrade2Params` and one global id per image: USM (when `use_sharpener`) -> blur, resize, noise (draw 0), JPEG -> [blur], resize,
+    noise (draw 1) -> [resize to (int(h / s2), int(w / s2)), sinc] and JPEG in the drawn order -> bicubic resize back (when
+    `resize_back` and s2 != 1) -> clamp(rint(. 255)) / 255.  Returns one fp32 [3, h', w'] tensor per image (and the sharpened inputs,
+    the reference's GT, with ``return_gt``).  Images that share every extent and launch-level choice (`_group_key2`) travel through the
+    launches together; every other parameter travels per image, so an image's result does not depend on its companions.
+
+    Two deviations from the reference, both on extents: its first resize is F.interpolate(scale_factor=), which maps coordinates
+    with 1 / scale instead of in / out (edtr_hip.h explains why only explicit extents are offered); and intermediate extents are
+    lowered to even numbers.  Where an extent is too small for a 21 x 21 kernel's reflect border, the blur is refused (ValueError)."""
+    import torch
+    from .rng import NoiseSource
+    _check_device_batch(hq, "degrade_batch2")
+    B = hq.shape[0]
+    if len(params) != B or len(image_ids) != B:
+        raise ValueError(f"{len(params)} parameter sets and {len(image_ids)} ids for a batch of {B}")
+    sizes = [(int(h), int(w)) for h, w in sizes] if sizes is not None else [tuple(hq.shape[2:])] * B
+    ids = [int(i) for i in image_ids]
+
+    def gn(x, sigma, gray, who, draw, rounds=False):
+        return add_gaussian_noise(x, sigma, gray, NoiseSource(seed, who), draw=draw, rounds=rounds)
+
+    def pn(x, scale, gray, who, draw):
+        return add_poisson_noise(x, scale, gray, NoiseSource(seed, who), draw=draw)
+
+    ops2 = dict(filter2d=filter2d, resize=resize, gaussian=gn, poisson=pn, jpeg=jpeg, usm=usm_sharpen)
+    lqs, gts = [None] * B, [None] * B
+    for idx in _groups([_group_key2(sizes[b], p) for b, p in enumerate(params)]):
+        h, w = sizes[idx[0]]
+        x = torch.cat([hq[i:i + 1, :, :h, :w] for i in idx]).contiguous()
+        lq, gt = _chain2(x, [params[i] for i in idx], ops2, [ids[i] for i in idx])
+        for j, i in enumerate(idx):
+            lqs[i], gts[i] = lq[j], gt[j]
+    return (lqs, gts) if return_gt else lqs
+
+
 def degrade_files(paths: Sequence[str], out_dir: str, cfg, seed: int, batch_size: int = 1, workers: int = 0, device=None) -> List[Tuple[str, str]]:
-    """Decode every file of ``paths`` (Pillow, RGB), degrade it with `draw_params(cfg, seed, k)` for its index k in ``paths`` and write
-    ``out_dir``/gt/<stem>.png (the decoded image) and ``out_dir``/lq/<stem>.png.  Files are grouped by extent (`imageio.plan_buckets`)
-    and cross the 8-bit boundary through `imageio.ingest` / `imageio.emit`; ``workers`` threads decode and encode.  The low-quality
+    """Decode every file of ``paths`` (Pillow, RGB), degrade it with `draw_params(cfg, seed, k)` (`draw_params2` for a `RealESRGANConfig`)
+    for its index k in ``paths`` and write ``out_dir``/gt/<stem>.png (the decoded image; the sharpened one where the configuration
+    sharpens) and ``out_dir``/lq/<stem>.png.  Files are grouped by extent (`imageio.plan_buckets`)
+    and cross the 8-bit boundary through `imageio.ingest` / `imageio.emit`; ``workers`` threads decode and encode.
     Returns [(gt path, lq path), ...]."""
     import torch
     from concurrent.futures import ThreadPoolExecutor
@@ -630,10 +1312,14 @@ def degrade_files(paths: Sequence[str], out_dir: str, cfg, seed: int, batch_size
         for _, idx in plan:
             raws = list(pool.map(decode, [paths[k] for k in idx]))
             batch, sizes = imageio.ingest(raws, device=device)
-            params = [draw_params(cfg, seed, k) for k in idx]
-            lqs = degrade_batch(batch, params, seed, idx, sizes)
-            for k, raw, lq in zip(idx, raws, lqs):
+            if isinstance(cfg, RealESRGANConfig):
+                lqs, gts = degrade_batch2(batch, [draw_params2(cfg, seed, k) for k in idx], seed, idx, sizes, return_gt=True)
+            else:
+                lqs, gts = degrade_batch(batch, [draw_params(cfg, seed, k) for k in idx], seed, idx, sizes), None
+            for j, (k, raw, lq) in enumerate(zip(idx, raws, lqs)):
                 out = imageio.emit(lq[None].contiguous(), [tuple(lq.shape[1:])])[0].cpu().numpy()
+                if gts is not None and cfg.use_sharpener:       # the reference's GT is the sharpened image
+                    raw = imageio.emit(gts[j][None].contiguous(), [tuple(gts[j].shape[1:])])[0].cpu().numpy()
                 jobs.append(pool.submit(encode, raw, names[k][0]))
                 jobs.append(pool.submit(encode, out, names[k][1]))
         for j in jobs:
@@ -647,7 +1333,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m edtr_amd.degrade", description="Write gt/ and lq/ versions of a folder of images.")
     ap.add_argument("--input", required=True, help="folder of png / jpg images")
     ap.add_argument("--output", required=True, help="folder that receives gt/<stem>.png and lq/<stem>.png")
-    ap.add_argument("--config", required=True, help=f"a YAML file with the reference's degradation keys, or one of {sorted(PRESETS)}")
+    ap.add_argument("--config", required=True, help=f"a YAML file with the reference's degradation keys, or one of {sorted(PRESETS) + ['realesrgan']}")
     ap.add_argument("--seed", type=int, required=True)
     ap.add_argument("--batch-size", type=int, default=1)
     ap.add_argument("--workers", type=int, default=0)

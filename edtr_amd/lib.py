@@ -28,6 +28,7 @@ DECLARED_SYMBOLS = [
     "edtr_image_resize_h_batch", "edtr_image_resize_ingest_batch", "edtr_image_emit_batch",
     "edtr_tile_gather", "edtr_tile_blend",
     "edtr_degrade_filter2d", "edtr_degrade_resize", "edtr_degrade_gaussian_noise", "edtr_degrade_jpeg",
+    "edtr_degrade_poisson_noise", "edtr_degrade_sepblur", "edtr_degrade_usm_apply",
 ]
 
 
@@ -285,6 +286,10 @@ def load() -> C.CDLL:
     lib.edtr_degrade_resize.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.edtr_degrade_gaussian_noise.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.POINTER(f32), vp, C.POINTER(i32), vp, u64, vp, i64, i64, i32, vp]
     lib.edtr_degrade_jpeg.argtypes = [vp, vp, i32, i32, i32, i32, C.POINTER(f32), vp, vp, vp, vp]
+    # second order: ..., scale_host, scale, gray_host, gray, tables, lows, levels, counts_out, seed, image_ids, image_id_base, draw, rounds
+    lib.edtr_degrade_poisson_noise.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.POINTER(f32), vp, C.POINTER(i32), vp, vp, vp, vp, vp, u64, vp, i64, i64, i32, vp]
+    lib.edtr_degrade_sepblur.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, i32, f32, vp]
+    lib.edtr_degrade_usm_apply.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]
     if lib.edtr_abi_version() != 10:
         raise RuntimeError("libedtr_hip.so ABI version mismatch")
     _lib = lib

@@ -813,6 +813,38 @@ def make_degrade_jpeg(*, x, out, quality, factor, dct, coefs=None, name="degrade
     return Rec(L.load().edtr_degrade_jpeg, args, (x, out, q_host, factor, dct, coefs), name, 4.0 * B * mcus * 6 * 4096, 8.0 * x.numel())
 
 
+def make_degrade_poisson_noise(*, x, out, noise_out, scale, gray, tables, lows, levels, counts_out, source, draw: int, rounds: bool,
+                               name="degrade.poisson_noise") -> Rec:
+    """``out`` = clamp(``x`` + noise * scale[b]) with the Poisson noise of edtr_hip.h drawn from ``source``'s stream; ``scale`` / ``gray``:
+    one Python value per image; ``tables`` uint32 [9, 256, 256] / ``lows`` int32 [9, 256]: `degrade.poisson_tables_on(device)`;
+    ``levels``: int32 [B, 16] workspace; ``counts_out``: None or int32 [B, 2]; ``noise_out``: None or a tensor that receives the noise."""
+    B, ch, H, W = x.shape
+    sc_host, gray_host = (ct.c_float * B)(*scale), (ct.c_int32 * B)(*gray)
+    sc = torch.tensor(list(sc_host), dtype=torch.float32).to(x.device)
+    gry = torch.tensor(list(gray_host), dtype=torch.int32).to(x.device)
+    seed, ids_p, base, ids = _noise_args(source, B, x.device, name)
+    args = (ptr(x), ptr(out), ptr(noise_out), B, ch, H, W, sc_host, ptr(sc), gray_host, ptr(gry), ptr(tables), ptr(lows), ptr(levels),
+            ptr(counts_out), seed, ids_p, base, int(draw), int(rounds))
+    keep = (x, out, noise_out, sc_host, sc, gray_host, gry, tables, lows, levels, counts_out, ids)
+    return Rec(L.load().edtr_degrade_poisson_noise, args, keep, name, 0.0, 24.0 * x.numel())
+
+
+def make_degrade_sepblur(*, x, taps, out, mask_out=None, threshold: float = 0.0, name="degrade.sepblur") -> Rec:
+    """fp32 ``x`` [B, 3, H, W] blurred with the fp32 tap vector ``taps`` [k] along rows, then columns (reflect borders) -> ``out``;
+    ``mask_out``: None or a tensor that receives |x - out| * 255 > ``threshold`` as 0 / 1."""
+    B, ch, H, W = x.shape
+    k = taps.numel()
+    args = (ptr(x), ptr(out), ptr(mask_out), B, ch, H, W, ptr(taps), k, float(threshold))
+    return Rec(L.load().edtr_degrade_sepblur, args, (x, taps, out, mask_out), name, 4.0 * x.numel() * k, 8.0 * x.numel())
+
+
+def make_degrade_usm_apply(*, x, blur, soft, out, weight: float, name="degrade.usm_apply") -> Rec:
+    """``out`` = soft * clamp(x + weight (x - blur), 0, 1) + (1 - soft) * x, all fp32 [B, 3, H, W]."""
+    B, ch, H, W = x.shape
+    args = (ptr(x), ptr(blur), ptr(soft), ptr(out), B, ch, H, W, float(weight))
+    return Rec(L.load().edtr_degrade_usm_apply, args, (x, blur, soft, out), name, 0.0, 16.0 * x.numel())
+
+
 def make_cast16(*, dtype, src: torch.Tensor, rows: int, C: int, dst: torch.Tensor, name="cast16") -> Rec:
     args = (dt_code(dtype), ptr(src), rows, C, src.stride(0), ptr(dst), dst.stride(0))
     return Rec(L.load().edtr_cast16, args, (src, dst), name, 0.0, 6.0 * rows * C)

@@ -25,6 +25,9 @@ PURPOSES = (PURPOSE_Q_SAMPLE, PURPOSE_STEP, PURPOSE_X_T, PURPOSE_VAE)
 # edtr_normal_fill and `normal_reference` keep refusing them, `stream_reference` evaluates them
 PURPOSE_DEGRADE, PURPOSE_DEGRADE_GRAY = 4, 5
 DEGRADE_PURPOSES = (PURPOSE_DEGRADE, PURPOSE_DEGRADE_GRAY)
+# colour / grey noise of edtr_degrade_poisson_noise: the raw words of the same counters (`uniform_words_reference`), never normals
+PURPOSE_DEGRADE_POISSON, PURPOSE_DEGRADE_POISSON_GRAY = 6, 7
+POISSON_PURPOSES = (PURPOSE_DEGRADE_POISSON, PURPOSE_DEGRADE_POISSON_GRAY)
 Z_MAX = float(np.sqrt(48.0 * np.log(2.0)))      # u1 >= 2^-24: no value of the stream is larger in magnitude
 
 _M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
@@ -72,11 +75,17 @@ def normal_reference(seed: int, image_ids, purpose: int, draw, per_image: int) -
     return stream_reference(seed, image_ids, purpose, draw, per_image)
 
 
-def stream_reference(seed: int, image_ids, purpose: int, draw, per_image: int) -> np.ndarray:
-    """`normal_reference` for every purpose of the header, the two of the degradation stage (`DEGRADE_PURPOSES`) included."""
+def uniform_words_reference(seed: int, image_ids, purpose: int, draw, per_image: int) -> np.ndarray:
+    """uint32 [B][per_image]: the raw Philox words of the stream, element e of an image receiving word e & 3 of the call on the counter
+    (e >> 2, draw, purpose, image id) — what edtr_degrade_poisson_noise inverts its tables with.  Every purpose of the header."""
+    if purpose not in PURPOSES + DEGRADE_PURPOSES + POISSON_PURPOSES:
+        raise ValueError(f"purpose must be one of {PURPOSES + DEGRADE_PURPOSES + POISSON_PURPOSES}, got {purpose}")
+    return _words(seed, image_ids, purpose, draw, per_image).reshape(-1, per_image)
+
+
+def _words(seed: int, image_ids, purpose: int, draw, per_image: int) -> np.ndarray:
+    """uint32 [B][per_image / 4][4]: one Philox call per group of four elements"""
     seed, ids = _check_seed(seed), _check_ids(image_ids)
-    if purpose not in PURPOSES + DEGRADE_PURPOSES:
-        raise ValueError(f"purpose must be one of {PURPOSES + DEGRADE_PURPOSES}, got {purpose}")
     if per_image <= 0 or per_image % 4:
         raise ValueError(f"per_image must be a positive multiple of 4, got {per_image}")
     B, G = len(ids), per_image // 4
@@ -88,7 +97,16 @@ def stream_reference(seed: int, image_ids, purpose: int, draw, per_image: int) -
     ctr[..., 1] = draws.astype(np.uint32)[:, None]
     ctr[..., 2] = purpose
     ctr[..., 3] = np.asarray(ids, dtype=np.uint32).reshape(B, 1)
-    x = philox4x32_10(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint32))
+    return philox4x32_10(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint32))
+
+
+def stream_reference(seed: int, image_ids, purpose: int, draw, per_image: int) -> np.ndarray:
+    """`normal_reference` for every purpose of the header that draws normals, the two of the degradation stage (`DEGRADE_PURPOSES`)
+    included."""
+    if purpose not in PURPOSES + DEGRADE_PURPOSES:
+        raise ValueError(f"purpose must be one of {PURPOSES + DEGRADE_PURPOSES}, got {purpose}")
+    x = _words(seed, image_ids, purpose, draw, per_image)
+    B, G = x.shape[:2]
     out = np.empty((B, G, 4), dtype=np.float64)
     for j in (0, 2):
         u1 = ((x[..., j] >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24

@@ -809,7 +809,9 @@ int edtr_image_sqdiff(const float* a, const float* b, int B, int channels, int H
  * given, and edtr_amd/degrade.py repeats every kernel in numpy.  Common errors (nothing is launched): a NULL tensor EDTR_E_NULL; B
  * <= 0 or > 65535 or a non-positive extent EDTR_E_SHAPE; an extent above 2^24 EDTR_E_UNSUPPORTED; a tensor that is not 4-byte
  * aligned EDTR_E_ALIGN.  Per-image parameters come twice, as the image descriptors do: a HOST array that is checked here and a
- * DEVICE array with the same values that the kernel reads.  Poisson noise, the sinc filter and USM sharpening are not provided. */
+ * DEVICE array with the same values that the kernel reads.  Poisson noise and USM sharpening are the entries of "second order" below;
+ * the sinc filter is an ordinary edtr_degrade_filter2d launch whose taps the host builds (edtr_amd/degrade.py,
+ * circular_lowpass_kernel).  Not provided: the training pair pool (queue_size > 0), which mixes images across batches. */
 /* out[b][c][y][x] = sum over (ky, kx), ky major, of fmul(x[b][c][R(y + ky - k/2)][R(x + kx - k/2)], kernels[b][ky][kx]), accumulated
  * with fadd from 0.0f: a correlation (no flip, as F.conv2d) over F.pad(mode="reflect") borders, R(i) = -i below 0 and 2 (n - 1) - i
  * from n on (the edge sample is not repeated).  kernels: fp32 [n_kernels][k][k] on the device, n_kernels == B, or 1 = one kernel for
@@ -865,6 +867,51 @@ int edtr_degrade_gaussian_noise(const float* x, float* out, float* noise_out, in
  * Hp/16 Wp/16 Cb blocks, then Cr (Hp, Wp the padded extents).  out may alias x.  replaces: DiffJPEG.forward, datasets/diffjpeg.py:450-492. */
 int edtr_degrade_jpeg(const float* x, float* out, int B, int channels, int H, int W, const float* quality_host, const float* factor,
                       const float* dct, float* coefs, edtr_stream_t stream);
+
+/* ---- Low-quality inputs, second order: Poisson noise and USM sharpening (additive to ABI 10) -----------------------------------------
+ * What RealESRGANBatchTransform.__call__ (datasets/detection_cocov2.py:413-539) needs beyond the four launches above.  The same rule:
+ * fmul / fadd / fdiv in the order given or integer arithmetic, restated in numpy by edtr_amd/degrade.py, the same common errors. */
+/* Poisson noise by table inversion on the stream of "Reproducible noise".  Per image b, per element e:
+ *   level  k = (int)clamp(rint(fmul(v, 255)), 0, 255), q = fdiv((float)k, 255); colour noise (gray[b] == 0): v = x[e], e = (c H + y) W + x
+ *          of the [3][H][W] image; grey noise (gray[b] == 1): v = fadd(fadd(fmul(0.2989f, r), fmul(0.587f, g)), fmul(0.114f, b)) of
+ *          the pixel (torchvision's rgb_to_grayscale), e = y W + x of the [H][W] plane, one value for the three channels
+ *   count  = the number of distinct k over the image's [3][H][W] (colour) or over its grey plane (grey); vals = 2^ceil(log2(count)),
+ *          formed in integers: one of 1, 2, ..., 256.  A first launch marks the levels in a presence bitmap per image (LDS atomics in
+ *          a workgroup, vector atomic ORs into `levels`: int32 [B][16], words 0..7 colour, 8..15 grey; zeroed by this entry), the
+ *          noise kernel popcounts it.  Nothing is read back.  counts_out (optional, int32 [B][2]) receives (colour count, grey count).
+ *   u      = word x[e & 3] of Philox on the counter (e >> 2, draw, purpose, image id), purpose EDTR_NOISE_DEGRADE_POISSON (colour)
+ *          or EDTR_NOISE_DEGRADE_POISSON_GRAY (grey); key, ids and draw as for edtr_degrade_gaussian_noise
+ *   n      = lows[t][k] + #{ j < 255 : tables[t][k][j] <= u }, t = log2(vals), by an 8-step binary search of the non-decreasing row
+ *   noise  = fadd(fdiv((float)n, (float)vals), -q);   out = clamp(fadd(x, fmul(noise, scale[b])), 0, 1), or with rounds = 1
+ *          fdiv(clamp(rint(fmul(that sum, 255)), 0, 255), 255)
+ * tables: uint32 [9][256][256] and lows: int32 [9][256] on the device, built by the caller in fp64 with + * / alone (so that every
+ * host builds the same bits): for vals = 2^t and level k, lambda = (double)fmul(fdiv((float)k, 255), (float)vals); lo = max(0,
+ * ceil(lambda) - 128); weights w[floor lambda] = 1, w[j] = (w[j - 1] lambda) / j upwards and w[j] = (w[j + 1] (j + 1)) / lambda
+ * downwards; total = the sum of w[0 .. lo + 256] in index order; cdf_j = (the sum of w[0 .. lo + j] in index order) / total;
+ * tables[t][k][j] = min(2^32 - 1, floor(cdf_j 2^32)).  A lambda = 0 row is all 0xffffffff.  The mass outside the 257-wide window is
+ * below 1e-13, under the 2^-32 quantum.  scale (fp32 [B], finite and >= 0, EDTR_E_SHAPE) and gray (0 or 1, EDTR_E_DTYPE) come as host
+ * and device arrays; H W % 4 != 0 or x / out / noise_out not 16-byte aligned EDTR_E_ALIGN; draw outside [0, 2^32) EDTR_E_SHAPE; rounds
+ * outside {0, 1} EDTR_E_DTYPE.  noise_out (optional, fp32 [B][3][H][W]) receives `noise`.  out must not alias x (EDTR_E_UNSUPPORTED):
+ * a grey lane reads all three channels.  replaces: add_poisson_noise_pt with torch.poisson, datasets/degradation.py:610-680. */
+#define EDTR_NOISE_DEGRADE_POISSON 6        /* colour noise of edtr_degrade_poisson_noise (draw = stage) */
+#define EDTR_NOISE_DEGRADE_POISSON_GRAY 7   /* grey noise of edtr_degrade_poisson_noise (draw = stage) */
+int edtr_degrade_poisson_noise(const float* x, float* out, float* noise_out, int B, int channels, int H, int W, const float* scale_host,
+                               const float* scale, const int32_t* gray_host, const int32_t* gray, const uint32_t* tables,
+                               const int32_t* lows, int32_t* levels, int32_t* counts_out, uint64_t seed, const int64_t* image_ids,
+                               int64_t image_id_base, int64_t draw, int rounds, edtr_stream_t stream);
+/* Separable correlation over F.pad(mode="reflect") borders with one tap vector for rows and columns (fp32 [k] on the device):
+ *   t[y'][x] = sum over kx of fmul(x[R(y')][R(x + kx - k/2)], taps[kx]), added with fadd from 0.0f in tap order, for every padded row y';
+ *   out[y][x] = sum over ky of fmul(t[y + ky - k/2][x], taps[ky]), added the same way.
+ * k odd, 3 <= k <= 63, k / 2 < min(H, W) (EDTR_E_SHAPE otherwise).  One launch: the 32 x 32 tile's patch with its halo and the rows-pass
+ * intermediate live in LDS.  mask_out (optional, fp32 [B][3][H][W]) receives fmul(fabs(fadd(x, -out)), 255) > threshold ? 1 : 0.
+ * Neither output may alias x or the other.  replaces: the two filter2D calls of USMSharp.forward, datasets/utils.py:110-116, whose
+ * kernel is the outer product g g^T. */
+int edtr_degrade_sepblur(const float* x, float* out, float* mask_out, int B, int channels, int H, int W, const float* taps, int k,
+                         float threshold, edtr_stream_t stream);
+/* sharp = clamp(fadd(x, fmul(weight, fadd(x, -blur))), 0, 1);  out = fadd(fmul(soft, sharp), fmul(fadd(1, -soft), x)).  All four fp32
+ * [B][3][H][W]; out may alias any input.  weight finite (EDTR_E_SHAPE).  replaces: USMSharp.forward, datasets/utils.py:117-119. */
+int edtr_degrade_usm_apply(const float* x, const float* blur, const float* soft, float* out, int B, int channels, int H, int W,
+                           float weight, edtr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * hipGraph capture of a launch sequence issued on `stream` (one denoise step, or a whole batch).

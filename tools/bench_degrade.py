@@ -1,4 +1,4 @@
-"""Time the degradation stage (edtr_amd/degrade.py) on the device: each of the four launches and the whole chain at batch 8 of
+"""Time the degradation stage (edtr_amd/degrade.py) on the device: each of the launches and the whole chains at batch 8 of
 512 x 512 with 41 x 41 blur kernels, next to the same operations as the reference performs them — torch on the host CPU
 (F.pad + grouped F.conv2d as filter2D, F.interpolate, randn-based noise, DiffJPEG's tensordot formulation) — in the same call.
 Writes profiles/degrade_timing.json; commit that file only after this has run on the device.
@@ -20,7 +20,7 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from edtr_amd import degrade  # noqa: E402
+from edtr_amd import degrade, ops  # noqa: E402
 from edtr_amd.build import source_hash  # noqa: E402
 from edtr_amd.rng import NoiseSource  # noqa: E402
 
@@ -118,6 +118,27 @@ def main() -> int:
         "jpeg_full_size": gpu_ms(lambda: degrade.jpeg(d_hq, quality), args.iters),
         "chain": gpu_ms(chain, args.iters),
     }
+    # the second-order chain (degrade.degrade_batch2): its three new launches, the separable blur beside the 2-D launch with the same
+    # (outer-product) kernel at k = 41 — 82 taps against 1681 — and the whole chain with the parameters of the "realesrgan" preset
+    g41 = degrade.gaussian_taps(41).astype(np.float32)
+    d_outer = torch.from_numpy(np.outer(g41, g41).astype(np.float32)[None]).cuda()
+    g51 = degrade.gaussian_taps(51).astype(np.float32)
+    d_blur = degrade.sepblur(d_hq, g51)
+    d_soft = degrade.sepblur(d_blur, g51)
+    scale = gen.uniform(0.05, 3.0, B).astype(np.float32)
+    cfg2 = degrade.load_config("realesrgan")
+    params2 = [degrade.draw_params2(cfg2, 0, i) for i in range(B)]
+    degrade.poisson_tables_on(d_hq.device)
+    gpu2 = {
+        "poisson_noise_full_size": gpu_ms(lambda: degrade.add_poisson_noise(d_hq, scale, gray, src), args.iters),
+        "poisson_noise_grey_full_size": gpu_ms(lambda: degrade.add_poisson_noise(d_hq, scale, [1] * B, src), args.iters),
+        "sepblur_k51_with_mask": gpu_ms(lambda: degrade.sepblur(d_hq, g51, 10.0), args.iters),
+        "usm_apply": gpu_ms(lambda: ops.launch(ops.make_degrade_usm_apply(x=d_hq, blur=d_blur, soft=d_soft, out=d_soft, weight=0.5)), args.iters),
+        "usm_sharpen": gpu_ms(lambda: degrade.usm_sharpen(d_hq), args.iters),
+        "sepblur_k41": gpu_ms(lambda: degrade.sepblur(d_hq, g41), args.iters),
+        "filter2d_k41_outer_product": gpu_ms(lambda: degrade.filter2d(d_hq, d_outer), args.iters),
+        "chain2_realesrgan_preset": gpu_ms(lambda: degrade.degrade_batch2(d_hq, params2, 0, range(B)), args.iters),
+    }
     cpu = {
         "filter2d": cpu_ms(lambda: cpu_filter2d(hq, kern), args.cpu_iters),
         "resize_down_bilinear": cpu_ms(lambda: F.interpolate(hq, size=(lq, lq), mode="bilinear"), args.cpu_iters),
@@ -130,7 +151,7 @@ def main() -> int:
     }
     out = {"batch": B, "size": S, "kernel": K, "lq_size": lq, "device": torch.cuda.get_device_name(0), "source_hash": source_hash(),
            "cpu_threads": args.cpu_threads, "unit": "ms per call (the GPU figures include the wrappers' allocations and uploads)",
-           "gpu_ms": gpu, "host_cpu_torch_ms": cpu, "speedup": {k: cpu[k] / gpu[k] for k in gpu}}
+           "gpu_ms": gpu, "second_order_gpu_ms": gpu2, "host_cpu_torch_ms": cpu, "speedup": {k: cpu[k] / gpu[k] for k in gpu}}
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
     path = os.path.join(ROOT, "profiles", "degrade_timing.json")
     with open(path, "w") as fh:

@@ -1,6 +1,6 @@
 """Make the read-only reference tree at /root/reference importable on CPU in THIS container.
 
-Only used by tools/make_goldens.py and tools/make_degrade_goldens.py (fixture generation) — never by tests, bench or the
+Only used by tools/make_goldens.py, tools/make_degrade_goldens.py and tools/make_degrade2_goldens.py (fixture generation) — never by tests, bench or the
 product.  The reference needs four packages the image lacks (torchvision, omegaconf, ftfy,
 timm); none of them is touched by the restoration hot path, so inert
 stand-in modules are registered before the import.
@@ -68,6 +68,30 @@ def install_degrade_stubs() -> None:
     install_stubs()
     if "torchvision.transforms._functional_tensor" not in sys.modules:
         _module("torchvision.transforms._functional_tensor", rgb_to_grayscale=lambda x, *a, **k: x)
+
+
+def install_degrade2_stubs() -> None:
+    """`install_degrade_stubs`, with the two stand-ins that tools/make_degrade2_goldens.py DOES call filled in by their published
+    formulas: cv2.getGaussianKernel(k, sigma) for a non-positive sigma and k > 7 (sigma = 0.3 ((k - 1) 0.5 - 1) + 0.8, fp64, [k, 1]),
+    and torchvision's rgb_to_grayscale ((0.2989 r + 0.587 g) + 0.114 b on the channel axis)."""
+    import numpy as np
+    install_degrade_stubs()
+
+    def get_gaussian_kernel(ksize, sigma):
+        assert ksize > 7 and ksize % 2 == 1, "only the formula branch of cv2.getGaussianKernel is stood in for"
+        if sigma <= 0:
+            sigma = 0.3 * ((ksize - 1) * 0.5 - 1) + 0.8
+        i = np.arange(ksize, dtype=np.float64) - (ksize - 1) * 0.5
+        g = np.exp(-(i * i) / (2.0 * sigma * sigma))
+        return (g / g.sum()).reshape(ksize, 1)
+
+    def rgb_to_grayscale(img, num_output_channels=1):
+        r, g, b = img.unbind(dim=-3)
+        gray = (0.2989 * r + 0.587 * g + 0.114 * b).to(img.dtype).unsqueeze(dim=-3)
+        return gray.expand(img.shape) if num_output_channels == 3 else gray
+
+    sys.modules["cv2"].getGaussianKernel = get_gaussian_kernel
+    sys.modules["torchvision.transforms._functional_tensor"].rgb_to_grayscale = rgb_to_grayscale
 
 
 def import_reference_file(name: str, relpath: str):
