@@ -8,7 +8,8 @@ inputs, second order".  All on the fp32 NCHW batches that `imageio.ingest` write
     python -m edtr_amd.degrade --input DIR --output DIR --config YAML|codeformer|realesrgan-stage1|realesrgan --seed N [--batch-size N --workers N]
 
 writes ``gt/<stem>.png`` and ``lq/<stem>.png`` under the output folder, as the reference's generators do (``gt/`` is the sharpened
-image where the configuration sharpens, as the reference's GT is).
+image where the configuration sharpens, as the reference's GT is).  ``--geometry YAML [--masks DIR]`` first applies the resize, pad,
+crop and flip of the reference's segmentation data sets to image and mask together (edtr_amd/labels.py) and adds ``mask/<stem>.png``.
 
 Three layers:
   * `filter2d`, `resize`, `add_gaussian_noise`, `jpeg`, `add_poisson_noise`, `sepblur`, `usm_sharpen`: thin wrappers over the launches
@@ -1273,12 +1274,19 @@ def degrade_batch2(hq, params: Sequence[Degrade2Params], seed: int, image_ids: S
     return (lqs, gts) if return_gt else lqs
 
 
-def degrade_files(paths: Sequence[str], out_dir: str, cfg, seed: int, batch_size: int = 1, workers: int = 0, device=None) -> List[Tuple[str, str]]:
+def degrade_files(paths: Sequence[str], out_dir: str, cfg, seed: int, batch_size: int = 1, workers: int = 0, device=None,
+                  geometry=None, masks: Optional[str] = None) -> List[Tuple[str, str]]:
     """Decode every file of ``paths`` (Pillow, RGB), degrade it with `draw_params(cfg, seed, k)` (`draw_params2` for a `RealESRGANConfig`)
     for its index k in ``paths`` and write ``out_dir``/gt/<stem>.png (the decoded image; the sharpened one where the configuration
     sharpens) and ``out_dir``/lq/<stem>.png.  Files are grouped by extent (`imageio.plan_buckets`)
     and cross the 8-bit boundary through `imageio.ingest` / `imageio.emit`; ``workers`` threads decode and encode.
-    Returns [(gt path, lq path), ...]."""
+    Returns [(gt path, lq path), ...].
+
+    ``geometry`` (a `labels.SegGeometry`, a mapping or a YAML path with its keys): every decoded file first goes through the resize,
+    pad, crop and flip of the reference's segmentation data sets (`labels.draw_geometry(geometry, seed, k, (h, w))` ->
+    `labels.prepare_pair`), and gt/ holds the prepared image.  ``masks`` (a folder with <stem>.png label maps, read as
+    np.array(Image.open(...)): palette indices, as the reference reads them): the mask goes through the same geometry and is written
+    to ``out_dir``/mask/<stem>.png as mode "L".  Image ids and the degradation's draws are the same with and without either."""
     import torch
     from concurrent.futures import ThreadPoolExecutor
     from . import imageio
@@ -1288,10 +1296,13 @@ def degrade_files(paths: Sequence[str], out_dir: str, cfg, seed: int, batch_size
     if int(batch_size) <= 0 or int(workers) < 0:
         raise ValueError(f"batch_size must be positive and workers non-negative, got {batch_size} and {workers}")
     paths = list(paths)
-    for sub in ("gt", "lq"):
+    for sub in ("gt", "lq") + (("mask",) if masks is not None else ()):
         os.makedirs(os.path.join(out_dir, sub), exist_ok=True)
     stems = [os.path.splitext(os.path.basename(p))[0] for p in paths]
     names = [(os.path.join(out_dir, "gt", s + ".png"), os.path.join(out_dir, "lq", s + ".png")) for s in stems]
+    if geometry is not None or masks is not None:
+        from . import labels
+        geometry = None if geometry is None else labels.load_geometry(geometry)
 
     def header(path):
         with Image.open(path) as im:
@@ -1301,17 +1312,36 @@ def degrade_files(paths: Sequence[str], out_dir: str, cfg, seed: int, batch_size
         with Image.open(path) as im:
             return np.array(im.convert("RGB"), dtype=np.uint8)
 
+    def decode_mask(stem):
+        with Image.open(os.path.join(masks, stem + ".png")) as im:
+            m = np.array(im)
+        if m.dtype != np.uint8 or m.ndim != 2:
+            raise ValueError(f"the mask of {stem} is not a uint8 label map (mode 'P' or 'L'), got {m.dtype} {m.shape}")
+        return m
+
     def encode(arr, name):
         Image.fromarray(arr).save(name)
 
     pool = ThreadPoolExecutor(max_workers=max(1, min(int(workers), MAX_WORKERS)))
     try:
         wh = list(pool.map(header, paths))
-        plan = imageio.plan_buckets([(h, w) for w, h in wh], int(batch_size))
+        geoms = None if geometry is None else [labels.draw_geometry(geometry, seed, k, (h, w)) for k, (w, h) in enumerate(wh)]
+        plan = imageio.plan_buckets([(h, w) for w, h in wh] if geoms is None else [g.out_hw for g in geoms], int(batch_size))
         jobs = []
         for _, idx in plan:
             raws = list(pool.map(decode, [paths[k] for k in idx]))
-            batch, sizes = imageio.ingest(raws, device=device)
+            if masks is not None:
+                for k, m in zip(idx, pool.map(decode_mask, [stems[k] for k in idx])):
+                    if geoms is not None:
+                        m = labels.prepare_mask(m, geoms[k], device=device).cpu().numpy()
+                    jobs.append(pool.submit(encode, m, os.path.join(out_dir, "mask", stems[k] + ".png")))
+            if geoms is not None:
+                # the prepared images stay on the device for the degradation; the host copies are what gt/ is written from
+                prepared = [labels.prepare_image(raw, geoms[k], device=device) for k, raw in zip(idx, raws)]
+                batch, sizes = imageio.ingest(prepared, device=device)
+                raws = [p.cpu().numpy() for p in prepared]
+            else:
+                batch, sizes = imageio.ingest(raws, device=device)
             if isinstance(cfg, RealESRGANConfig):
                 lqs, gts = degrade_batch2(batch, [draw_params2(cfg, seed, k) for k in idx], seed, idx, sizes, return_gt=True)
             else:
@@ -1337,6 +1367,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--seed", type=int, required=True)
     ap.add_argument("--batch-size", type=int, default=1)
     ap.add_argument("--workers", type=int, default=0)
+    ap.add_argument("--geometry", default=None, help="a YAML file with the reference's segmentation geometry keys (gt_size, resize_range, "
+                    "out_size, crop_type, hflip): resize, pad, crop and flip every image before it is degraded")
+    ap.add_argument("--masks", default=None, help="folder of <stem>.png label maps: each goes through the same geometry into mask/<stem>.png")
     return ap
 
 
@@ -1347,7 +1380,7 @@ def main(argv=None) -> int:
     if not paths:
         print(f"no images in {args.input}", file=sys.stderr)
         return 1
-    written = degrade_files(paths, args.output, args.config, args.seed, args.batch_size, args.workers)
+    written = degrade_files(paths, args.output, args.config, args.seed, args.batch_size, args.workers, geometry=args.geometry, masks=args.masks)
     print(f"wrote {len(written)} gt / lq pairs to {args.output}")
     return 0
 

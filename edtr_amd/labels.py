@@ -1,0 +1,486 @@
+"""Segmentation labels on the device: what sits between the restored image and the figure the reference's segmentation test reports
+(main/seg/test_edtr.py:139-174), and the geometry its data sets apply to image and mask together (datasets/segmentation.py:82-114,
+207-215).  A label map is uint8 [H, W] (255 = "ignore"), an image uint8 [h, w, 3]; the four launches are include/edtr_hip.h "Label
+maps" (kernels in csrc/labels.hip).  The task networks stay outside: `evaluate` takes logits from any callable.
+
+Three layers, as in `degrade`:
+  * `resize_nearest`, `window`, `confusion`, `colorize`: thin wrappers over the launches (torch tensors on the device, the caller's
+    stream).  With inputs already on the device nothing waits for the device; a numpy input is uploaded first (one host -> device
+    copy), and `confusion`'s ``sizes`` travel in a pinned, non-blocking upload;
+  * `*_reference`: the numpy restatement of each.  They are the NORMATIVE definition: the kernels are tested against them by
+    equality, and they against Pillow and the reference's own functions (tests/golden/labels.npz);
+  * host-side parameter code in numpy: `nearest_index` (Pillow's accumulating NEAREST rule), `voc_palette`, `compute_iou` (the
+    reference's fp32 arithmetic), `SegGeometry` with the reference's YAML keys and `draw_geometry`, which draws one image's resize,
+    crop and flip from ``numpy.random.default_rng([seed, image_id, GEOMETRY_WORD])`` — a stream of its own, so that
+    `degrade.draw_params` / `draw_params2` return what they returned before.
+
+`prepare_pair` / `paired_mask` are the data sets' `load_items`, `evaluate` the test loop's tail."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+
+IGNORE = 255                            # the reference's "don't care" label; every target >= n is ignored
+GEOMETRY_WORD = 0x47454F4D              # "GEOM": the purpose word of `draw_geometry`'s generator
+CROP_TYPES = ("none", "center", "random")
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# numpy restatements (normative) and host-side parameters
+# ----------------------------------------------------------------------------------------------------------------------------------
+def nearest_index(n_in: int, n_out: int) -> np.ndarray:
+    """int32 [n_out]: the source index of every output position of `Image.resize(..., Image.NEAREST)` along one axis.  Pillow's
+    ImagingScaleAffine accumulates in double — xo = 0.5 s; idx[x] = (int)xo; xo += s with s = n_in / n_out — which is NOT
+    floor((x + 0.5) n_in / n_out): the two differ for many (n_in, n_out), 2 -> 7 and 500 -> 546 among them."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in <= 0 or n_out <= 0:
+        raise ValueError(f"sizes must be positive, got {n_in} -> {n_out}")
+    s = n_in / n_out
+    idx = np.empty(n_out, dtype=np.int32)
+    xo = 0.5 * s
+    for x in range(n_out):
+        idx[x] = int(xo)
+        xo += s
+    return np.minimum(idx, n_in - 1)
+
+
+def _u8(x, what: str) -> np.ndarray:
+    x = np.ascontiguousarray(x)
+    if x.dtype != np.uint8 or x.ndim not in (2, 3) or (x.ndim == 3 and x.shape[2] not in (1, 3)):
+        raise TypeError(f"{what} takes a uint8 [h, w] label map or a uint8 [h, w, C] array with C of 1 or 3")
+    return x
+
+
+def _hw(size) -> Tuple[int, int]:
+    H, W = (int(size), int(size)) if isinstance(size, (int, np.integer)) else (int(size[0]), int(size[1]))
+    if H <= 0 or W <= 0:
+        raise ValueError(f"an extent must be positive, got {H} x {W}")
+    return H, W
+
+
+def resize_nearest_reference(x, size) -> np.ndarray:
+    """`Image.fromarray(x).resize((W, H), Image.NEAREST)` for ``size`` = (H, W): a gather through `nearest_index` of each axis"""
+    x = _u8(x, "resize_nearest_reference")
+    H, W = _hw(size)
+    return np.ascontiguousarray(x[nearest_index(x.shape[0], H)][:, nearest_index(x.shape[1], W)])
+
+
+def window_reference(x, out_hw, origin=(0, 0), hflip: bool = False, vflip: bool = False, fill: int = 0) -> np.ndarray:
+    """out (y, x) = x (y0 + y', x0 + x'), y' = H - 1 - y under ``vflip``, x' = W - 1 - x under ``hflip``; ``fill`` outside the source:
+    np.pad(constant), a crop at ``origin`` = (y0, x0) and the two flips of `augment` at once."""
+    x = _u8(x, "window_reference")
+    H, W = _hw(out_hw)
+    y0, x0 = int(origin[0]), int(origin[1])
+    if not 0 <= int(fill) <= 255:
+        raise ValueError(f"fill must be a byte, got {fill}")
+    sy = y0 + (np.arange(H)[::-1] if vflip else np.arange(H))
+    sx = x0 + (np.arange(W)[::-1] if hflip else np.arange(W))
+    inside = ((sy >= 0) & (sy < x.shape[0]))[:, None] & ((sx >= 0) & (sx < x.shape[1]))[None, :]
+    got = x[np.clip(sy, 0, x.shape[0] - 1)][:, np.clip(sx, 0, x.shape[1] - 1)]
+    return np.ascontiguousarray(np.where(inside if x.ndim == 2 else inside[:, :, None], got, np.uint8(fill)).astype(np.uint8))
+
+
+def argmax_reference(logits) -> np.ndarray:
+    """uint8 argmax over axis 1 by torch's CPU rule, which is numpy's: the first NaN if there is one, else the first maximum
+    (-0.0 == 0.0 is a tie)"""
+    return np.argmax(np.asarray(logits), axis=1).astype(np.uint8)
+
+
+def confusion_reference(logits, target, n: Optional[int] = None, sizes=None, return_pred: bool = False):
+    """int64 [n, n]: `calculate_mat(target, argmax(logits), n)` as main/seg/test_edtr.py:159 calls it — a pixel counts iff its target is
+    < n and then adds 1 to mat[target][argmax]; with ``sizes`` only the top-left (h, w) of image b counts.  ``logits`` [B, n, H, W]
+    (any float type numpy holds; widen bf16 to fp32 first), ``target`` uint8 [B, H, W]."""
+    logits = np.asarray(logits)
+    target = np.asarray(target)
+    if logits.ndim != 4 or target.shape != logits.shape[:1] + logits.shape[2:] or target.dtype != np.uint8:
+        raise ValueError(f"expected logits [B, n, H, W] and a uint8 target [B, H, W], got {logits.shape} and {target.shape} {target.dtype}")
+    n = logits.shape[1] if n is None else int(n)
+    if n != logits.shape[1]:
+        raise ValueError(f"{logits.shape[1]} logit planes for n = {n}")
+    pred = argmax_reference(logits)
+    keep = target < n
+    if sizes is not None:
+        B, H, W = target.shape
+        for b, (h, w) in enumerate(sizes):
+            if not (0 < int(h) <= H and 0 < int(w) <= W):
+                raise ValueError(f"a {h} x {w} extent lies outside the {H} x {W} slot")
+            keep[b, int(h):, :] = False
+            keep[b, :, int(w):] = False
+    inds = n * target[keep].astype(np.int64) + pred[keep]
+    mat = np.bincount(inds, minlength=n * n).reshape(n, n).astype(np.int64)
+    return (mat, pred) if return_pred else mat
+
+
+def compute_iou(mat) -> np.ndarray:
+    """fp32 [n]: diag / (row sums + column sums - diag) on float32(mat), the reference's compute_iou (utils/segmentation.py:105-108).
+    A class absent from truth and prediction alike is 0 / 0 = NaN, and a mean over it is NaN: the reference's behaviour, kept.
+    Equal to the reference bit for bit while every row and column sum stays below 2^24 (all partial sums are then exact in fp32).
+    Beyond that — a whole VOC validation set counts about 3.6e8 pixels — numpy and torch add the 21 terms in different orders (torch's
+    is a detail of its CPU reduction kernels); each sum is then within 20 * 2^-24 relative of the exact one, the union
+    rows + columns - diagonal has no cancellation (it is at least either sum), and an IoU can differ from the reference's by up to
+    about 100 * 2^-24 = 6e-6 relative (tests/golden/labels.npz holds such a matrix; the CPU test asserts that bound)."""
+    h = np.asarray(mat).astype(np.float32)
+    if h.ndim != 2 or h.shape[0] != h.shape[1]:
+        raise ValueError(f"a confusion matrix is square, got {h.shape}")
+    d = np.diag(h)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (d / (h.sum(1, dtype=np.float32) + h.sum(0, dtype=np.float32) - d)).astype(np.float32)
+
+
+def mean_iou(mat) -> float:
+    """`compute_iou(confmat).mean().item() * 100` (main/seg/test_edtr.py:174)"""
+    return float(np.mean(compute_iou(mat), dtype=np.float32)) * 100
+
+
+def voc_palette() -> np.ndarray:
+    """uint8 [256, 3]: the standard PASCAL-VOC colour map by its bit-reversal rule — bit j of channel c of label i is bit 3 j + c of i,
+    placed at bit 7 - j"""
+    pal = np.zeros((256, 3), dtype=np.uint8)
+    for i in range(256):
+        c = i
+        for j in range(8):
+            for ch in range(3):
+                pal[i, ch] |= ((c >> ch) & 1) << (7 - j)
+            c >>= 3
+    return pal
+
+
+def _palette(palette) -> np.ndarray:
+    if palette is None:
+        return voc_palette()
+    p = np.asarray(palette)
+    if p.dtype != np.uint8 or p.ndim != 2 or p.shape[1] != 3 or not 1 <= p.shape[0] <= 256:
+        raise TypeError("a palette is a uint8 [k, 3] array with k <= 256 (labels from k on come out black)")
+    full = np.zeros((256, 3), dtype=np.uint8)
+    full[:p.shape[0]] = p
+    return full
+
+
+def colorize_reference(labels, palette=None) -> np.ndarray:
+    """uint8 [..., 3] = palette[labels]: the bytes save_image writes for convert2color's mask"""
+    labels = np.asarray(labels)
+    if labels.dtype != np.uint8:
+        raise TypeError("colorize_reference takes uint8 labels")
+    return _palette(palette)[labels]
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# geometry of the reference's segmentation data sets
+# ----------------------------------------------------------------------------------------------------------------------------------
+@dataclass
+class SegGeometry:
+    """The geometry keys of DegradedSegmentationDataset (configs/seg/*/train/*.yaml, `dataset.train.params`).  ``resize_range`` None:
+    r = 1; ``out_size`` None: no padding (and then no crop)."""
+    gt_size: int = 560
+    resize_range: Optional[Sequence[float]] = None
+    out_size: Optional[int] = 512
+    crop_type: str = "center"
+    hflip: bool = False
+    rotation: bool = False
+
+    KEYS = ("gt_size", "resize_range", "out_size", "crop_type", "hflip", "rotation")
+
+    def __post_init__(self):
+        if self.rotation:
+            # the reference's rot90 branch calls transpose(1, 0, 2) on the 2-D mask and cannot run; every seg config sets rotation: false
+            raise NotImplementedError("rotation is not provided: the reference's own rotation cannot run on a mask")
+        if int(self.gt_size) <= 0:
+            raise ValueError(f"gt_size must be positive, got {self.gt_size}")
+        if self.crop_type not in CROP_TYPES:
+            raise ValueError(f"crop_type must be one of {CROP_TYPES}, got {self.crop_type!r}")
+        if self.out_size is not None and int(self.out_size) <= 0:
+            raise ValueError(f"out_size must be positive, got {self.out_size}")
+        if self.crop_type != "none" and self.out_size is None:
+            raise ValueError("a crop needs an out_size")
+        if self.resize_range is not None and not (len(self.resize_range) == 2 and 0 < float(self.resize_range[0]) <= float(self.resize_range[1])):
+            raise ValueError(f"resize_range must be [a, b] with 0 < a <= b, got {list(self.resize_range)}")
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "SegGeometry":
+        """From a mapping that holds the keys at its top level, under dataset.params or under dataset.train.params / dataset.val.params
+        as the reference's configs do; other keys are ignored."""
+        def find(node):
+            if not isinstance(node, dict):
+                return None
+            if "gt_size" in node:
+                return node
+            for key in ("dataset", "train", "val", "params"):
+                hit = find(node.get(key))
+                if hit is not None:
+                    return hit
+            return None
+        node = find(d)
+        if node is None:
+            raise ValueError("no gt_size key: not a geometry of the reference's segmentation data sets")
+        return cls(**{k: node[k] for k in cls.KEYS if k in node})
+
+
+def load_geometry(spec) -> SegGeometry:
+    """A `SegGeometry`, a mapping with its keys, or the path of a YAML file that holds them"""
+    if isinstance(spec, SegGeometry):
+        return spec
+    if isinstance(spec, dict):
+        return SegGeometry.from_dict(spec)
+    try:
+        import yaml
+    except ImportError as e:
+        raise RuntimeError("reading a YAML geometry needs PyYAML (`import yaml` failed)") from e
+    with open(spec) as fh:
+        return SegGeometry.from_dict(yaml.safe_load(fh))
+
+
+@dataclass
+class GeometryParams:
+    """What `draw_geometry` fixed for one image: resize to ``size``, pad by ``pad`` at the bottom / right, cut ``out_hw`` at ``origin``
+    of the padded image, flip."""
+    size: Tuple[int, int]               # (h, w) after the resize
+    pad: Tuple[int, int]                # (rows, columns) added at the bottom / right
+    origin: Tuple[int, int]             # (y0, x0) of the crop in the padded image
+    out_hw: Tuple[int, int]
+    hflip: bool
+
+
+def resized_extent(gt_size: int, h: int, w: int, r: float = 1.0) -> Tuple[int, int]:
+    """(h', w') of datasets/segmentation.py:86-92 with its order of operations: the shorter side to int(gt_size * r), the longer one
+    to int(gt_size * long / short * r)"""
+    if w >= h:
+        ow, oh = int(gt_size * w / h * r), int(gt_size * r)
+    else:
+        ow, oh = int(gt_size * r), int(gt_size * h / w * r)
+    if oh <= 0 or ow <= 0:
+        raise ValueError(f"gt_size {gt_size} and r {r} leave nothing of a {h} x {w} image")
+    return oh, ow
+
+
+def draw_geometry(cfg: SegGeometry, seed: int, image_id: int, hw: Tuple[int, int]) -> GeometryParams:
+    """One image's geometry from ``numpy.random.default_rng([seed, image_id, GEOMETRY_WORD])``: a function of the configuration, the
+    seed, the image's data-set index and its extent.  Four uniform draws, made whether or not they are used: r, the crop's row, its
+    column, the flip."""
+    seed, image_id = int(seed), int(image_id)
+    if not 0 <= seed < 1 << 64 or not 0 <= image_id < 1 << 32:
+        raise ValueError(f"seed must be in [0, 2^64) and image_id in [0, 2^32), got {seed} and {image_id}")
+    h, w = int(hw[0]), int(hw[1])
+    if h <= 0 or w <= 0:
+        raise ValueError(f"an image extent must be positive, got {h} x {w}")
+    gen = np.random.default_rng([seed, image_id, GEOMETRY_WORD])
+    u_r, u_y, u_x, u_flip = (float(gen.uniform()) for _ in range(4))
+    r = 1.0
+    if cfg.resize_range is not None:
+        r = float(cfg.resize_range[0]) + u_r * (float(cfg.resize_range[1]) - float(cfg.resize_range[0]))
+    rh, rw = resized_extent(int(cfg.gt_size), h, w, r)
+    out = None if cfg.out_size is None else int(cfg.out_size)
+    ph, pw = (0, 0) if out is None else (max(out - rh, 0), max(out - rw, 0))
+    H, W = rh + ph, rw + pw
+    if cfg.crop_type == "none":
+        origin, out_hw = (0, 0), (H, W)
+    elif cfg.crop_type == "center":
+        origin, out_hw = ((H - out) // 2, (W - out) // 2), (out, out)
+    else:
+        origin, out_hw = (min(int(u_y * (H - out + 1)), H - out), min(int(u_x * (W - out + 1)), W - out)), (out, out)
+    return GeometryParams((rh, rw), (ph, pw), origin, out_hw, bool(cfg.hflip and u_flip < 0.5))
+
+
+def prepare_pair_reference(image_u8, mask_u8, geom: GeometryParams):
+    """numpy restatement of `prepare_pair`: (gt uint8 [H, W, 3], mask uint8 [H, W])"""
+    from .imageio import resize_u8_reference
+    rh, rw = geom.size
+    gt = window_reference(resize_u8_reference(np.asarray(image_u8), rw, rh), geom.out_hw, geom.origin, geom.hflip, False, 0)
+    mask = window_reference(resize_nearest_reference(mask_u8, (rh, rw)), geom.out_hw, geom.origin, geom.hflip, False, IGNORE)
+    return gt, mask
+
+
+def _center_origin(hw, center_crop) -> Tuple[Tuple[int, int], Tuple[int, int]]:
+    c = _hw(center_crop)
+    if hw[0] < c[0] or hw[1] < c[1]:
+        raise ValueError(f"a {hw[0]} x {hw[1]} mask is smaller than the {c[0]} x {c[1]} centre crop")
+    return ((hw[0] - c[0]) // 2, (hw[1] - c[1]) // 2), c
+
+
+def paired_mask_reference(mask_u8, gt_hw, center_crop=None) -> np.ndarray:
+    """numpy restatement of `paired_mask`"""
+    m = resize_nearest_reference(mask_u8, gt_hw)
+    if center_crop is None:
+        return m
+    origin, c = _center_origin(m.shape[:2], center_crop)
+    return window_reference(m, c, origin, fill=IGNORE)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# device side
+# ----------------------------------------------------------------------------------------------------------------------------------
+_INDEX_TABLES: dict = {}
+_PALETTES: dict = {}
+INDEX_TABLES_KEPT = 64
+
+
+def _index_on(n_in: int, n_out: int, device):
+    import torch
+    from .imageio import _device_key
+    key = (n_in, n_out) + _device_key(device)
+    if key not in _INDEX_TABLES:
+        while len(_INDEX_TABLES) >= INDEX_TABLES_KEPT:
+            # (a table that a queued launch still reads stays valid as long as that launch was queued on the stream the table was
+            # allocated on: torch's allocator hands a freed block out again on that stream only, behind the launch)
+            _INDEX_TABLES.pop(next(iter(_INDEX_TABLES)))
+        _INDEX_TABLES[key] = torch.from_numpy(nearest_index(n_in, n_out)).to(device)
+    return _INDEX_TABLES[key]
+
+
+def _on_device(x, device, what: str):
+    """``x`` (numpy array or torch tensor, uint8 [h, w] or [h, w, C]) as a contiguous uint8 [h, w, C] device tensor, and whether it was 2-D"""
+    import torch
+    from .imageio import _device
+    t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.ndim not in (2, 3) or (t.ndim == 3 and t.shape[2] not in (1, 3)):
+        raise TypeError(f"{what} takes a uint8 [h, w] label map or a uint8 [h, w, C] image with C of 1 or 3")
+    dev = t.device if t.is_cuda and device is None else _device(device)
+    flat = t.ndim == 2
+    t = t.to(dev).contiguous()
+    return (t[:, :, None] if flat else t), flat
+
+
+def resize_nearest(x, size, device=None):
+    """`resize_nearest_reference` on the device: ``size`` = (H, W)"""
+    import torch
+    from . import ops
+    src, flat = _on_device(x, device, "resize_nearest")
+    H, W = _hw(size)
+    dst = torch.empty((H, W, src.shape[2]), dtype=torch.uint8, device=src.device)
+    ops.launch(ops.make_label_resize_nearest(src=src, dst=dst, y_idx=_index_on(src.shape[0], H, src.device),
+                                             x_idx=_index_on(src.shape[1], W, src.device)))
+    return dst[:, :, 0] if flat else dst
+
+
+def window(x, out_hw, origin=(0, 0), hflip: bool = False, vflip: bool = False, fill: int = 0, device=None):
+    """`window_reference` on the device"""
+    import torch
+    from . import ops
+    src, flat = _on_device(x, device, "window")
+    H, W = _hw(out_hw)
+    if not 0 <= int(fill) <= 255:
+        raise ValueError(f"fill must be a byte, got {fill}")
+    dst = torch.empty((H, W, src.shape[2]), dtype=torch.uint8, device=src.device)
+    ops.launch(ops.make_label_window(src=src, dst=dst, y0=int(origin[0]), x0=int(origin[1]), hflip=hflip, vflip=vflip, fill=int(fill)))
+    return dst[:, :, 0] if flat else dst
+
+
+def confusion(logits, target, n: int = 21, sizes=None, mat=None, return_pred: bool = False, max_blocks: int = 0):
+    """`confusion_reference` on the device, one launch: ``logits`` a contiguous fp32 / fp16 / bf16 [B, n, H, W] tensor, ``target`` uint8
+    [B, H, W].  ``mat`` (int64 [n, n] on the device) is ADDED to and returned; without it a zeroed one is made.  ``max_blocks`` caps
+    the grid (0: the default cap).  Returns mat, or (mat, pred uint8 [B, H, W]) with ``return_pred``; nothing is brought to the host,
+    and with ``target`` on the device the call does not wait for it (a host ``target`` is uploaded first)."""
+    import torch
+    from . import ops
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.ndim != 4 or not logits.is_contiguous():
+        raise TypeError("confusion takes a contiguous [B, n, H, W] logits tensor on the device")
+    if logits.shape[1] != int(n):
+        raise ValueError(f"{logits.shape[1]} logit planes for n = {n}")
+    target = torch.as_tensor(target)
+    if target.dtype != torch.uint8 or tuple(target.shape) != (logits.shape[0],) + tuple(logits.shape[2:]):
+        raise ValueError(f"target must be uint8 [B, H, W] matching the logits, got {target.dtype} {tuple(target.shape)}")
+    target = target.to(logits.device).contiguous()
+    if sizes is not None:
+        sizes = [(int(h), int(w)) for h, w in sizes]
+        if len(sizes) != logits.shape[0]:
+            raise ValueError(f"{len(sizes)} sizes for a batch of {logits.shape[0]}")
+    if mat is None:
+        mat = torch.zeros((int(n), int(n)), dtype=torch.int64, device=logits.device)
+    elif mat.dtype != torch.int64 or tuple(mat.shape) != (int(n), int(n)) or not mat.is_contiguous() or mat.device != logits.device:
+        raise TypeError(f"mat must be a contiguous int64 [{n}, {n}] tensor on the logits' device")
+    pred = torch.empty(target.shape, dtype=torch.uint8, device=logits.device) if return_pred else None
+    ops.launch(ops.make_seg_confusion(logits=logits, target=target, mat=mat, sizes=sizes, pred=pred, max_blocks=int(max_blocks)))
+    return (mat, pred) if return_pred else mat
+
+
+def _palette_on(palette, device):
+    import torch
+    from .imageio import _device_key
+    if palette is not None:
+        return torch.from_numpy(_palette(palette)).to(device)
+    key = _device_key(device)
+    if key not in _PALETTES:
+        _PALETTES[key] = torch.from_numpy(voc_palette()).to(device)
+    return _PALETTES[key]
+
+
+def colorize(labels, palette=None, device=None):
+    """`colorize_reference` on the device: uint8 [H, W] or [B, H, W] labels -> uint8 [..., 3]; ``palette`` None (`voc_palette`) or a
+    uint8 [k, 3] array"""
+    import torch
+    from . import ops
+    from .imageio import _device
+    t = torch.from_numpy(np.ascontiguousarray(labels)) if isinstance(labels, np.ndarray) else labels
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.ndim not in (2, 3):
+        raise TypeError("colorize takes uint8 [H, W] or [B, H, W] labels")
+    dev = t.device if t.is_cuda and device is None else _device(device)
+    t = t.to(dev).contiguous()
+    dst = torch.empty(tuple(t.shape) + (3,), dtype=torch.uint8, device=dev)
+    ops.launch(ops.make_label_colorize(labels=t if t.ndim == 3 else t[None], palette=_palette_on(palette, dev), dst=dst))
+    return dst
+
+
+def prepare_pair(image_u8, mask_u8, geom: GeometryParams, device=None):
+    """`load_items` of DegradedSegmentationDataset for one decoded pair under the geometry `draw_geometry` fixed: the image through the
+    BICUBIC `imageio.resize_u8`, the mask through `resize_nearest`, then one `window` launch each (fill 0 against fill 255).
+    Returns (gt uint8 [H, W, 3], mask uint8 [H, W]) on the device."""
+    gt = prepare_image(image_u8, geom, device)
+    return gt, prepare_mask(mask_u8, geom, gt.device)
+
+
+def prepare_image(image_u8, geom: GeometryParams, device=None):
+    """the image half of `prepare_pair`"""
+    from . import imageio
+    rh, rw = geom.size
+    return window(imageio.resize_u8(image_u8, rw, rh, device=device), geom.out_hw, geom.origin, geom.hflip, False, 0)
+
+
+def prepare_mask(mask_u8, geom: GeometryParams, device=None):
+    """the mask half of `prepare_pair`"""
+    if getattr(mask_u8, "ndim", 0) != 2:
+        raise TypeError("a mask is a uint8 [h, w] label map")
+    return window(resize_nearest(mask_u8, geom.size, device=device), geom.out_hw, geom.origin, geom.hflip, False, IGNORE)
+
+
+def paired_mask(mask_u8, gt_hw, center_crop=None, device=None):
+    """The mask of PairedSegmentationDataset.load_items: NEAREST to the ground-truth extent ``gt_hw`` = (h, w), then the centre crop of
+    ``center_crop`` (the reference's is 512).  A mask smaller than the crop raises ValueError, where the reference would slice with a
+    negative origin."""
+    H, W = _hw(gt_hw)
+    if center_crop is None:
+        return resize_nearest(mask_u8, (H, W), device=device)
+    origin, c = _center_origin((H, W), center_crop)
+    return window(resize_nearest(mask_u8, (H, W), device=device), c, origin, fill=IGNORE)
+
+
+def evaluate(images, masks, segnet, n_classes: int = 21, return_preds: bool = False, palette=None):
+    """The tail of the reference's segmentation test: for every image (fp32 [3, h, w] or [1, 3, h, w] on the device, as
+    `evalutil.restore_dataset` returns them) one call of ``segnet`` — any callable from [1, 3, h, w] fp32 to logits [1, n, h, w], or to
+    a mapping with key "out" as torchvision's models return — and one `confusion` launch into a shared matrix against the uint8
+    [h, w] mask; with ``return_preds`` also the argmax and its colour map.  One device -> host copy at the end; masks that are not on
+    the device yet cost one upload each, so hand device tensors in where the loop must not touch the host.  Returns
+    {"mat": int64 [n, n], "iou": fp32 [n], "miou": float (in percent)} (and "preds", "colors": lists of device tensors)."""
+    import torch
+    images, masks = list(images), list(masks)
+    if not images or len(images) != len(masks):
+        raise ValueError(f"evaluate needs as many masks as images, got {len(masks)} for {len(images)}")
+    mat, preds, colors = None, [], []
+    for img, mask in zip(images, masks):
+        x = img if img.ndim == 4 else img[None]
+        out = segnet(x)
+        logits = (out["out"] if hasattr(out, "keys") else out).contiguous()
+        m = torch.as_tensor(mask)
+        if m.ndim != 2:
+            raise ValueError(f"a mask is a uint8 [h, w] label map, got {tuple(m.shape)}")
+        if mat is None:
+            mat = torch.zeros((int(n_classes), int(n_classes)), dtype=torch.int64, device=logits.device)
+        res = confusion(logits, m[None], n_classes, mat=mat, return_pred=return_preds)
+        if return_preds:
+            preds.append(res[1][0])
+            colors.append(colorize(res[1][0], palette))
+    host = mat.cpu().numpy()
+    result = {"mat": host, "iou": compute_iou(host), "miou": mean_iou(host)}
+    if return_preds:
+        result["preds"], result["colors"] = preds, colors
+    return result

@@ -14,6 +14,8 @@ ACT_NONE, ACT_GEGLU, ACT_SILU, ACT_GELU, ACT_LRELU = 0, 1, 2, 3, 4
 SQDIFF_BLOCKS = 64          # EDTR_SQDIFF_BLOCKS: fp64 partial sums per image of edtr_image_sqdiff
 TILE_WINDOWS_MAX = 4096     # EDTR_TILE_WINDOWS_MAX: windows per table of edtr_tile_gather / edtr_tile_blend
 RESIZE_BILINEAR, RESIZE_BICUBIC, RESIZE_AREA = 0, 1, 2      # EDTR_RESIZE_*: modes of edtr_degrade_resize
+LOGITS_F32, LOGITS_F16, LOGITS_BF16 = 0, 1, 2               # EDTR_LOGITS_*: logits_dtype of edtr_seg_confusion
+SEG_MAX_CLASSES = 32        # EDTR_SEG_MAX_CLASSES: the largest n of edtr_seg_confusion
 
 DECLARED_SYMBOLS = [
     "edtr_abi_version", "edtr_error_string", "edtr_device_info", "edtr_igemm", "edtr_flash_attn64",
@@ -29,6 +31,7 @@ DECLARED_SYMBOLS = [
     "edtr_tile_gather", "edtr_tile_blend",
     "edtr_degrade_filter2d", "edtr_degrade_resize", "edtr_degrade_gaussian_noise", "edtr_degrade_jpeg",
     "edtr_degrade_poisson_noise", "edtr_degrade_sepblur", "edtr_degrade_usm_apply",
+    "edtr_seg_confusion", "edtr_label_resize_nearest", "edtr_label_window", "edtr_label_colorize",
 ]
 
 
@@ -290,6 +293,11 @@ def load() -> C.CDLL:
     lib.edtr_degrade_poisson_noise.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.POINTER(f32), vp, C.POINTER(i32), vp, vp, vp, vp, vp, u64, vp, i64, i64, i32, vp]
     lib.edtr_degrade_sepblur.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, i32, f32, vp]
     lib.edtr_degrade_usm_apply.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]
+    # label maps (edtr_hip.h "Label maps"): sizes_host is a ctypes int32 array (or None)
+    lib.edtr_seg_confusion.argtypes = [i32, vp, vp, i32, i32, i32, i32, C.POINTER(i32), vp, vp, vp, i32, vp]
+    lib.edtr_label_resize_nearest.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]
+    lib.edtr_label_window.argtypes = [vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp]
+    lib.edtr_label_colorize.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     if lib.edtr_abi_version() != 10:
         raise RuntimeError("libedtr_hip.so ABI version mismatch")
     _lib = lib

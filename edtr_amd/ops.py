@@ -845,6 +845,49 @@ def make_degrade_usm_apply(*, x, blur, soft, out, weight: float, name="degrade.u
     return Rec(L.load().edtr_degrade_usm_apply, args, (x, blur, soft, out), name, 0.0, 16.0 * x.numel())
 
 
+# -- label maps (edtr_hip.h "Label maps"; the callers and the host restatements are edtr_amd/labels.py) -------------------------------
+_LOGITS_DT = {torch.float32: L.LOGITS_F32, torch.float16: L.LOGITS_F16, torch.bfloat16: L.LOGITS_BF16}
+
+
+def make_seg_confusion(*, logits, target, mat, sizes=None, pred=None, max_blocks: int = 0, name="labels.confusion") -> Rec:
+    """int64 ``mat`` [n, n] += the confusion matrix of argmax(``logits`` [B, n, H, W], fp32 / fp16 / bf16) against uint8 ``target``
+    [B, H, W]; ``sizes``: None or one (h, w) per image (uploaded here from pinned memory without waiting, and handed to the entry point as a host
+    array as well);
+    ``pred``: None or a uint8 [B, H, W] tensor that receives the argmax."""
+    B, n, H, W = logits.shape
+    if logits.dtype not in _LOGITS_DT:
+        raise TypeError(f"logits must be float32, float16 or bfloat16, got {logits.dtype}")
+    sizes_host = dsizes = None
+    if sizes is not None:
+        flat = [int(v) for hw in sizes for v in hw]
+        sizes_host = (ct.c_int32 * len(flat))(*flat)
+        dsizes = torch.tensor(flat, dtype=torch.int32).pin_memory().to(logits.device, non_blocking=True)      # (the host does not wait for it)
+    args = (_LOGITS_DT[logits.dtype], ptr(logits), ptr(target), B, n, H, W, sizes_host, ptr(dsizes), ptr(mat), ptr(pred), int(max_blocks))
+    nbytes = float(logits.element_size() * logits.numel() + target.numel() * (2 if pred is not None else 1))
+    return Rec(L.load().edtr_seg_confusion, args, (logits, target, sizes_host, dsizes, mat, pred), name, 0.0, nbytes)
+
+
+def make_label_resize_nearest(*, src, dst, y_idx, x_idx, name="labels.resize_nearest") -> Rec:
+    """uint8 ``src`` [in_h, in_w, C] -> ``dst`` [out_h, out_w, C] (C 1 or 3) through the int32 device tables ``y_idx`` [out_h] /
+    ``x_idx`` [out_w] of `labels.nearest_index`."""
+    (in_h, in_w, ch), (out_h, out_w, _) = src.shape, dst.shape
+    args = (ptr(src), in_h, in_w, ch, ptr(dst), out_h, out_w, ptr(y_idx), ptr(x_idx))
+    return Rec(L.load().edtr_label_resize_nearest, args, (src, dst, y_idx, x_idx), name, 0.0, 2.0 * dst.numel())
+
+
+def make_label_window(*, src, dst, y0: int, x0: int, hflip: bool, vflip: bool, fill: int, name="labels.window") -> Rec:
+    """uint8 ``src`` [h, w, C] -> ``dst`` [H, W, C]: the window at (y0, x0), flipped, ``fill`` outside the source."""
+    (h, w, ch), (H, W, _) = src.shape, dst.shape
+    args = (ptr(src), h, w, ch, ptr(dst), H, W, int(y0), int(x0), int(bool(hflip)), int(bool(vflip)), int(fill))
+    return Rec(L.load().edtr_label_window, args, (src, dst), name, 0.0, 2.0 * dst.numel())
+
+
+def make_label_colorize(*, labels, palette, dst, name="labels.colorize") -> Rec:
+    """uint8 ``labels`` [B, H, W] -> ``dst`` [B, H, W, 3] through the uint8 [256, 3] device ``palette``."""
+    B, H, W = labels.shape
+    return Rec(L.load().edtr_label_colorize, (ptr(labels), B, H, W, ptr(palette), ptr(dst)), (labels, palette, dst), name, 0.0, 4.0 * labels.numel())
+
+
 def make_cast16(*, dtype, src: torch.Tensor, rows: int, C: int, dst: torch.Tensor, name="cast16") -> Rec:
     args = (dt_code(dtype), ptr(src), rows, C, src.stride(0), ptr(dst), dst.stride(0))
     return Rec(L.load().edtr_cast16, args, (src, dst), name, 0.0, 6.0 * rows * C)

@@ -913,6 +913,53 @@ int edtr_degrade_sepblur(const float* x, float* out, float* mask_out, int B, int
 int edtr_degrade_usm_apply(const float* x, const float* blur, const float* soft, float* out, int B, int channels, int H, int W,
                            float weight, edtr_stream_t stream);
 
+/* ---- Label maps: what sits between the restored image and a segmentation score (additive to ABI 10) ------------------------------
+ * The reference's segmentation test goes on after the restoration (main/seg/test_edtr.py:139-174): logits -> argmax -> calculate_mat
+ * against the ground-truth mask -> compute_iou, and convert2color for the PNG; its data sets resize, pad, crop and flip image and mask
+ * together (datasets/segmentation.py:82-114, 207-215).  A label map here is uint8 [H][W] (255 = "ignore" by the reference's
+ * convention), an image uint8 [h][w][3].  Every launch is an integer or gather function of its inputs: edtr_amd/labels.py restates
+ * each in numpy and the kernels are tested against that by equality.  Rows move as dwords / float4 where the pitch and the base keep
+ * them aligned and element by element otherwise, as in "Images in, images out": nothing needs more than its natural alignment. */
+#define EDTR_LOGITS_F32 0
+#define EDTR_LOGITS_F16 1
+#define EDTR_LOGITS_BF16 2
+#define EDTR_SEG_MAX_CLASSES 32
+/* mat [n][n] (int64, device) += the confusion matrix of argmax(logits) against target; pred (optional, uint8 [B][H][W]) = the argmax.
+ * logits: [B][n][H][W] contiguous, fp32 / fp16 / bf16 by logits_dtype (EDTR_LOGITS_*; 16-bit values are widened exactly).
+ * target: uint8 [B][H][W].  sizes (optional): int32 [B][2] = (h, w): only the top-left h x w of image b is counted; passed on the host
+ * (sizes_host: checked here) and on the device (sizes: read by the kernel), both or neither.
+ *   argmax  torch's CPU rule: the lowest index among the NaN channels if there is one, else the lowest index among the maxima
+ *           (-0.0 == 0.0 is a tie)
+ *   count   a pixel inside sizes counts iff target < n (255 and every other value is ignored); it adds 1 to mat[target][argmax]
+ *   pred    every pixel of every slot is written, counted or not
+ * mat is ADDED to (the caller zeroes it: a data set accumulates without a host sync).  Integer sums: the result does not depend on
+ * the grid or on the order.  One launch, capped at max_blocks workgroups (0: the default cap) and grid-strided; counts go to LDS
+ * histograms and each workgroup adds its non-zero bins to mat once.
+ * Errors (nothing is launched): NULL logits / target / mat, or only one of sizes_host / sizes EDTR_E_NULL; unknown logits_dtype
+ * EDTR_E_DTYPE; B, n, H, W <= 0, max_blocks < 0 or a sizes_host entry outside [1, H] x [1, W] EDTR_E_SHAPE; n > EDTR_SEG_MAX_CLASSES
+ * EDTR_E_UNSUPPORTED; logits not aligned to an element, sizes to 4 or mat to 8 bytes EDTR_E_ALIGN.
+ * replaces: output.argmax(1) -> calculate_mat(mask, pred, n), main/seg/test_edtr.py:156-159, utils/segmentation.py:99-102. */
+int edtr_seg_confusion(int logits_dtype, const void* logits, const uint8_t* target, int B, int n, int H, int W,
+                       const int32_t* sizes_host, const int32_t* sizes, int64_t* mat, uint8_t* pred, int max_blocks,
+                       edtr_stream_t stream);
+/* src [in_h][in_w][channels] -> dst [out_h][out_w][channels], uint8, channels 1 or 3 (EDTR_E_UNSUPPORTED otherwise):
+ * dst (y, x) = src (y_idx[y], x_idx[x]) with the int32 tables y_idx [out_h] / x_idx [out_w] on the device.  The host builds them by
+ * Pillow's accumulating rule (ImagingScaleAffine: xo = 0.5 s; idx[x] = (int)xo; xo += s, in double, s = in / out), which is not
+ * floor((x + 0.5) in / out); the kernel forces every entry inside the source.
+ * replaces: Image.resize(size, Image.NEAREST), datasets/segmentation.py:89,92,210. */
+int edtr_label_resize_nearest(const uint8_t* src, int in_h, int in_w, int channels, uint8_t* dst, int out_h, int out_w,
+                              const int32_t* y_idx, const int32_t* x_idx, edtr_stream_t stream);
+/* src [h][w][channels] -> dst [H][W][channels], uint8, channels 1 or 3: dst (y, x) = src (y0 + y', x0 + x'), y' = H - 1 - y under vflip
+ * (else y), x' = W - 1 - x under hflip (else x); a position outside the source gives the byte `fill` (0 for images, 255 for masks).
+ * Pad, crop and both flips in one gather; no transposition.  hflip / vflip not 0 / 1 or fill outside [0, 255]: EDTR_E_DTYPE.
+ * replaces: np.pad(..., 'constant'), center_crop_arr / random_crop_arr and augment's flips, datasets/segmentation.py:96-114. */
+int edtr_label_window(const uint8_t* src, int h, int w, int channels, uint8_t* dst, int H, int W, int y0, int x0, int hflip,
+                      int vflip, int fill, edtr_stream_t stream);
+/* labels uint8 [B][H][W] -> dst uint8 [B][H][W][3] = palette[label], palette uint8 [256][3] on the device: the bytes save_image
+ * writes for convert2color's mask (a colour c / 255 through the emit rule gives c back).
+ * replaces: convert2color -> save_image, utils/segmentation.py:52-96, main/seg/test_edtr.py:170-174. */
+int edtr_label_colorize(const uint8_t* labels, int B, int H, int W, const uint8_t* palette, uint8_t* dst, edtr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * hipGraph capture of a launch sequence issued on `stream` (one denoise step, or a whole batch).
  * ---------------------------------------------------------------------------------------- */
