@@ -16,6 +16,8 @@ TILE_WINDOWS_MAX = 4096     # EDTR_TILE_WINDOWS_MAX: windows per table of edtr_t
 RESIZE_BILINEAR, RESIZE_BICUBIC, RESIZE_AREA = 0, 1, 2      # EDTR_RESIZE_*: modes of edtr_degrade_resize
 LOGITS_F32, LOGITS_F16, LOGITS_BF16 = 0, 1, 2               # EDTR_LOGITS_*: logits_dtype of edtr_seg_confusion
 SEG_MAX_CLASSES = 32        # EDTR_SEG_MAX_CLASSES: the largest n of edtr_seg_confusion
+NMS_MAX_BOXES = 32768       # EDTR_NMS_MAX_BOXES: the largest n of edtr_boxes_nms
+BOX_SHIFT, BOX_MUL, BOX_DIV, BOX_CLIP = 1, 2, 4, 8          # EDTR_BOX_*: flags of edtr_boxes_transform
 
 DECLARED_SYMBOLS = [
     "edtr_abi_version", "edtr_error_string", "edtr_device_info", "edtr_igemm", "edtr_flash_attn64",
@@ -32,6 +34,7 @@ DECLARED_SYMBOLS = [
     "edtr_degrade_filter2d", "edtr_degrade_resize", "edtr_degrade_gaussian_noise", "edtr_degrade_jpeg",
     "edtr_degrade_poisson_noise", "edtr_degrade_sepblur", "edtr_degrade_usm_apply",
     "edtr_seg_confusion", "edtr_label_resize_nearest", "edtr_label_window", "edtr_label_colorize",
+    "edtr_boxes_rank", "edtr_boxes_nms", "edtr_boxes_candidates", "edtr_boxes_filter_shift", "edtr_boxes_transform", "edtr_boxes_bilinear_scale",
 ]
 
 
@@ -298,6 +301,13 @@ def load() -> C.CDLL:
     lib.edtr_label_resize_nearest.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]
     lib.edtr_label_window.argtypes = [vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.edtr_label_colorize.argtypes = [vp, i32, i32, i32, vp, vp, vp]
+    # detection boxes (edtr_hip.h "Detection boxes"): weights is a ctypes float array of four
+    lib.edtr_boxes_rank.argtypes = [vp, i32, vp, vp]
+    lib.edtr_boxes_nms.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp, vp, i32, vp, vp]
+    lib.edtr_boxes_candidates.argtypes = [vp, vp, vp, i32, i32, f32, f32, f32, f32, C.POINTER(f32), f32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.edtr_boxes_filter_shift.argtypes = [vp, vp, vp, i32, f32, f32, f32, vp, vp, vp, vp, i32, vp]
+    lib.edtr_boxes_transform.argtypes = [vp, vp, i32, i32, f32, f32, f32, f32, f32, f32, vp]
+    lib.edtr_boxes_bilinear_scale.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, f32, vp]
     if lib.edtr_abi_version() != 10:
         raise RuntimeError("libedtr_hip.so ABI version mismatch")
     _lib = lib

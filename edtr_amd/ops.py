@@ -888,6 +888,57 @@ def make_label_colorize(*, labels, palette, dst, name="labels.colorize") -> Rec:
     return Rec(L.load().edtr_label_colorize, (ptr(labels), B, H, W, ptr(palette), ptr(dst)), (labels, palette, dst), name, 0.0, 4.0 * labels.numel())
 
 
+# -- detection boxes (edtr_hip.h "Detection boxes"; the callers and the host restatements are edtr_amd/boxes.py) ---------------------
+def make_boxes_rank(*, scores, order, name="boxes.rank") -> Rec:
+    """int32 ``order`` [n] = the stable descending argsort of fp32 ``scores`` [n] (NaN first), by counting"""
+    return Rec(L.load().edtr_boxes_rank, (ptr(scores), scores.numel(), ptr(order)), (scores, order), name, 0.0, 8.0 * scores.numel())
+
+
+def make_boxes_nms(*, boxes, scores, labels, iou_threshold: float, order, mask, keep, count, name="boxes.nms") -> Rec:
+    """``keep`` int64 [max_out] / ``count`` int32 [1] = the per-label NMS of fp32 ``boxes`` [n, 4] / ``scores`` [n]; ``labels``: None,
+    int32 [n] or int64 [n]; ``order`` int32 [n] and ``mask`` int64 [n * ceil(n / 64)]: workspaces."""
+    n = boxes.shape[0]
+    i64 = int(labels is not None and labels.dtype == torch.int64)
+    args = (ptr(boxes), ptr(scores), ptr(labels), i64, n, float(iou_threshold), ptr(order), ptr(mask), ptr(keep), keep.numel(), ptr(count))
+    return Rec(L.load().edtr_boxes_nms, args, (boxes, scores, labels, order, mask, keep, count), name, 0.0, 8.0 * mask.numel())
+
+
+def make_boxes_candidates(*, logits, regression, proposals, image_hw, score_thresh, min_size, weights, xform_clip, cand_boxes, cand_scores,
+                          flags, block_counts, out_boxes, out_scores, out_labels, count, name="boxes.candidates") -> Rec:
+    """The candidate stage of the detector head's post-processing: fp32 ``logits`` [P, C], ``regression`` [P, 4 C], ``proposals`` [P, 4]
+    -> the flagged candidates in ``out_boxes`` / ``out_scores`` / ``out_labels`` (int32) and their number in ``count`` (int32 [1])."""
+    P, C = logits.shape
+    w_host = (ct.c_float * 4)(*[float(w) for w in weights])
+    args = (ptr(logits), ptr(regression), ptr(proposals), P, C, float(image_hw[0]), float(image_hw[1]), float(score_thresh), float(min_size),
+            w_host, float(xform_clip), ptr(cand_boxes), ptr(cand_scores), ptr(flags), ptr(block_counts), ptr(out_boxes), ptr(out_scores),
+            ptr(out_labels), ptr(count))
+    keep = (logits, regression, proposals, w_host, cand_boxes, cand_scores, flags, block_counts, out_boxes, out_scores, out_labels, count)
+    return Rec(L.load().edtr_boxes_candidates, args, keep, name, 0.0, 4.0 * (logits.numel() + regression.numel()) + 42.0 * P * (C - 1))
+
+
+def make_boxes_filter_shift(*, boxes, scores, labels, score_min: float, dx: float, dy: float, out_boxes, out_scores, out_labels, offset,
+                            name="boxes.filter_shift") -> Rec:
+    """the boxes with score >= ``score_min``, shifted by (dx, dy), appended to the ``out_*`` tensors at the device counter ``offset``"""
+    n = boxes.shape[0]
+    args = (ptr(boxes), ptr(scores), ptr(labels), n, float(score_min), float(dx), float(dy), ptr(out_boxes), ptr(out_scores), ptr(out_labels),
+            ptr(offset), out_scores.numel())
+    return Rec(L.load().edtr_boxes_filter_shift, args, (boxes, scores, labels, out_boxes, out_scores, out_labels, offset), name, 0.0, 56.0 * n)
+
+
+def make_boxes_transform(*, src, dst, flags: int, dx=0.0, dy=0.0, fx=1.0, fy=1.0, clip_w=0.0, clip_h=0.0, name="boxes.transform") -> Rec:
+    """``dst`` = ``src`` (fp32 [n, 4]) shifted, multiplied or divided, clipped: each under its lib.BOX_* flag, in that order"""
+    args = (ptr(src), ptr(dst), src.shape[0], int(flags), float(dx), float(dy), float(fx), float(fy), float(clip_w), float(clip_h))
+    return Rec(L.load().edtr_boxes_transform, args, (src, dst), name, 0.0, 32.0 * src.shape[0])
+
+
+def make_boxes_bilinear_scale(*, src, dst, rscale_h: float, rscale_w: float, name="boxes.bilinear_scale") -> Rec:
+    """fp32 ``src`` [planes, ih, iw] -> ``dst`` [planes, oh, ow] as F.interpolate(scale_factor=, mode="bilinear"): source coordinates from
+    ``rscale_*`` = fp32(1 / scale_factor)."""
+    planes, ih, iw = src.shape
+    args = (ptr(src), ptr(dst), planes, ih, iw, dst.shape[1], dst.shape[2], float(rscale_h), float(rscale_w))
+    return Rec(L.load().edtr_boxes_bilinear_scale, args, (src, dst), name, 0.0, 4.0 * (src.numel() + dst.numel()))
+
+
 def make_cast16(*, dtype, src: torch.Tensor, rows: int, C: int, dst: torch.Tensor, name="cast16") -> Rec:
     args = (dt_code(dtype), ptr(src), rows, C, src.stride(0), ptr(dst), dst.stride(0))
     return Rec(L.load().edtr_cast16, args, (src, dst), name, 0.0, 6.0 * rows * C)

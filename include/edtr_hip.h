@@ -960,6 +960,75 @@ int edtr_label_window(const uint8_t* src, int h, int w, int channels, uint8_t* d
  * replaces: convert2color -> save_image, utils/segmentation.py:52-96, main/seg/test_edtr.py:170-174. */
 int edtr_label_colorize(const uint8_t* labels, int B, int H, int W, const uint8_t* palette, uint8_t* dst, edtr_stream_t stream);
 
+/* ---- Detection boxes: what sits between a detector and the boxes a user sees (additive to ABI 10) ---------------------------------
+ * The reference's demo runs its detector on the restored image in three modes (demo.py:126-160) and merges the tiled mode's windows
+ * with torchvision's batched_nms; the detector's head ends in RoIHeads.postprocess_detections (model/faster_rcnn.py:1187-1244).
+ * Boxes are fp32 [n][4] in xyxy, 16-byte aligned; scores fp32 [n].  edtr_amd/boxes.py restates every launch in numpy: all arithmetic
+ * is correctly rounded fp32 in the order written here (no contraction), so the restatements agree bit for bit except where expf
+ * enters.  No launch waits on another workgroup and none uses an atomic: dependent phases are separate launches on the stream. */
+#define EDTR_NMS_MAX_BOXES 32768
+/* Non-maximum suppression, per label.  With key(s) the uint32 order of torch's sort (all NaN scores equal and largest, -0.0 == 0.0):
+ *   order   rank(i) = #{j : key(s_j) > key(s_i)} + #{j < i : key(s_j) == key(s_i)}; order[rank(i)] = i   (stable, descending)
+ *   walk    in that order: a candidate not yet suppressed is kept, and suppresses every LATER candidate j of the SAME label with
+ *           inter / ((area_i + area_j) - inter) > iou_threshold, where area = (x2 - x1) * (y2 - y1),
+ *           inter = max0(min(x2_i, x2_j) - max(x1_i, x1_j)) * max0(min(y2_i, y2_j) - max(y1_i, y1_j)), max(a, b) = a > b ? a : b,
+ *           min(a, b) = a < b ? a : b, max0(d) = d > 0 ? d : 0 (0 / 0 = NaN suppresses nothing)
+ *   keep    [max_out] int64: the kept indices into the input in walk order, the walk ending after max_out of them; the rest -1;
+ *           *count (int32, device) = the number written
+ * labels: NULL (one label), int32 [n] or, with labels_i64 = 1, int64 [n].  Workspaces: order int32 [n], mask uint64
+ * [n][ceil(n / 64)] (neither needs zeroing).  Three launches: the counting rank (the j side tiled through LDS), one wave64 workgroup
+ * per 64 x 64 block of the upper triangle of (row, column) in rank order whose lane r writes the 64-bit word of row r, and a
+ * one-workgroup scan with the removed-set in LDS.
+ * Errors: a NULL pointer but labels EDTR_E_NULL; n <= 0 or max_out <= 0 EDTR_E_SHAPE; n > EDTR_NMS_MAX_BOXES EDTR_E_UNSUPPORTED;
+ * labels_i64 not 0 / 1 EDTR_E_DTYPE; boxes not aligned to 16 bytes, the others to their element EDTR_E_ALIGN.
+ * replaces: torchvision.ops.batched_nms (its per-label form, _batched_nms_vanilla), demo.py:156, model/faster_rcnn.py:1235. */
+/* The first launch of edtr_boxes_nms alone: order [n] (int32) = the stable descending argsort of scores by key, by counting — O(n^2)
+ * comparisons, deterministic, no atomics.  n <= 0 EDTR_E_SHAPE, n > EDTR_NMS_MAX_BOXES EDTR_E_UNSUPPORTED. */
+int edtr_boxes_rank(const float* scores, int n, int32_t* order, edtr_stream_t stream);
+int edtr_boxes_nms(const float* boxes, const float* scores, const void* labels, int labels_i64, int n, float iou_threshold,
+                   int32_t* order, uint64_t* mask, int64_t* keep, int max_out, int32_t* count, edtr_stream_t stream);
+/* The candidate stage of postprocess_detections for one image: logits [P][C], regression [P][4 C], proposals [P][4] ->
+ *   score   softmax over the C logits of a row (fp32; maximum and sum by wave reduction, expf)
+ *   box     for every class c >= 1, BoxCoder.decode_single (model/util.py:702-743) in its order: w = x2 - x1, cx = x1 + 0.5 w;
+ *           dx = r0 / wx, dw = min(r2 / ww, xform_clip); pcx = dx w + cx, pw = expf(dw) w; x1' = pcx - 0.5 pw, x2' = pcx + 0.5 pw
+ *           (y alike); then clamped to [0, img_w] / [0, img_h]
+ *   flag    score > score_thresh && x2' - x1' >= min_size && y2' - y1' >= min_size
+ * out_boxes / out_scores / out_labels (int32, = c) receive the flagged candidates in candidate-index order p (C - 1) + (c - 1), and
+ * *count (int32, device) their number.  weights: four floats on the HOST (wx, wy, ww, wh; non-zero).  Workspaces: cand_boxes
+ * [P (C - 1)][4], cand_scores and flags (bytes) [P (C - 1)], block_counts int32 [ceil(P / 4)]; the outputs hold up to P (C - 1) rows.
+ * Three launches: one wave per proposal row, a one-workgroup prefix sum of the per-workgroup counts, the ordered scatter.
+ * Errors: NULL EDTR_E_NULL; P <= 0, C < 2, a zero or NaN weight EDTR_E_SHAPE; P C > 2^24 EDTR_E_UNSUPPORTED; regression, proposals
+ * and the box outputs not aligned to 16 bytes EDTR_E_ALIGN.
+ * replaces: F.softmax, BoxCoder.decode, clip_boxes_to_image, torch.where, remove_small_boxes, model/faster_rcnn.py:1199-1232. */
+int edtr_boxes_candidates(const float* logits, const float* regression, const float* proposals, int P, int C, float img_h, float img_w,
+                          float score_thresh, float min_size, const float* weights, float xform_clip, float* cand_boxes,
+                          float* cand_scores, uint8_t* flags, int32_t* block_counts, float* out_boxes, float* out_scores,
+                          int32_t* out_labels, int32_t* count, edtr_stream_t stream);
+/* One window of the tiled mode: the boxes with score >= score_min (a NaN score fails), in their order, shifted by (dx, dy), appended
+ * to out_boxes / out_scores / out_labels (int32) at row *offset (int32, device), which is moved on; nothing is written at or past
+ * row `capacity`.  labels int64 [n].  One workgroup; the running offset stays on the device, so a loop over windows needs no host sync.
+ * replaces: the score filter, move_boxes and the three torch.cat of demo.py:143-155, utils/detection.py:687-692. */
+int edtr_boxes_filter_shift(const float* boxes, const float* scores, const int64_t* labels, int n, float score_min, float dx, float dy,
+                            float* out_boxes, float* out_scores, int32_t* out_labels, int32_t* offset, int capacity,
+                            edtr_stream_t stream);
+#define EDTR_BOX_SHIFT 1
+#define EDTR_BOX_MUL 2
+#define EDTR_BOX_DIV 4
+#define EDTR_BOX_CLIP 8
+/* dst = src with, in this order and each only under its flag: x += dx, y += dy; x *= fx, y *= fy (or x /= fx, y /= fy); x clamped to
+ * [0, clip_w], y to [0, clip_h].  dst may be src.  Unknown flag bits, or MUL and DIV together: EDTR_E_DTYPE.
+ * replaces: move_boxes, resize_boxes (model/faster_rcnn.py:2558-2571), boxes /= scale (demo.py:135), clip_boxes_to_image. */
+int edtr_boxes_transform(const float* src, float* dst, int n, int flags, float dx, float dy, float fx, float fy, float clip_w,
+                         float clip_h, edtr_stream_t stream);
+/* F.interpolate(scale_factor=s, mode="bilinear", align_corners=False) of fp32 [planes][ih][iw] -> [planes][oh][ow]: the source
+ * coordinate of output o is max(fma(rscale, o + 0.5, -0.5), 0) with rscale = fp32(1 / s) — torch's rule when a scale factor is given,
+ * where edtr_degrade_resize uses in / out — and the caller's oh = floor(ih s), ow = floor(iw s).  The product and the sum of the
+ * coordinate are ONE rounding, as in torch's builds, which contract them; the weights and the four products are those of
+ * edtr_degrade_resize's bilinear mode, each rounded.  rscale_h / rscale_w not positive: EDTR_E_SHAPE.
+ * replaces: demo.py:132. */
+int edtr_boxes_bilinear_scale(const float* src, float* dst, int planes, int ih, int iw, int oh, int ow, float rscale_h, float rscale_w,
+                              edtr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * hipGraph capture of a launch sequence issued on `stream` (one denoise step, or a whole batch).
  * ---------------------------------------------------------------------------------------- */
