@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -10,11 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libedtr_hip.so")
 SOURCES = ["igemm.hip", "halo512.hip", "attention.hip", "attn512.hip", "norm.hip", "elementwise.hip", "swin.hip", "ffn.hip", "lin320.hip", "rng.hip", "imageio.hip", "degrade.hip", "degrade2.hip", "labels.hip", "boxes.hip"]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(os.path.dirname(HERE), "include", "edtr_hip.h")]
-# files #include'd by one source only (generated code): a regenerated .inc must rebuild its object
-EXTRA_DEPS = {"attention.hip": [os.path.join(CSRC, "attn_v3_loop.inc")],
-              "elementwise.hip": [os.path.join(CSRC, "noise_elem.h")], "rng.hip": [os.path.join(CSRC, "noise_elem.h"), os.path.join(CSRC, "philox.h")],
-              "degrade.hip": [os.path.join(CSRC, "philox.h")], "degrade2.hip": [os.path.join(CSRC, "philox.h")]}
+INCLUDE = os.path.join(os.path.dirname(HERE), "include")
+ABI_HEADER = os.path.join(INCLUDE, "edtr_hip.h")
 ARCH = "gfx950"
 
 
@@ -23,6 +21,37 @@ def _hipcc() -> str:
         if cand and os.path.exists(cand):
             return cand
     raise RuntimeError("hipcc not found (needed to build libedtr_hip.so)")
+
+
+_INCLUDE_LINE = re.compile(r'^[ \t]*#[ \t]*include[ \t]+(?:"([^"]+)"|([A-Za-z_]\w*))', re.M)
+
+
+def object_deps(src: str) -> list:
+    """The files the object of csrc/``src`` is compiled from, the source first: its quoted #include lines followed through csrc/ and
+    include/ (depth first, in the order of the lines, each file once), so that a header can never be forgotten in a hand-kept table.
+    `#include NAME` takes the file of the `#define NAME "file"` next to it (a regenerated .inc must rebuild its object).  A quoted
+    include that is no file of these two directories is an error; <system> headers belong to the toolchain."""
+    deps: list = []
+
+    def visit(path):
+        path = os.path.normpath(path)
+        if path in deps:
+            return
+        if os.path.dirname(path) not in (CSRC, INCLUDE) or not os.path.isfile(path):
+            raise RuntimeError(f"{src}: #include of {path}, which is no file of csrc/ or include/")
+        deps.append(path)
+        with open(path) as fh:
+            text = fh.read()
+        for quoted, macro in _INCLUDE_LINE.findall(text):
+            if macro:
+                default = re.search(r'^[ \t]*#[ \t]*define[ \t]+%s[ \t]+"([^"]+)"' % macro, text, re.M)
+                if not default:
+                    raise RuntimeError(f"{os.path.basename(path)}: #include {macro} without a #define {macro} \"file\"")
+                quoted = default.group(1)
+            visit(os.path.join(os.path.dirname(path), quoted))
+
+    visit(os.path.join(CSRC, src))
+    return deps
 
 
 def _stale(target: str, deps) -> bool:
@@ -38,7 +67,7 @@ def source_hash() -> str:
     import hashlib
     h = hashlib.sha1()
     files = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".inc", ".h")))
-    for path in [os.path.join(CSRC, f) for f in files] + [HEADERS[1]]:
+    for path in [os.path.join(CSRC, f) for f in files] + [ABI_HEADER]:
         with open(path, "rb") as fh:
             h.update(os.path.basename(path).encode() + b"\0" + fh.read())
     return h.hexdigest()[:12]
@@ -68,7 +97,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
         # -Werror=pass-failed: a `#pragma unroll` the optimizer could not honour is an ERROR — in round 4 such a loop around the
         # shared epilogue silently stayed rolled and sent a kernel's accumulators through scratch memory
         flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Werror=pass-failed"]
-        key = _object_key(flags, [s] + HEADERS + EXTRA_DEPS.get(src, []))
+        key = _object_key(flags, object_deps(src))
         keyfile = o + ".key"
         have = open(keyfile).read().strip() if os.path.exists(keyfile) and os.path.exists(o) else ""
         if force or have != key:

@@ -6,6 +6,7 @@
 // contraction switched off, so numpy repeats the launches bit for bit — all but expf, which the softmax and the decoding call.
 // No launch waits on another workgroup: dependent phases are separate launches, and nothing here uses an atomic.
 #include "common.h"
+#include "glue.h"
 
 #pragma clang fp contract(off)
 
@@ -14,16 +15,6 @@ namespace {
 constexpr int kMaxBoxes = 32768;            // n of edtr_boxes_nms (EDTR_NMS_MAX_BOXES): 512 mask words per row, 4 KiB of LDS in the scan
 constexpr int kLimit = 1 << 24;
 
-inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-inline unsigned blocks_for(int64_t n) {
-    int64_t b = (n + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
-
-__device__ __forceinline__ float mul_rn(float a, float b) { return a * b; }
-__device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
-__device__ __forceinline__ float div_rn(float a, float b) { return a / b; }     // IEEE: hipcc's fp32 division is correctly rounded
 __device__ __forceinline__ float larger(float a, float b) { return a > b ? a : b; }        // b where either is NaN
 __device__ __forceinline__ float smaller(float a, float b) { return a < b ? a : b; }
 
@@ -66,9 +57,6 @@ __global__ void __launch_bounds__(256) nms_rank_kernel(const float* scores, int 
     if (i < n && rank < n) order[rank] = i;
 }
 
-// (the rank launch writes a permutation of 0 .. n - 1; an index is forced inside all the same, so that no input can make a load stray)
-__device__ __forceinline__ int inside(int idx, int n) { return idx < 0 ? 0 : (idx > n - 1 ? n - 1 : idx); }
-
 __device__ __forceinline__ int64_t label_of(const void* labels, int labels_i64, int idx) {
     if (!labels) return 0;
     return labels_i64 ? static_cast<const int64_t*>(labels)[idx] : (int64_t) static_cast<const int32_t*>(labels)[idx];
@@ -76,7 +64,8 @@ __device__ __forceinline__ int64_t label_of(const void* labels, int labels_i64, 
 
 // Workgroup (cb, rb), one wave: the block of rank-ordered rows 64 rb .. and rank-ordered columns 64 cb ..; blocks below the diagonal
 // leave at once.  Lane r builds the 64-bit word of row 64 rb + r: bit c set iff column 64 cb + c comes later in the order, has the
-// same label and inter / (area_r + area_c - inter) > thr.
+// same label and inter / (area_r + area_c - inter) > thr.  (The rank launch writes a permutation of 0 .. n - 1; an index is forced inside
+// all the same, clamp_index, so that no input can make a load stray.)
 __global__ void __launch_bounds__(64) nms_mask_kernel(const float* boxes, const void* labels, int labels_i64, const int32_t* order, int n,
                                                       int words, float thr, uint64_t* mask) {
     const int cb = (int)blockIdx.x, rb = (int)blockIdx.y, lane = (int)threadIdx.x;
@@ -88,7 +77,7 @@ __global__ void __launch_bounds__(64) nms_mask_kernel(const float* boxes, const 
     f32x4 b = {0.0f, 0.0f, 0.0f, 0.0f};
     int64_t lab = 0;
     if (cj < n) {
-        const int idx = inside(order[cj], n);
+        const int idx = clamp_index(order[cj], n);
         b = *reinterpret_cast<const f32x4*>(boxes + 4 * (int64_t)idx);
         lab = label_of(labels, labels_i64, idx);
     }
@@ -101,7 +90,7 @@ __global__ void __launch_bounds__(64) nms_mask_kernel(const float* boxes, const 
     f32x4 rbx = b;
     int64_t rl = lab;
     if (rb != cb) {
-        const int idx = inside(order[ri], n);
+        const int idx = clamp_index(order[ri], n);
         rbx = *reinterpret_cast<const f32x4*>(boxes + 4 * (int64_t)idx);
         rl = label_of(labels, labels_i64, idx);
     }
@@ -337,13 +326,6 @@ __global__ void __launch_bounds__(256) box_transform_kernel(const float* src, fl
     }
 }
 
-// ATen's guard_index_and_lambda: idx = min(floor(src), n - 1), t = clamp(src - idx, 0, 1)
-__device__ __forceinline__ void index_lambda(float src, int n, int& idx, float& t) {
-    const int f = (int)floorf(src);
-    idx = f < n - 1 ? f : n - 1;
-    t = fminf(fmaxf(add_rn(src, -(float)idx), 0.0f), 1.0f);
-}
-
 // F.interpolate(scale_factor=, mode="bilinear", align_corners=False): one lane per output element; the source coordinate is
 // max(fma(rscale, dst + 0.5, -0.5), 0) with rscale = fp32(1 / scale_factor) handed in by the caller.  The fma is torch's: its
 // builds contract area_pixel_compute_source_index, and with two roundings there the weights come out up to 2e-6 away from torch's.
@@ -359,13 +341,7 @@ __global__ void __launch_bounds__(256) bilinear_scale_kernel(const float* x, flo
         index_lambda(fmaxf(__builtin_fmaf(rh, add_rn((float)oy, 0.5f), -0.5f), 0.0f), ih, y0, ty);
         index_lambda(fmaxf(__builtin_fmaf(rw, add_rn((float)ox, 0.5f), -0.5f), 0.0f), iw, x0, tx);
         y0 = y0 < 0 ? 0 : y0, x0 = x0 < 0 ? 0 : x0;
-        const int y1 = y0 + (y0 < ih - 1 ? 1 : 0), x1 = x0 + (x0 < iw - 1 ? 1 : 0);
-        const float wy0 = add_rn(1.0f, -ty), wx0 = add_rn(1.0f, -tx);
-        const float* r0 = src + (int64_t)y0 * iw;
-        const float* r1 = src + (int64_t)y1 * iw;
-        const float top = add_rn(mul_rn(wx0, r0[x0]), mul_rn(tx, r0[x1]));
-        const float bot = add_rn(mul_rn(wx0, r1[x0]), mul_rn(tx, r1[x1]));
-        out[e] = add_rn(mul_rn(wy0, top), mul_rn(ty, bot));
+        out[e] = bilinear_blend(src, ih, iw, y0, ty, x0, tx);
     }
 }
 

@@ -1,39 +1,22 @@
 // Low-quality inputs from high-quality ones (edtr_hip.h "Low-quality inputs"; the host restatements are edtr_amd/degrade.py): the
 // blur -> resize -> Gaussian noise -> JPEG chain of the reference's degradation, one launch each, on fp32 NCHW batches [B][3][H][W].
 // Every product, sum and quotient that decides a result bit is a correctly rounded fp32 operation in a stated order (mul_rn / add_rn
-// / div_rn below, compiled with contraction switched off), so numpy repeats each kernel bit for bit.  No MFMA: the blur and the
+// / div_rn of glue.h, compiled with contraction switched off), so numpy repeats each kernel bit for bit.  No MFMA: the blur and the
 // JPEG transform live in LDS, the resize and the noise are streaming kernels.
 #include "common.h"
+#include "glue.h"
 #include "philox.h"
 
-// File scope: no product below is fused into a sum.  (HIP's own mul_rn-style intrinsics are plain operators compiled under the
-// default -ffp-contract=fast, so a product and a sum written with them may still become one FMA; these three may not.)
+// File scope: no product below is fused into a sum, whatever it is written with.
 #pragma clang fp contract(off)
 
 namespace {
-
-__device__ __forceinline__ float mul_rn(float a, float b) { return a * b; }
-__device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
-__device__ __forceinline__ float div_rn(float a, float b) { return a / b; }     // IEEE: hipcc's fp32 division is correctly rounded
 
 constexpr int kFilterTile = 32;             // output tile edge of the blur: 256 lanes x 4 rows
 constexpr int kFilterKMin = 3, kFilterKMax = 41;
 constexpr int kDctPitch = 65;               // LDS row pitch of the 64 x 64 DCT table: row reads and column reads both hit 32 banks
 
-inline unsigned blocks_for(int64_t n) {
-    int64_t b = (n + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
-
 // ---- filter2D --------------------------------------------------------------------------------------------------------------------
-
-// F.pad(mode="reflect") index: the edge sample is not repeated.  One reflection is enough for k / 2 < n; the final clamp only serves
-// halo positions that belong to outputs outside the image (partial tiles), which are never stored.
-__device__ __forceinline__ int reflect(int i, int n) {
-    i = i < 0 ? -i : i;
-    i = i >= n ? 2 * (n - 1) - i : i;
-    return i < 0 ? 0 : (i >= n ? n - 1 : i);
-}
 
 // workgroup (tile, channel, image): the 32 x 32 output tile's input patch with its halo, (32 + k - 1)^2 floats, and the image's k x k
 // taps are staged in LDS once; lane (tx, ty) owns output rows ty, ty + 8, ty + 16, ty + 24 of column tx.  Per tap one broadcast read
@@ -85,13 +68,6 @@ __device__ __forceinline__ float source_index(float scale, int dst) {
     return add_rn(mul_rn(scale, add_rn((float)dst, 0.5f)), -0.5f);
 }
 
-// ATen's guard_index_and_lambda: idx = min(floor(src), n - 1), t = clamp(src - idx, 0, 1)
-__device__ __forceinline__ void index_lambda(float src, int n, int& idx, float& t) {
-    const int f = (int)floorf(src);
-    idx = f < n - 1 ? f : n - 1;
-    t = fminf(fmaxf(add_rn(src, -(float)idx), 0.0f), 1.0f);
-}
-
 // the cubic convolution weights for A = -0.75 (A + 2 = 1.25, A + 3 = 2.25, 5 A = -3.75, 8 A = -6, 4 A = -3: all exact)
 __device__ __forceinline__ float cubic1(float v) {      // |v| <= 1: ((A + 2) v - (A + 3)) v v + 1
     return add_rn(mul_rn(mul_rn(add_rn(mul_rn(1.25f, v), -2.25f), v), v), 1.0f);
@@ -106,7 +82,6 @@ __device__ __forceinline__ void cubic_weights(float t, float (&w)[4]) {
     w[2] = cubic1(u);
     w[3] = cubic2(add_rn(u, 1.0f));
 }
-__device__ __forceinline__ int clampi(int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); }
 
 // one lane per output element of planes x oh x ow; MODE = EDTR_RESIZE_*
 template <int MODE>
@@ -123,13 +98,7 @@ __global__ void __launch_bounds__(256) resize_kernel(const float* x, float* out,
             float ty, tx;
             index_lambda(fmaxf(source_index(sh, oy), 0.0f), ih, y0, ty);
             index_lambda(fmaxf(source_index(sw, ox), 0.0f), iw, x0, tx);
-            const int y1 = y0 + (y0 < ih - 1 ? 1 : 0), x1 = x0 + (x0 < iw - 1 ? 1 : 0);
-            const float wy0 = add_rn(1.0f, -ty), wx0 = add_rn(1.0f, -tx);
-            const float* r0 = src + (int64_t)y0 * iw;
-            const float* r1 = src + (int64_t)y1 * iw;
-            const float top = add_rn(mul_rn(wx0, r0[x0]), mul_rn(tx, r0[x1]));
-            const float bot = add_rn(mul_rn(wx0, r1[x0]), mul_rn(tx, r1[x1]));
-            v = add_rn(mul_rn(wy0, top), mul_rn(ty, bot));
+            v = bilinear_blend(src, ih, iw, y0, ty, x0, tx);
         } else if (MODE == EDTR_RESIZE_BICUBIC) {
             int y0, x0;
             float ty, tx, wy[4], wx[4];
@@ -137,11 +106,11 @@ __global__ void __launch_bounds__(256) resize_kernel(const float* x, float* out,
             index_lambda(source_index(sw, ox), iw, x0, tx);
             cubic_weights(ty, wy);
             cubic_weights(tx, wx);
-            const int c0 = clampi(x0 - 1, iw), c1 = clampi(x0, iw), c2 = clampi(x0 + 1, iw), c3 = clampi(x0 + 2, iw);
+            const int c0 = clamp_index(x0 - 1, iw), c1 = clamp_index(x0, iw), c2 = clamp_index(x0 + 1, iw), c3 = clamp_index(x0 + 2, iw);
             v = 0.0f;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float* r = src + (int64_t)clampi(y0 - 1 + i, ih) * iw;
+                const float* r = src + (int64_t)clamp_index(y0 - 1 + i, ih) * iw;
                 float s = mul_rn(wx[0], r[c0]);
                 s = add_rn(s, mul_rn(wx[1], r[c1]));
                 s = add_rn(s, mul_rn(wx[2], r[c2]));
@@ -164,17 +133,9 @@ __global__ void __launch_bounds__(256) resize_kernel(const float* x, float* out,
 
 // ---- Gaussian noise from the seeded stream -------------------------------------------------------------------------------------------
 
-struct NoiseArgs {
-    uint32_t k0, k1;
-    const int64_t* ids;     // [B] global image ids, or NULL: id_base + b
-    uint32_t id_base, draw;
-    int64_t plane4;         // H W / 4: groups of four elements per plane
-    int rounds;
-};
-
 __device__ __forceinline__ float noisy(float xv, float z, float sigma, int rounds) {
     const float o = add_rn(xv, div_rn(mul_rn(z, sigma), 255.0f));
-    if (rounds) return div_rn(fminf(fmaxf(rintf(mul_rn(o, 255.0f)), 0.0f), 255.0f), 255.0f);
+    if (rounds) return round_to_levels(o);
     return fminf(fmaxf(o, 0.0f), 1.0f);
 }
 
@@ -188,7 +149,7 @@ __global__ void __launch_bounds__(256) noise_kernel(const float* x, float* out, 
         int64_t eg = g - b * per4;
         const bool grey = gray[b] != 0;
         if (grey) eg %= a.plane4;
-        const uint32_t id = a.ids ? (uint32_t)a.ids[b] : a.id_base + (uint32_t)b;
+        const uint32_t id = EDTR_IMAGE_ID(a, b);
         const f32x4 z = philox_normal4(a.k0, a.k1, (uint32_t)eg, a.draw, grey ? EDTR_NOISE_DEGRADE_GRAY : EDTR_NOISE_DEGRADE, id);
         const float s = sigma[b];
         const f32x4 xv = *reinterpret_cast<const f32x4*>(x + g * 4);
@@ -296,15 +257,6 @@ __global__ void __launch_bounds__(256) jpeg_kernel(const float* x, float* out, i
     }
 }
 
-int check_batch(const void* x, const void* out, int B, int channels, int H, int W) {
-    if (channels != 3) return EDTR_E_UNSUPPORTED;
-    if (!x || !out) return EDTR_E_NULL;
-    if (B <= 0 || B > 65535 || H <= 0 || W <= 0) return EDTR_E_SHAPE;
-    if (H > (1 << 24) || W > (1 << 24)) return EDTR_E_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 3u) return EDTR_E_ALIGN;
-    return EDTR_OK;
-}
-
 }  // namespace
 
 extern "C" int edtr_degrade_filter2d(const float* x, float* out, int B, int channels, int H, int W, const float* kernels,
@@ -315,7 +267,7 @@ extern "C" int edtr_degrade_filter2d(const float* x, float* out, int B, int chan
     if (k < kFilterKMin || k > kFilterKMax || !(k & 1)) return EDTR_E_SHAPE;
     if (k / 2 >= (H < W ? H : W)) return EDTR_E_SHAPE;              // reflect padding needs the mirrored samples to exist
     if (n_kernels != 1 && n_kernels != B) return EDTR_E_SHAPE;
-    if (reinterpret_cast<uintptr_t>(kernels) & 3u) return EDTR_E_ALIGN;
+    if (!aligned_to(kernels, 4)) return EDTR_E_ALIGN;
     const int tiles_x = (W + kFilterTile - 1) / kFilterTile, tiles_y = (H + kFilterTile - 1) / kFilterTile;
     if ((int64_t)tiles_x * tiles_y > 0x7fffffff) return EDTR_E_UNSUPPORTED;
     const int tw = kFilterTile + k - 1;
@@ -353,27 +305,9 @@ extern "C" int edtr_degrade_gaussian_noise(const float* x, float* out, float* no
                                            edtr_stream_t stream) {
     if (int rc = check_batch(x, out, B, channels, H, W)) return rc;
     if (!sigma_host || !sigma || !gray_host || !gray) return EDTR_E_NULL;
-    if (rounds != 0 && rounds != 1) return EDTR_E_DTYPE;
-    if (draw < 0 || draw >= (int64_t)1 << 32) return EDTR_E_SHAPE;
-    const int64_t hw = (int64_t)H * W;
-    if (hw & 3) return EDTR_E_ALIGN;                                // per_image = 3 H W (colour) or H W (grey), both multiples of 4
-    if (hw > (int64_t)1 << 32) return EDTR_E_UNSUPPORTED;           // e >> 2 is one 32-bit counter word
-    for (int b = 0; b < B; ++b) {
-        if (!(sigma_host[b] >= 0.0f) || sigma_host[b] > 3.0e38f) return EDTR_E_SHAPE;
-        if (gray_host[b] != 0 && gray_host[b] != 1) return EDTR_E_DTYPE;
-    }
-    if (reinterpret_cast<uintptr_t>(image_ids) & 7u) return EDTR_E_ALIGN;
-    if (!image_ids && (image_id_base < 0 || image_id_base + B > (int64_t)1 << 32)) return EDTR_E_SHAPE;
-    if (!aligned16(x) || !aligned16(out) || !aligned16(noise_out)) return EDTR_E_ALIGN;
-    if ((reinterpret_cast<uintptr_t>(sigma) | reinterpret_cast<uintptr_t>(gray)) & 3u) return EDTR_E_ALIGN;
     NoiseArgs a;
-    a.k0 = (uint32_t)(seed & 0xffffffffu);
-    a.k1 = (uint32_t)(seed >> 32);
-    a.ids = image_ids;
-    a.id_base = (uint32_t)image_id_base;
-    a.draw = (uint32_t)draw;
-    a.plane4 = hw >> 2;
-    a.rounds = rounds;
+    if (int rc = make_noise_args(a, x, out, noise_out, B, H, W, sigma_host, gray_host, seed, image_ids, image_id_base, draw, rounds)) return rc;
+    if (!all_aligned_to(4, sigma, gray)) return EDTR_E_ALIGN;
     const int64_t n4 = (int64_t)B * 3 * a.plane4;
     hipLaunchKernelGGL(noise_kernel, dim3(blocks_for(n4)), dim3(256), 0, static_cast<hipStream_t>(stream), x, out, noise_out, sigma,
                        gray, a, n4);
@@ -387,7 +321,7 @@ extern "C" int edtr_degrade_jpeg(const float* x, float* out, int B, int channels
     if (!quality_host || !factor || !dct) return EDTR_E_NULL;
     for (int b = 0; b < B; ++b)
         if (!(quality_host[b] > 0.0f) || !(quality_host[b] <= 100.0f)) return EDTR_E_SHAPE;
-    if ((reinterpret_cast<uintptr_t>(factor) | reinterpret_cast<uintptr_t>(dct) | reinterpret_cast<uintptr_t>(coefs)) & 3u) return EDTR_E_ALIGN;
+    if (!all_aligned_to(4, factor, dct, coefs)) return EDTR_E_ALIGN;
     const int64_t mcus = (int64_t)((H + 15) / 16) * ((W + 15) / 16);
     if (mcus > 0x7fffffff) return EDTR_E_UNSUPPORTED;
     const unsigned gx = (unsigned)(mcus < 256 ? mcus : 256);        // a workgroup stages the 16 KB table once for the MCUs it walks

@@ -3,33 +3,17 @@
 // The rule of degrade.hip holds: every product, sum and quotient that decides a result bit is a correctly rounded fp32 operation in
 // a stated order (compiled with contraction switched off) or integer arithmetic, so numpy repeats each kernel bit for bit.
 #include "common.h"
+#include "glue.h"
 #include "philox.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-__device__ __forceinline__ float mul_rn(float a, float b) { return a * b; }
-__device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
-__device__ __forceinline__ float div_rn(float a, float b) { return a / b; }
-
 constexpr int kSepTile = 32;                // output tile edge of the separable blur: 256 lanes x 4 rows
 constexpr int kSepKMin = 3, kSepKMax = 63;
 constexpr int kMidPitch = 32;               // row pitch of the rows-pass intermediate (see sepblur_kernel)
 constexpr int kLevelWords = 16;             // presence bitmap of an image: words 0..7 colour levels, 8..15 grey levels
-
-inline unsigned blocks_for(int64_t n) {
-    int64_t b = (n + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
-
-// F.pad(mode="reflect") index, as in degrade.hip: one reflection is enough for k / 2 < n; the clamp only serves halo positions of
-// outputs outside the image, which are never stored
-__device__ __forceinline__ int reflect(int i, int n) {
-    i = i < 0 ? -i : i;
-    i = i >= n ? 2 * (n - 1) - i : i;
-    return i < 0 ? 0 : (i >= n ? n - 1 : i);
-}
 
 // ---- separable blur ---------------------------------------------------------------------------------------------------------------
 
@@ -102,7 +86,7 @@ __global__ void __launch_bounds__(256) usm_apply_kernel(const float* x, const fl
 
 // ---- Poisson noise ------------------------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ int level_of(float v) { return (int)fminf(fmaxf(rintf(mul_rn(v, 255.0f)), 0.0f), 255.0f); }
+__device__ __forceinline__ int level_of(float v) { return (int)level8(v); }
 // torchvision's rgb_to_grayscale: (0.2989 r + 0.587 g) + 0.114 b
 __device__ __forceinline__ float grey_of(float r, float g, float b) {
     return add_rn(add_rn(mul_rn(0.2989f, r), mul_rn(0.587f, g)), mul_rn(0.114f, b));
@@ -137,14 +121,6 @@ __global__ void __launch_bounds__(256) levels_kernel(const float* x, uint32_t* l
     if (threadIdx.x < kLevelWords && bits[threadIdx.x]) atomicOr(levels + (int64_t)blockIdx.y * kLevelWords + threadIdx.x, bits[threadIdx.x]);
 }
 
-struct PoissonArgs {
-    uint32_t k0, k1;
-    const int64_t* ids;
-    uint32_t id_base, draw;
-    int64_t plane4;
-    int rounds;
-};
-
 // n = lo + #{ j < 255 : row[j] <= u }: eight steps over the non-decreasing row, the last index read is 254
 __device__ __forceinline__ int invert(const uint32_t* row, int lo, uint32_t u) {
     int pos = 0;
@@ -159,7 +135,7 @@ __device__ __forceinline__ int invert(const uint32_t* row, int lo, uint32_t u) {
 // grey plane, so the three channels of a pixel receive the same noise.
 __global__ void __launch_bounds__(256) poisson_kernel(const float* x, float* out, float* noise_out, const float* scale, const int32_t* gray,
                                                       const uint32_t* levels, const uint32_t* tables, const int32_t* lows, int32_t* counts_out,
-                                                      PoissonArgs a, int64_t n4) {
+                                                      NoiseArgs a, int64_t n4) {
     const int64_t per4 = 3 * a.plane4;
     for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n4; g += (int64_t)gridDim.x * 256) {
         const int64_t b = g / per4;
@@ -191,7 +167,7 @@ __global__ void __launch_bounds__(256) poisson_kernel(const float* x, float* out
             const f32x4 bb = *reinterpret_cast<const f32x4*>(img + (2 * a.plane4 + eg) * 4);
             src = f32x4{grey_of(r.x, gg.x, bb.x), grey_of(r.y, gg.y, bb.y), grey_of(r.z, gg.z, bb.z), grey_of(r.w, gg.w, bb.w)};
         }
-        const uint32_t id = a.ids ? (uint32_t)a.ids[b] : a.id_base + (uint32_t)b;
+        const uint32_t id = EDTR_IMAGE_ID(a, b);
         const u32x4 w = philox4x32_10(u32x4{(uint32_t)eg, a.draw, grey ? (uint32_t)EDTR_NOISE_DEGRADE_POISSON_GRAY : (uint32_t)EDTR_NOISE_DEGRADE_POISSON, id},
                                       a.k0, a.k1);
         const float s = scale[b];
@@ -205,20 +181,11 @@ __global__ void __launch_bounds__(256) poisson_kernel(const float* x, float* out
             const int n = invert(T + k * 256, lo[k], us[i]);
             nz[i] = add_rn(div_rn((float)n, vals), -q);
             const float o = add_rn(xs[i], mul_rn(nz[i], s));
-            res[i] = a.rounds ? div_rn(fminf(fmaxf(rintf(mul_rn(o, 255.0f)), 0.0f), 255.0f), 255.0f) : fminf(fmaxf(o, 0.0f), 1.0f);
+            res[i] = a.rounds ? round_to_levels(o) : fminf(fmaxf(o, 0.0f), 1.0f);
         }
         if (noise_out) *reinterpret_cast<f32x4*>(noise_out + g * 4) = f32x4{nz[0], nz[1], nz[2], nz[3]};
         *reinterpret_cast<f32x4*>(out + g * 4) = f32x4{res[0], res[1], res[2], res[3]};
     }
-}
-
-int check_batch(const void* x, const void* out, int B, int channels, int H, int W) {
-    if (channels != 3) return EDTR_E_UNSUPPORTED;
-    if (!x || !out) return EDTR_E_NULL;
-    if (B <= 0 || B > 65535 || H <= 0 || W <= 0) return EDTR_E_SHAPE;
-    if (H > (1 << 24) || W > (1 << 24)) return EDTR_E_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 3u) return EDTR_E_ALIGN;
-    return EDTR_OK;
 }
 
 }  // namespace
@@ -231,7 +198,7 @@ extern "C" int edtr_degrade_sepblur(const float* x, float* out, float* mask_out,
     if (k < kSepKMin || k > kSepKMax || !(k & 1)) return EDTR_E_SHAPE;
     if (k / 2 >= (H < W ? H : W)) return EDTR_E_SHAPE;
     if (mask_out && !(threshold == threshold)) return EDTR_E_SHAPE;
-    if ((reinterpret_cast<uintptr_t>(taps) | reinterpret_cast<uintptr_t>(mask_out)) & 3u) return EDTR_E_ALIGN;
+    if (!all_aligned_to(4, taps, mask_out)) return EDTR_E_ALIGN;
     const int tiles_x = (W + kSepTile - 1) / kSepTile, tiles_y = (H + kSepTile - 1) / kSepTile;
     if ((int64_t)tiles_x * tiles_y > 0x7fffffff) return EDTR_E_UNSUPPORTED;
     const int th = kSepTile + k - 1;
@@ -247,7 +214,7 @@ extern "C" int edtr_degrade_usm_apply(const float* x, const float* blur, const f
     if (int rc = check_batch(x, out, B, channels, H, W)) return rc;
     if (!blur || !soft) return EDTR_E_NULL;
     if (!(weight == weight) || weight > 3.0e38f || weight < -3.0e38f) return EDTR_E_SHAPE;
-    if ((reinterpret_cast<uintptr_t>(blur) | reinterpret_cast<uintptr_t>(soft)) & 3u) return EDTR_E_ALIGN;
+    if (!all_aligned_to(4, blur, soft)) return EDTR_E_ALIGN;
     const int64_t n = (int64_t)B * 3 * H * W;
     hipLaunchKernelGGL(usm_apply_kernel, dim3(blocks_for(n)), dim3(256), 0, static_cast<hipStream_t>(stream), x, blur, soft, out, weight, n);
     EDTR_LAUNCH_CHECK();
@@ -260,38 +227,19 @@ extern "C" int edtr_degrade_poisson_noise(const float* x, float* out, float* noi
                                           const int64_t* image_ids, int64_t image_id_base, int64_t draw, int rounds, edtr_stream_t stream) {
     if (int rc = check_batch(x, out, B, channels, H, W)) return rc;
     if (!scale_host || !scale || !gray_host || !gray || !tables || !lows || !levels) return EDTR_E_NULL;
-    if (rounds != 0 && rounds != 1) return EDTR_E_DTYPE;
-    if (draw < 0 || draw >= (int64_t)1 << 32) return EDTR_E_SHAPE;
-    const int64_t hw = (int64_t)H * W;
-    if (hw & 3) return EDTR_E_ALIGN;
-    if (hw > (int64_t)1 << 32) return EDTR_E_UNSUPPORTED;
-    for (int b = 0; b < B; ++b) {
-        if (!(scale_host[b] >= 0.0f) || scale_host[b] > 3.0e38f) return EDTR_E_SHAPE;
-        if (gray_host[b] != 0 && gray_host[b] != 1) return EDTR_E_DTYPE;
-    }
-    if (reinterpret_cast<uintptr_t>(image_ids) & 7u) return EDTR_E_ALIGN;
-    if (!image_ids && (image_id_base < 0 || image_id_base + B > (int64_t)1 << 32)) return EDTR_E_SHAPE;
-    if (!aligned16(x) || !aligned16(out) || !aligned16(noise_out)) return EDTR_E_ALIGN;
-    if ((reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(gray) | reinterpret_cast<uintptr_t>(tables) |
-         reinterpret_cast<uintptr_t>(lows) | reinterpret_cast<uintptr_t>(levels) | reinterpret_cast<uintptr_t>(counts_out)) & 3u)
-        return EDTR_E_ALIGN;
+    NoiseArgs a;
+    if (int rc = make_noise_args(a, x, out, noise_out, B, H, W, scale_host, gray_host, seed, image_ids, image_id_base, draw, rounds)) return rc;
+    if (!all_aligned_to(4, scale, gray, tables, lows, levels, counts_out)) return EDTR_E_ALIGN;
     if (x == out) return EDTR_E_UNSUPPORTED;        // a grey image's lanes read all three channels of a pixel, which another lane writes
     if (static_cast<const void*>(levels) == x || static_cast<const void*>(levels) == out) return EDTR_E_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     uint32_t* lv = reinterpret_cast<uint32_t*>(levels);
     hipLaunchKernelGGL(zero_levels_kernel, dim3((B * kLevelWords + 255) / 256), dim3(256), 0, st, lv, B * kLevelWords);
     EDTR_LAUNCH_CHECK();
+    const int64_t hw = (int64_t)H * W;
     const unsigned per_image = blocks_for(hw) < 64u ? blocks_for(hw) : 64u;
     hipLaunchKernelGGL(levels_kernel, dim3(per_image, B), dim3(256), 0, st, x, lv, hw);
     EDTR_LAUNCH_CHECK();
-    PoissonArgs a;
-    a.k0 = (uint32_t)(seed & 0xffffffffu);
-    a.k1 = (uint32_t)(seed >> 32);
-    a.ids = image_ids;
-    a.id_base = (uint32_t)image_id_base;
-    a.draw = (uint32_t)draw;
-    a.plane4 = hw >> 2;
-    a.rounds = rounds;
     const int64_t n4 = (int64_t)B * 3 * a.plane4;
     hipLaunchKernelGGL(poisson_kernel, dim3(blocks_for(n4)), dim3(256), 0, st, x, out, noise_out, scale, gray, lv, tables, lows, counts_out, a,
                        n4);

@@ -1,5 +1,6 @@
 // Layout conversion and small elementwise kernels (HBM-bound or negligible) + runtime helpers.
 #include "common.h"
+#include "glue.h"
 #include "noise_elem.h"
 #include <string.h>
 #include <algorithm>
@@ -316,11 +317,6 @@ __global__ void __launch_bounds__(256) tile_acc_kernel(const float* tile, const 
     }
 }
 
-inline unsigned blocks_for(int64_t n) {
-    int64_t b = (n + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
-
 }  // namespace
 
 namespace {
@@ -427,7 +423,7 @@ extern "C" int edtr_add_stats(int dtype, const void* a, int lda, const void* b, 
     if (!a || !out || !gn_partial) return EDTR_E_NULL;
     if (dtype != EDTR_BF16 && dtype != EDTR_F16) return EDTR_E_DTYPE;
     if (rows <= 0 || C <= 0 || (slot_rows != 64 && slot_rows != 128) || rows % slot_rows || gn_ld < C) return EDTR_E_SHAPE;
-    if ((C & 31) || (lda & 7) || (ldo & 7) || (b && (ldb & 7)) || !aligned16(a) || (b && !aligned16(b)) || !aligned16(out) || (reinterpret_cast<uintptr_t>(gn_partial) & 7))
+    if ((C & 31) || (lda & 7) || (ldo & 7) || (b && (ldb & 7)) || !aligned16(a) || (b && !aligned16(b)) || !aligned16(out) || !aligned_to(gn_partial, 8))
         return EDTR_E_ALIGN;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)(C / 32), (unsigned)(rows / slot_rows));
@@ -730,8 +726,6 @@ __global__ void __launch_bounds__(256) tile_blend_kernel(const float* __restrict
     }
 }
 
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
 // the table's host copy: n windows of th x tw inside the H x W plane.  *all_wi4: every wi is a multiple of 4.
 int check_windows(const int32_t* t, int n, int th, int tw, int H, int W, bool* all_wi4) {
     bool a = true;
@@ -777,7 +771,7 @@ extern "C" int edtr_tile_gather(const float* src, int B, int C, int H, int W, co
     if (!src || !table_host || !table || !dst) return EDTR_E_NULL;
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || n <= 0 || n > EDTR_TILE_WINDOWS_MAX || th <= 0 || tw <= 0 || th > H || tw > W)
         return EDTR_E_SHAPE;
-    if (!aligned4(src) || !aligned4(dst) || !aligned4(table)) return EDTR_E_ALIGN;
+    if (!all_aligned_to(4, src, dst, table)) return EDTR_E_ALIGN;
     bool all_wi4 = false;
     const int rc = check_windows(table_host, n, th, tw, H, W, &all_wi4);
     if (rc != EDTR_OK) return rc;
@@ -794,7 +788,7 @@ extern "C" int edtr_tile_blend(const float* tiles, const float* wts, const int32
     if (!tiles || !wts || !table_host || !table || !out) return EDTR_E_NULL;
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || n <= 0 || n > EDTR_TILE_WINDOWS_MAX || th <= 0 || tw <= 0 || th > H || tw > W)
         return EDTR_E_SHAPE;
-    if (!aligned4(tiles) || !aligned4(wts) || !aligned4(out) || !aligned4(table)) return EDTR_E_ALIGN;
+    if (!all_aligned_to(4, tiles, wts, out, table)) return EDTR_E_ALIGN;
     bool all_wi4 = false;
     const int rc = check_windows(table_host, n, th, tw, H, W, &all_wi4);
     if (rc != EDTR_OK) return rc;

@@ -4,6 +4,7 @@
 // bytes, three float4 of the planes) and moves them as dwords / float4 wherever the row pitch keeps them aligned, element by
 // element otherwise.  Integer and correctly rounded fp32 / fp64 arithmetic only: every result is a bit-exact function of its inputs.
 #include "common.h"
+#include "glue.h"
 
 namespace {
 
@@ -177,8 +178,9 @@ __global__ void __launch_bounds__(256) ingest_kernel(const void* src_, int h, in
     }
 }
 
-// save_image's quantisation: trunc(clamp(x * 255 + 0.5, 0, 255)), the product and the sum each rounded to fp32 on their own (the
-// __f*_rn forms are never contracted into an FMA).  fmaxf(NaN, 0) = 0: a NaN pixel is written as 0.
+// save_image's quantisation: trunc(clamp(x * 255 + 0.5, 0, 255)), written with HIP's __f*_rn forms and NOT with glue.h's mul_rn /
+// add_rn: as compiled today the product and the sum are one v_fma_f32 (DESIGN.md "glue.h"), and the shared operators would un-fuse
+// it and change output bytes.  fmaxf(NaN, 0) = 0: a NaN pixel is written as 0.
 __device__ __forceinline__ uint32_t quant8(float x) {
     const float t = __fadd_rn(__fmul_rn(x, 255.0f), 0.5f);
     return (uint32_t)fminf(fmaxf(t, 0.0f), 255.0f);
@@ -302,13 +304,6 @@ __global__ void __launch_bounds__(256) sqdiff_finish_kernel(const double* partia
     }
 }
 
-inline unsigned blocks_for(int64_t n) {
-    int64_t b = (n + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
-
-__host__ __device__ inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
 // ---- the ragged batch forms: workgroup column blockIdx.y works on image blockIdx.y of a device array of edtr_image_desc ----------
 // Every choice that a per-image entry point makes on the host (which passes run, the dword forms) is made here per image from its
 // descriptor; it is uniform over a workgroup.  The arithmetic is that of resize_h_kernel / resize_v_kernel / ingest_kernel /
@@ -370,7 +365,7 @@ __global__ void __launch_bounds__(256) resize_h_batch_kernel(const edtr_image_de
     const edtr_image_desc d = descs[blockIdx.y];
     if (!desc_sane(d, tmp_bytes, tmp) || !desc_horiz(d)) return;
     uint8_t* dst = tmp + d.tmp_offset;
-    const bool vec = d.out_w % 4 == 0 && aligned4(dst);
+    const bool vec = d.out_w % 4 == 0 && aligned_to(dst, 4);
     const int groups = (d.out_w + 3) >> 2;
     const int64_t total = (int64_t)d.in_h * groups;
     for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
@@ -397,7 +392,7 @@ __global__ void __launch_bounds__(256) resize_ingest_batch_kernel(const edtr_ima
     const uint8_t* S = desc_horiz(d) ? tmp + d.tmp_offset : d.src;
     const bool vert = desc_vert(d);
     const int h = d.out_h, w = d.out_w, row_bytes = w * 3;
-    const bool vec_src = row_bytes % 4 == 0 && aligned4(S);
+    const bool vec_src = row_bytes % 4 == 0 && aligned_to(S, 4);
     const int groups = (W + 3) >> 2;
     const int64_t total = (int64_t)H * groups, plane = (int64_t)H * W;
     float* slot = batch + (int64_t)d.b * 3 * plane;
@@ -488,7 +483,7 @@ __global__ void __launch_bounds__(256) emit_batch_kernel(const float* batch, int
     const int h = (int)row[1], w = (int)row[2];
     if (off < 0 || off + (int64_t)h * w * 3 > dst_bytes) return;
     uint8_t* out = dst + off;
-    const bool vec_dst = w % 4 == 0 && aligned4(out);
+    const bool vec_dst = w % 4 == 0 && aligned_to(out, 4);
     const int groups = (w + 3) >> 2;
     const int64_t total = (int64_t)h * groups, plane = (int64_t)H * W;
     const float* slot = batch + b * 3 * plane;
@@ -538,9 +533,7 @@ extern "C" int edtr_image_resize_u8(const uint8_t* src, int in_h, int in_w, int 
     if (vert && (!v_bounds || !v_coefs)) return EDTR_E_NULL;
     if ((horiz && h_ksize <= 0) || (vert && v_ksize <= 0)) return EDTR_E_SHAPE;
     if (horiz && vert && !tmp) return EDTR_E_NULL;
-    if ((reinterpret_cast<uintptr_t>(h_bounds) | reinterpret_cast<uintptr_t>(h_coefs) | reinterpret_cast<uintptr_t>(v_bounds) |
-         reinterpret_cast<uintptr_t>(v_coefs)) & 3u)
-        return EDTR_E_ALIGN;
+    if (!all_aligned_to(4, h_bounds, h_coefs, v_bounds, v_coefs)) return EDTR_E_ALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (!horiz && !vert) {
         const hipError_t e = hipMemcpyAsync(dst, src, (size_t)in_h * in_w * 3, hipMemcpyDeviceToDevice, st);
@@ -550,7 +543,7 @@ extern "C" int edtr_image_resize_u8(const uint8_t* src, int in_h, int in_w, int 
     if (horiz) {
         uint8_t* hdst = vert ? tmp : dst;
         const int64_t n = (int64_t)in_h * ((out_w + 3) / 4);
-        if (out_w % 4 == 0 && aligned4(hdst))
+        if (out_w % 4 == 0 && aligned_to(hdst, 4))
             hipLaunchKernelGGL(resize_h_kernel<true>, dim3(blocks_for(n)), dim3(256), 0, st, src, hdst, in_h, in_w, out_w, h_bounds, h_coefs, h_ksize);
         else
             hipLaunchKernelGGL(resize_h_kernel<false>, dim3(blocks_for(n)), dim3(256), 0, st, src, hdst, in_h, in_w, out_w, h_bounds, h_coefs, h_ksize);
@@ -560,7 +553,7 @@ extern "C" int edtr_image_resize_u8(const uint8_t* src, int in_h, int in_w, int 
     if (vert) {
         const int row_bytes = out_w * 3;
         const int64_t n = (int64_t)out_h * ((row_bytes + 3) / 4);
-        if (row_bytes % 4 == 0 && aligned4(vsrc) && aligned4(dst))
+        if (row_bytes % 4 == 0 && aligned_to(vsrc, 4) && aligned_to(dst, 4))
             hipLaunchKernelGGL(resize_v_kernel<true>, dim3(blocks_for(n)), dim3(256), 0, st, vsrc, dst, in_h, out_h, row_bytes, v_bounds, v_coefs, v_ksize);
         else
             hipLaunchKernelGGL(resize_v_kernel<false>, dim3(blocks_for(n)), dim3(256), 0, st, vsrc, dst, in_h, out_h, row_bytes, v_bounds, v_coefs, v_ksize);
@@ -575,11 +568,9 @@ extern "C" int edtr_image_ingest(int src_f32, const void* src, int h, int w, int
     if (!src || !batch || (!src_f32 && !table)) return EDTR_E_NULL;
     if (h <= 0 || w <= 0 || B <= 0 || b < 0 || b >= B || h > H || w > W) return EDTR_E_SHAPE;
     if ((src_f32 != 0 && src_f32 != 1) || (replicate != 0 && replicate != 1)) return EDTR_E_DTYPE;
-    if ((reinterpret_cast<uintptr_t>(batch) & 3u) || (src_f32 && (reinterpret_cast<uintptr_t>(src) & 3u)) ||
-        (reinterpret_cast<uintptr_t>(table) & 3u))
-        return EDTR_E_ALIGN;
+    if (!all_aligned_to(4, batch, table) || (src_f32 && !aligned_to(src, 4))) return EDTR_E_ALIGN;
     float* slot = batch + (int64_t)b * 3 * H * W;
-    const bool vs = w % 4 == 0 && (src_f32 ? aligned16(src) : aligned4(src));
+    const bool vs = w % 4 == 0 && (src_f32 ? aligned16(src) : aligned_to(src, 4));
     const bool vd = W % 4 == 0 && aligned16(slot);
     const dim3 grid(blocks_for((int64_t)H * ((W + 3) / 4))), block(256);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -605,9 +596,9 @@ extern "C" int edtr_image_emit(const float* batch, int b, int B, int channels, i
     if (channels != 3) return EDTR_E_UNSUPPORTED;
     if (!batch || !dst) return EDTR_E_NULL;
     if (h <= 0 || w <= 0 || B <= 0 || b < 0 || b >= B || h > H || w > W) return EDTR_E_SHAPE;
-    if (reinterpret_cast<uintptr_t>(batch) & 3u) return EDTR_E_ALIGN;
+    if (!aligned_to(batch, 4)) return EDTR_E_ALIGN;
     const float* slot = batch + (int64_t)b * 3 * H * W;
-    const bool vs = W % 4 == 0 && aligned16(slot), vd = w % 4 == 0 && aligned4(dst);
+    const bool vs = W % 4 == 0 && aligned16(slot), vd = w % 4 == 0 && aligned_to(dst, 4);
     const dim3 grid(blocks_for((int64_t)h * ((w + 3) / 4))), block(256);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (vs && vd) hipLaunchKernelGGL((emit_kernel<true, true>), grid, block, 0, st, slot, H, W, dst, h, w);
@@ -629,9 +620,7 @@ static int check_descs(const edtr_image_desc* d, int B, const uint8_t* tmp, int6
         if (horiz && (!d[i].h_bounds || !d[i].h_coefs || !tmp)) return EDTR_E_NULL;
         if (vert && (!d[i].v_bounds || !d[i].v_coefs)) return EDTR_E_NULL;
         if ((horiz && d[i].h_ksize <= 0) || (vert && d[i].v_ksize <= 0)) return EDTR_E_SHAPE;
-        if ((reinterpret_cast<uintptr_t>(d[i].h_bounds) | reinterpret_cast<uintptr_t>(d[i].h_coefs) |
-             reinterpret_cast<uintptr_t>(d[i].v_bounds) | reinterpret_cast<uintptr_t>(d[i].v_coefs)) & 3u)
-            return EDTR_E_ALIGN;
+        if (!all_aligned_to(4, d[i].h_bounds, d[i].h_coefs, d[i].v_bounds, d[i].v_coefs)) return EDTR_E_ALIGN;
         if (horiz) {
             const int64_t bytes = (int64_t)d[i].in_h * d[i].out_w * 3;
             if (d[i].tmp_offset < 0 || d[i].tmp_offset + bytes > tmp_bytes) return EDTR_E_SHAPE;
@@ -648,7 +637,7 @@ extern "C" int edtr_image_resize_h_batch(const edtr_image_desc* descs_host, cons
     if (channels != 3) return EDTR_E_UNSUPPORTED;
     if (!descs_host || !descs) return EDTR_E_NULL;
     if (B <= 0 || B > 65535 || tmp_bytes < 0) return EDTR_E_SHAPE;
-    if (reinterpret_cast<uintptr_t>(descs) & 7u) return EDTR_E_ALIGN;
+    if (!aligned_to(descs, 8)) return EDTR_E_ALIGN;
     int64_t groups = 0;
     const int rc = check_descs(descs_host, B, tmp, tmp_bytes, &groups);
     if (rc != EDTR_OK) return rc;
@@ -665,8 +654,7 @@ extern "C" int edtr_image_resize_ingest_batch(const edtr_image_desc* descs_host,
     if (!descs_host || !descs || !batch || !table) return EDTR_E_NULL;
     if (B <= 0 || B > 65535 || slots <= 0 || H <= 0 || W <= 0 || tmp_bytes < 0) return EDTR_E_SHAPE;
     if (replicate != 0 && replicate != 1) return EDTR_E_DTYPE;
-    if ((reinterpret_cast<uintptr_t>(descs) & 7u) || (reinterpret_cast<uintptr_t>(batch) & 3u) || (reinterpret_cast<uintptr_t>(table) & 3u))
-        return EDTR_E_ALIGN;
+    if (!aligned_to(descs, 8) || !all_aligned_to(4, batch, table)) return EDTR_E_ALIGN;
     int64_t groups = 0;
     const int rc = check_descs(descs_host, B, tmp, tmp_bytes, &groups);
     if (rc != EDTR_OK) return rc;
@@ -687,7 +675,7 @@ extern "C" int edtr_image_emit_batch(const float* batch, int B, int channels, in
     if (channels != 3) return EDTR_E_UNSUPPORTED;
     if (!batch || !table_host || !table || !dst) return EDTR_E_NULL;
     if (B <= 0 || n <= 0 || n > 65535 || H <= 0 || W <= 0 || dst_bytes < 0) return EDTR_E_SHAPE;
-    if ((reinterpret_cast<uintptr_t>(batch) & 3u) || (reinterpret_cast<uintptr_t>(table) & 7u)) return EDTR_E_ALIGN;
+    if (!aligned_to(batch, 4) || !aligned_to(table, 8)) return EDTR_E_ALIGN;
     int64_t groups = 0;
     for (int i = 0; i < n; ++i) {
         const int64_t b = table_host[4 * i], h = table_host[4 * i + 1], w = table_host[4 * i + 2], off = table_host[4 * i + 3];
@@ -711,9 +699,7 @@ extern "C" int edtr_image_sqdiff(const float* a, const float* b, int B, int chan
     if (!a || !b || !partials || !out) return EDTR_E_NULL;
     if (B <= 0 || B > 65535 || H <= 0 || W <= 0 || crop_border < 0) return EDTR_E_SHAPE;
     if (y_channel != 0 && y_channel != 1) return EDTR_E_DTYPE;
-    if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(sizes)) & 3u) ||
-        ((reinterpret_cast<uintptr_t>(partials) | reinterpret_cast<uintptr_t>(out)) & 7u))
-        return EDTR_E_ALIGN;
+    if (!all_aligned_to(4, a, b, sizes) || !all_aligned_to(8, partials, out)) return EDTR_E_ALIGN;
     static_assert(kSqBlocks == EDTR_SQDIFF_BLOCKS, "edtr_hip.h and imageio.hip disagree on the partials per image");
     const bool vec = W % 4 == 0 && aligned16(a) && aligned16(b);
     const dim3 grid(kSqBlocks, B), block(256);

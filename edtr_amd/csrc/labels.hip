@@ -4,6 +4,7 @@
 // wherever the row pitch and the base keep them aligned, element by element otherwise.  Integer arithmetic and comparisons only:
 // every result is a bit-exact function of its inputs, whatever the grid.
 #include "common.h"
+#include "glue.h"
 
 namespace {
 
@@ -12,13 +13,6 @@ constexpr int kBins = kMaxClasses * kMaxClasses;
 constexpr int kLimit = 1 << 24;             // extents and origins of the gathers stay below this: every index fits an int
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-inline unsigned blocks_for(int64_t n) {
-    int64_t b = (n + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
-
-inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // four consecutive logits of one plane, widened exactly to fp32.  DT: EDTR_LOGITS_F32 / _F16 / _BF16.  VEC: one 16-byte (fp32) or
 // 8-byte (16-bit) load; else the first `valid` of them one by one (the others are never looked at).
@@ -175,7 +169,7 @@ __device__ __forceinline__ void store4(uint8_t* o, const uint32_t (&p)[4], int v
     }
 }
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }       // (not glue.h's clamp_index: both ends given)
 
 // dst (y, x) = src (y_idx[y], x_idx[x]); the tables are forced inside the source: a wrong one cannot make the kernel read out of bounds
 template <int C, bool VEC>

@@ -16,10 +16,6 @@ struct Stream {          // what does not depend on the element: passed by value
     int64_t groups;      // per_image / 4
 };
 
-__device__ __forceinline__ uint32_t image_id(const Stream& s, int64_t b) {
-    return s.ids ? (uint32_t)s.ids[b] : s.id_base + (uint32_t)b;
-}
-
 // the normals of elements 4 * eg + 0..3 of image `id`
 __device__ __forceinline__ f32x4 normal4(const Stream& s, uint32_t eg, uint32_t draw, uint32_t purpose, uint32_t id) {
     return philox_normal4(s.k0, s.k1, eg, draw, purpose, id);
@@ -31,7 +27,7 @@ __device__ __forceinline__ void st4(float* p, const f32x4& v) { *reinterpret_cas
 __global__ void __launch_bounds__(256) normal_fill_kernel(float* out, Stream s, uint32_t purpose, uint32_t draw, int64_t n4) {
     for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n4; g += (int64_t)gridDim.x * 256) {
         const int64_t b = g / s.groups;
-        st4(out + g * 4, normal4(s, (uint32_t)(g - b * s.groups), draw, purpose, image_id(s, b)));
+        st4(out + g * 4, normal4(s, (uint32_t)(g - b * s.groups), draw, purpose, EDTR_IMAGE_ID(s, b)));
     }
 }
 
@@ -42,7 +38,7 @@ __global__ void __launch_bounds__(256) q_sample_rng_kernel(const float* x, const
         int64_t ti = t[b];
         ti = ti < 0 ? 0 : (ti >= n_tab ? n_tab - 1 : ti);
         const float a = tab_a[ti], bb = tab_b[ti];
-        const f32x4 z = normal4(s, (uint32_t)(g - b * s.groups), 0u, EDTR_NOISE_Q_SAMPLE, image_id(s, b));
+        const f32x4 z = normal4(s, (uint32_t)(g - b * s.groups), 0u, EDTR_NOISE_Q_SAMPLE, EDTR_IMAGE_ID(s, b));
         const f32x4 xv = ld4(x + g * 4);
         st4(out + g * 4, f32x4{q_sample_elem(a, xv.x, bb, z.x), q_sample_elem(a, xv.y, bb, z.y), q_sample_elem(a, xv.z, bb, z.z),
                                q_sample_elem(a, xv.w, bb, z.w)});
@@ -64,7 +60,7 @@ __global__ void __launch_bounds__(256) sampler_update_rng_kernel(const float* x,
             c_recip = c[0], c_recipm1 = c[1], coef1 = c[2], coef2 = c[3], sigma = c[4];
             draw = (uint32_t)k;
         }
-        const f32x4 z = normal4(s, (uint32_t)(g - b * s.groups), draw, EDTR_NOISE_STEP, image_id(s, b));
+        const f32x4 z = normal4(s, (uint32_t)(g - b * s.groups), draw, EDTR_NOISE_STEP, EDTR_IMAGE_ID(s, b));
         const f32x4 xv = ld4(x + g * 4), ev = ld4(eps + g * 4);
         float p0[4], xp[4];
         sampler_update_elem(xv.x, ev.x, z.x, c_recip, c_recipm1, coef1, coef2, sigma, p0[0], xp[0]);
@@ -83,7 +79,7 @@ __global__ void __launch_bounds__(256) gaussian_sample_rng_kernel(const float* m
     for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n4; g += (int64_t)gridDim.x * 256) {
         const int64_t b = g / s.groups;
         const uint32_t eg = (uint32_t)(g - b * s.groups);
-        const f32x4 z = normal4(s, eg, 0u, EDTR_NOISE_VAE, image_id(s, b));
+        const f32x4 z = normal4(s, eg, 0u, EDTR_NOISE_VAE, EDTR_IMAGE_ID(s, b));
         const float zz[4] = {z.x, z.y, z.z, z.w};
         float o[4];
 #pragma unroll
@@ -97,24 +93,13 @@ __global__ void __launch_bounds__(256) gaussian_sample_rng_kernel(const float* m
     }
 }
 
-inline unsigned blocks_for(int64_t n) {
-    int64_t b = (n + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
-
 // the checks every entry shares; fills `s`.  Nothing is launched unless this answers EDTR_OK.
 int make_stream(int B, int64_t per_image, uint64_t seed, const int64_t* image_ids, int64_t image_id_base, Stream& s) {
     if (B <= 0 || per_image <= 0) return EDTR_E_SHAPE;
     if (per_image & 3) return EDTR_E_ALIGN;
     if (per_image > (int64_t)1 << 34) return EDTR_E_UNSUPPORTED;          // e >> 2 is one 32-bit counter word
-    if (reinterpret_cast<uintptr_t>(image_ids) & 7u) return EDTR_E_ALIGN;
-    if (!image_ids && (image_id_base < 0 || image_id_base + B > (int64_t)1 << 32)) return EDTR_E_SHAPE;
-    s.k0 = (uint32_t)(seed & 0xffffffffu);
-    s.k1 = (uint32_t)(seed >> 32);
-    s.ids = image_ids;
-    s.id_base = (uint32_t)image_id_base;
     s.groups = per_image >> 2;
-    return EDTR_OK;
+    return key_stream(s, B, seed, image_ids, image_id_base);
 }
 
 }  // namespace
@@ -123,7 +108,7 @@ extern "C" int edtr_normal_fill(float* out, int B, int64_t per_image, uint64_t s
                                 int64_t image_id_base, int purpose, int64_t draw, edtr_stream_t stream) {
     if (!out) return EDTR_E_NULL;
     if (purpose < EDTR_NOISE_Q_SAMPLE || purpose > EDTR_NOISE_VAE) return EDTR_E_DTYPE;
-    if (draw < 0 || draw >= (int64_t)1 << 32) return EDTR_E_SHAPE;
+    if (!draw_ok(draw)) return EDTR_E_SHAPE;
     Stream s;
     if (int rc = make_stream(B, per_image, seed, image_ids, image_id_base, s)) return rc;
     if (!aligned16(out)) return EDTR_E_ALIGN;
@@ -153,7 +138,7 @@ extern "C" int edtr_sampler_update_rng(const float* x, const float* eps, float c
                                        float sigma, float* x_prev, float* pred_x0, int B, int64_t per_image, uint64_t seed,
                                        const int64_t* image_ids, int64_t image_id_base, int64_t draw, edtr_stream_t stream) {
     if (!x || !eps || !x_prev) return EDTR_E_NULL;
-    if (draw < 0 || draw >= (int64_t)1 << 32) return EDTR_E_SHAPE;
+    if (!draw_ok(draw)) return EDTR_E_SHAPE;
     Stream s;
     if (int rc = make_stream(B, per_image, seed, image_ids, image_id_base, s)) return rc;
     if (!aligned16(x) || !aligned16(eps) || !aligned16(x_prev) || (pred_x0 && !aligned16(pred_x0))) return EDTR_E_ALIGN;

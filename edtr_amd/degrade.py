@@ -1052,16 +1052,15 @@ def degrade2_reference(hq, params: Sequence[Degrade2Params], seed: int, image_id
 # ----------------------------------------------------------------------------------------------------------------------------------
 # device side
 # ----------------------------------------------------------------------------------------------------------------------------------
-_DCT_TABLES: dict = {}
-
-
 def _dct_on(device):
-    import torch
-    from .imageio import _device_key
-    key = _device_key(device)
-    if key not in _DCT_TABLES:
-        _DCT_TABLES[key] = torch.from_numpy(dct_table()).to(device)
-    return _DCT_TABLES[key]
+    from .imageio import on_device
+    return on_device(("dct",), device, dct_table)
+
+
+def _per_image(values, gray, B: int):
+    """one float and one 0 / 1 per image from ``values`` / ``gray`` given per image or once for all"""
+    return ([float(v) for v in np.broadcast_to(np.asarray(values, dtype=np.float64).reshape(-1), (B,))],
+            [int(bool(v)) for v in np.broadcast_to(np.asarray(gray).reshape(-1), (B,))])
 
 
 def _check_device_batch(x, what: str):
@@ -1102,9 +1101,7 @@ def add_gaussian_noise(x, sigma, gray, source, draw: int = 0, rounds: bool = Fal
     import torch
     from . import ops
     _check_device_batch(x, "add_gaussian_noise")
-    B = x.shape[0]
-    sigma = [float(v) for v in np.broadcast_to(np.asarray(sigma, dtype=np.float64).reshape(-1), (B,))]
-    gray = [int(bool(v)) for v in np.broadcast_to(np.asarray(gray).reshape(-1), (B,))]
+    sigma, gray = _per_image(sigma, gray, x.shape[0])
     out = torch.empty_like(x)
     noise = torch.empty_like(x) if return_noise else None
     ops.launch(ops.make_degrade_gaussian_noise(x=x, out=out, noise_out=noise, sigma=sigma, gray=gray, source=source, draw=draw, rounds=rounds))
@@ -1177,18 +1174,15 @@ def degrade_batch(hq, params: Sequence[DegradeParams], seed: int, image_ids: Seq
 # ----------------------------------------------------------------------------------------------------------------------------------
 # second order: device side
 # ----------------------------------------------------------------------------------------------------------------------------------
-_POISSON_ON: dict = {}
+def _poisson_arrays():
+    T, lo = poisson_tables()
+    return T.view(np.int32), lo
 
 
 def poisson_tables_on(device):
     """(uint32-as-int32 [9, 256, 256], int32 [9, 256]) tensors of `poisson_tables` on ``device``: built once, uploaded once per device"""
-    import torch
-    from .imageio import _device_key
-    key = _device_key(device)
-    if key not in _POISSON_ON:
-        T, lo = poisson_tables()
-        _POISSON_ON[key] = (torch.from_numpy(T.view(np.int32)).to(device), torch.from_numpy(lo).to(device))
-    return _POISSON_ON[key]
+    from .imageio import on_device
+    return on_device(("poisson",), device, _poisson_arrays)
 
 
 def add_poisson_noise(x, scale, gray, source, draw: int = 0, rounds: bool = False, return_noise: bool = False, return_counts: bool = False):
@@ -1198,8 +1192,7 @@ def add_poisson_noise(x, scale, gray, source, draw: int = 0, rounds: bool = Fals
     from . import ops
     _check_device_batch(x, "add_poisson_noise")
     B = x.shape[0]
-    scale = [float(v) for v in np.broadcast_to(np.asarray(scale, dtype=np.float64).reshape(-1), (B,))]
-    gray = [int(bool(v)) for v in np.broadcast_to(np.asarray(gray).reshape(-1), (B,))]
+    scale, gray = _per_image(scale, gray, B)
     tables, lows = poisson_tables_on(x.device)
     out = torch.empty_like(x)
     noise = torch.empty_like(x) if return_noise else None

@@ -160,7 +160,7 @@ def plan_buckets(sizes: Sequence[Tuple[int, int]], batch_size: int, min_size: Op
 # ----------------------------------------------------------------------------------------------------------------------------------
 # device side
 # ----------------------------------------------------------------------------------------------------------------------------------
-_INGEST_TABLES: dict = {}               # one 1 KB table per device: kept for good
+_ON_DEVICE: dict = {}                   # family -> {key + device: tensor(s)}: what `on_device` keeps
 _RESIZE_TABLES: OrderedDict = OrderedDict()     # (in, out, device) -> (bounds, coefficients): the RESIZE_TABLES_KEPT most recently used
 RESIZE_TABLES_KEPT = 64
 
@@ -177,12 +177,24 @@ def _device_key(device) -> Tuple[str, int]:
     return d.type, d.index if d.index is not None else (torch.cuda.current_device() if d.type == "cuda" else 0)
 
 
-def _ingest_table(device):
+def on_device(key: tuple, device, build, kept: int = 0):
+    """The device copy of ``build()`` (a numpy array, or a tuple of them -> a tuple of tensors): built once and uploaded once per
+    ``key`` and physical device.  ``key[0]`` names the family of tables; ``kept`` > 0 bounds the family, oldest entry out first.
+    (A table that a queued launch still reads stays valid as long as that launch was queued on the stream the table was allocated
+    on: torch's allocator hands a freed block out again on that stream only, behind the launch.)"""
     import torch
-    key = _device_key(device)
-    if key not in _INGEST_TABLES:
-        _INGEST_TABLES[key] = torch.from_numpy(INGEST_TABLE.copy()).to(device)
-    return _INGEST_TABLES[key]
+    cache = _ON_DEVICE.setdefault(key[0], {})
+    key = key + _device_key(device)
+    if key not in cache:
+        while kept and len(cache) >= kept:
+            cache.pop(next(iter(cache)))
+        made = build()
+        cache[key] = tuple(torch.from_numpy(a).to(device) for a in made) if isinstance(made, tuple) else torch.from_numpy(made).to(device)
+    return cache[key]
+
+
+def _ingest_table(device):
+    return on_device(("ingest",), device, INGEST_TABLE.copy)      # one 1 KB table per device: kept for good
 
 
 def _resize_tables(in_size: int, out_size: int, device):

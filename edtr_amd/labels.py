@@ -310,22 +310,12 @@ def paired_mask_reference(mask_u8, gt_hw, center_crop=None) -> np.ndarray:
 # ----------------------------------------------------------------------------------------------------------------------------------
 # device side
 # ----------------------------------------------------------------------------------------------------------------------------------
-_INDEX_TABLES: dict = {}
-_PALETTES: dict = {}
 INDEX_TABLES_KEPT = 64
 
 
 def _index_on(n_in: int, n_out: int, device):
-    import torch
-    from .imageio import _device_key
-    key = (n_in, n_out) + _device_key(device)
-    if key not in _INDEX_TABLES:
-        while len(_INDEX_TABLES) >= INDEX_TABLES_KEPT:
-            # (a table that a queued launch still reads stays valid as long as that launch was queued on the stream the table was
-            # allocated on: torch's allocator hands a freed block out again on that stream only, behind the launch)
-            _INDEX_TABLES.pop(next(iter(_INDEX_TABLES)))
-        _INDEX_TABLES[key] = torch.from_numpy(nearest_index(n_in, n_out)).to(device)
-    return _INDEX_TABLES[key]
+    from .imageio import on_device
+    return on_device(("nearest_index", n_in, n_out), device, lambda: nearest_index(n_in, n_out), kept=INDEX_TABLES_KEPT)
 
 
 def _on_device(x, device, what: str):
@@ -396,13 +386,10 @@ def confusion(logits, target, n: int = 21, sizes=None, mat=None, return_pred: bo
 
 def _palette_on(palette, device):
     import torch
-    from .imageio import _device_key
+    from .imageio import on_device
     if palette is not None:
         return torch.from_numpy(_palette(palette)).to(device)
-    key = _device_key(device)
-    if key not in _PALETTES:
-        _PALETTES[key] = torch.from_numpy(voc_palette()).to(device)
-    return _PALETTES[key]
+    return on_device(("voc_palette",), device, voc_palette)
 
 
 def colorize(labels, palette=None, device=None):

@@ -791,13 +791,17 @@ def make_degrade_resize(*, x, out, mode: int, name="degrade.resize") -> Rec:
     return Rec(L.load().edtr_degrade_resize, args, (x, out), name, 0.0, 4.0 * (x.numel() + out.numel()))
 
 
+def _host_and_device(values, B: int, ctype, device):
+    """one value per image as the ctypes array an entry point checks and as its copy on ``device`` (the values as the C type holds them)"""
+    host = (ctype * B)(*values)
+    return host, torch.tensor(list(host), dtype=torch.float32 if ctype is ct.c_float else torch.int32).to(device)
+
+
 def make_degrade_gaussian_noise(*, x, out, noise_out, sigma, gray, source, draw: int, rounds: bool, name="degrade.gaussian_noise") -> Rec:
     """``out`` = clamp(``x`` + n * sigma[b] / 255) with n from ``source``'s stream; ``sigma`` / ``gray``: one Python value per image
     (uploaded here, and handed to the entry point as host arrays as well); ``noise_out``: None or a tensor that receives n."""
     B, ch, H, W = x.shape
-    sig_host, gray_host = (ct.c_float * B)(*sigma), (ct.c_int32 * B)(*gray)
-    sig = torch.tensor(list(sig_host), dtype=torch.float32).to(x.device)
-    gry = torch.tensor(list(gray_host), dtype=torch.int32).to(x.device)
+    (sig_host, sig), (gray_host, gry) = _host_and_device(sigma, B, ct.c_float, x.device), _host_and_device(gray, B, ct.c_int32, x.device)
     seed, ids_p, base, ids = _noise_args(source, B, x.device, name)
     args = (ptr(x), ptr(out), ptr(noise_out), B, ch, H, W, sig_host, ptr(sig), gray_host, ptr(gry), seed, ids_p, base, int(draw), int(rounds))
     return Rec(L.load().edtr_degrade_gaussian_noise, args, (x, out, noise_out, sig_host, sig, gray_host, gry, ids), name, 0.0, 8.0 * x.numel())
@@ -819,9 +823,7 @@ def make_degrade_poisson_noise(*, x, out, noise_out, scale, gray, tables, lows, 
     one Python value per image; ``tables`` uint32 [9, 256, 256] / ``lows`` int32 [9, 256]: `degrade.poisson_tables_on(device)`;
     ``levels``: int32 [B, 16] workspace; ``counts_out``: None or int32 [B, 2]; ``noise_out``: None or a tensor that receives the noise."""
     B, ch, H, W = x.shape
-    sc_host, gray_host = (ct.c_float * B)(*scale), (ct.c_int32 * B)(*gray)
-    sc = torch.tensor(list(sc_host), dtype=torch.float32).to(x.device)
-    gry = torch.tensor(list(gray_host), dtype=torch.int32).to(x.device)
+    (sc_host, sc), (gray_host, gry) = _host_and_device(scale, B, ct.c_float, x.device), _host_and_device(gray, B, ct.c_int32, x.device)
     seed, ids_p, base, ids = _noise_args(source, B, x.device, name)
     args = (ptr(x), ptr(out), ptr(noise_out), B, ch, H, W, sc_host, ptr(sc), gray_host, ptr(gry), ptr(tables), ptr(lows), ptr(levels),
             ptr(counts_out), seed, ids_p, base, int(draw), int(rounds))

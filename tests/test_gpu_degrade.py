@@ -196,3 +196,53 @@ def test_degrade_files_writes_the_same_bytes_for_batch_size_1_and_2(tmp_path):
                 assert a.read() == b.read()
         assert same(np.array(Image.open(g1)), np.array(Image.open(p)))
         assert Image.open(l1).size == Image.open(p).size and not same(np.array(Image.open(l1)), np.array(Image.open(p)))
+
+
+def test_bad_arguments_answer_the_documented_codes_and_launch_nothing():
+    """every rejection of the four entry points of csrc/degrade.hip, code by code: one thing changed at a time on a valid call"""
+    L, s = lib.load(), ops.stream_ptr()
+    x = torch.zeros((2, 3, 4, 4), dtype=torch.float32, device=DEV)
+    out, noise_out = torch.full_like(x, 7.0), torch.full_like(x, 7.0)
+    ker = torch.full((2, 3, 3), 1.0 / 9.0, dtype=torch.float32, device=DEV)
+    sig = torch.ones(2, dtype=torch.float32, device=DEV)
+    gry = torch.zeros(2, dtype=torch.int32, device=DEV)
+    ids = torch.zeros(2, dtype=torch.int64, device=DEV)
+    dct = torch.zeros((64, 64), dtype=torch.float32, device=DEV)
+    P = lambda t: t.data_ptr()
+    f32s, i32s = lambda *v: (C.c_float * len(v))(*v), lambda *v: (C.c_int32 * len(v))(*v)
+    E_NULL, E_SHAPE, E_ALIGN, E_DTYPE, E_UNSUPPORTED = -1, -2, -3, -4, -5
+    batch = dict(x=P(x), out=P(out), B=2, channels=3, H=4, W=4)
+    noise = dict(x=P(x), out=P(out), noise_out=P(noise_out), B=2, channels=3, H=4, W=4)
+    valid = {      # the arguments in the order of the entry point (H, W: in_h, in_w of the resize)
+        "filter2d": (L.edtr_degrade_filter2d, dict(batch, kernels=P(ker), n_kernels=2, k=3)),
+        "resize": (L.edtr_degrade_resize, dict(batch, out_h=4, out_w=4, mode=lib.RESIZE_BILINEAR)),
+        "gaussian_noise": (L.edtr_degrade_gaussian_noise, dict(noise, sigma_host=f32s(1.0, 1.0), sigma=P(sig), gray_host=i32s(0, 0), gray=P(gry),
+                                                               seed=1, image_ids=None, image_id_base=0, draw=0, rounds=0)),
+        "jpeg": (L.edtr_degrade_jpeg, dict(batch, quality_host=f32s(50.0, 50.0), factor=P(sig), dct=P(dct), coefs=None)),
+    }
+
+    def code(name, **change):
+        fn, args = valid[name]
+        assert set(change) <= set(args)
+        return fn(*{**args, **change}.values(), s)
+
+    for name in valid:
+        for change, want in ((dict(channels=1), E_UNSUPPORTED), (dict(channels=1, x=None), E_UNSUPPORTED),      # the channel check comes first
+                             (dict(x=None), E_NULL), (dict(out=None), E_NULL), (dict(B=0), E_SHAPE), (dict(B=65536), E_SHAPE),
+                             (dict(H=(1 << 24) + 4), E_UNSUPPORTED), (dict(x=P(x) + 2), E_ALIGN)):
+            assert code(name, **change) == want, (name, change)
+    for change, want in ((dict(sigma_host=None), E_NULL), (dict(rounds=2), E_DTYPE), (dict(rounds=2, draw=-1), E_DTYPE),   # rounds before draw
+                         (dict(draw=-1), E_SHAPE), (dict(draw=1 << 32), E_SHAPE), (dict(H=3, W=3), E_ALIGN),              # H W % 4
+                         (dict(sigma_host=f32s(-1.0, 1.0)), E_SHAPE), (dict(sigma_host=f32s(1.0, float("nan"))), E_SHAPE),
+                         (dict(gray_host=i32s(2, 0)), E_DTYPE), (dict(image_ids=P(ids) + 4), E_ALIGN),
+                         (dict(image_ids=None, image_id_base=(1 << 32) - 1), E_SHAPE),                                   # image_id_base + B > 2^32
+                         (dict(x=P(x) + 4), E_ALIGN)):                                                                    # the 16-byte rule
+        assert code("gaussian_noise", **change) == want, change
+    for change, want in ((dict(k=4), E_SHAPE), (dict(k=43), E_SHAPE), (dict(n_kernels=3), E_SHAPE), (dict(out=P(x)), E_UNSUPPORTED)):
+        assert code("filter2d", **change) == want, change
+    for change, want in ((dict(mode=3), E_DTYPE), (dict(out_h=0), E_SHAPE)):
+        assert code("resize", **change) == want, change
+    for q in (0.0, 101.0):
+        assert code("jpeg", quality_host=f32s(50.0, q)) == E_SHAPE, q
+    torch.cuda.synchronize()
+    assert bool((out == 7.0).all()) and bool((noise_out == 7.0).all()) and bool((x == 0.0).all())      # nothing was launched

@@ -3,6 +3,7 @@ csrc/degrade2.hip is a bit-exact function of its inputs — the Poisson sampler 
 the smallest at which each can still go wrong: reflect borders on all four sides, a halo of 25 (and of 31) against the 32-wide tile and
 partial tiles for the separable blur; 256, 5 and 1 levels, a grey image and the largest image id for the Poisson noise."""
 import copy
+import ctypes as C
 import os
 
 import numpy as np
@@ -158,3 +159,52 @@ def test_degrade_files_writes_the_same_bytes_for_batch_size_1_and_4(tmp_path):
         assert Image.open(l1).size == Image.open(p).size and Image.open(g1).size == Image.open(p).size
         assert not np.array_equal(np.array(Image.open(g1)), np.array(Image.open(p)))       # gt/ is the sharpened image
         assert not np.array_equal(np.array(Image.open(l1)), np.array(Image.open(g1)))
+
+
+def test_bad_arguments_answer_the_documented_codes_and_launch_nothing():
+    """every rejection of the three entry points of csrc/degrade2.hip, code by code: one thing changed at a time on a valid call"""
+    from edtr_amd import lib, ops
+    L, s = lib.load(), ops.stream_ptr()
+    x = torch.zeros((2, 3, 4, 4), dtype=torch.float32, device=DEV)
+    out, aux = torch.full_like(x, 7.0), torch.full_like(x, 7.0)            # aux: mask_out / noise_out
+    taps = torch.full((3,), 1.0 / 3.0, dtype=torch.float32, device=DEV)
+    sc = torch.ones(2, dtype=torch.float32, device=DEV)
+    gry = torch.zeros(2, dtype=torch.int32, device=DEV)
+    ids = torch.zeros(2, dtype=torch.int64, device=DEV)
+    tables = torch.zeros((9, 256, 256), dtype=torch.int32, device=DEV)     # (the sizes a launch would read)
+    lows = torch.zeros((9, 256), dtype=torch.int32, device=DEV)
+    levels = torch.full((2, 16), 7, dtype=torch.int32, device=DEV)
+    P = lambda t: t.data_ptr()
+    f32s, i32s = lambda *v: (C.c_float * len(v))(*v), lambda *v: (C.c_int32 * len(v))(*v)
+    E_NULL, E_SHAPE, E_ALIGN, E_DTYPE, E_UNSUPPORTED = -1, -2, -3, -4, -5
+    shape = dict(B=2, channels=3, H=4, W=4)
+    valid = {      # the arguments in the order of the entry point
+        "sepblur": (L.edtr_degrade_sepblur, dict(x=P(x), out=P(out), mask_out=P(aux), **shape, taps=P(taps), k=3, threshold=10.0)),
+        "usm_apply": (L.edtr_degrade_usm_apply, dict(x=P(x), blur=P(x), soft=P(x), out=P(out), **shape, weight=0.5)),
+        "poisson_noise": (L.edtr_degrade_poisson_noise, dict(x=P(x), out=P(out), noise_out=P(aux), **shape, scale_host=f32s(1.0, 1.0), scale=P(sc),
+                                                             gray_host=i32s(0, 0), gray=P(gry), tables=P(tables), lows=P(lows), levels=P(levels),
+                                                             counts_out=None, seed=1, image_ids=None, image_id_base=0, draw=0, rounds=0)),
+    }
+
+    def code(name, **change):
+        fn, args = valid[name]
+        assert set(change) <= set(args)
+        return fn(*{**args, **change}.values(), s)
+
+    for name in valid:
+        for change, want in ((dict(channels=1), E_UNSUPPORTED), (dict(channels=1, x=None), E_UNSUPPORTED),      # the channel check comes first
+                             (dict(x=None), E_NULL), (dict(out=None), E_NULL), (dict(B=0), E_SHAPE), (dict(B=65536), E_SHAPE),
+                             (dict(H=(1 << 24) + 4), E_UNSUPPORTED), (dict(x=P(x) + 2), E_ALIGN)):
+            assert code(name, **change) == want, (name, change)
+    for change, want in ((dict(scale_host=None), E_NULL), (dict(rounds=2), E_DTYPE), (dict(rounds=2, draw=-1), E_DTYPE),    # rounds before draw
+                         (dict(draw=-1), E_SHAPE), (dict(draw=1 << 32), E_SHAPE), (dict(H=3, W=3), E_ALIGN),              # H W % 4
+                         (dict(scale_host=f32s(-1.0, 1.0)), E_SHAPE), (dict(scale_host=f32s(1.0, float("nan"))), E_SHAPE),
+                         (dict(gray_host=i32s(2, 0)), E_DTYPE), (dict(image_ids=P(ids) + 4), E_ALIGN),
+                         (dict(image_ids=None, image_id_base=(1 << 32) - 1), E_SHAPE),                                   # image_id_base + B > 2^32
+                         (dict(x=P(x) + 4), E_ALIGN),                                                                     # the 16-byte rule
+                         (dict(tables=None), E_NULL), (dict(out=P(x)), E_UNSUPPORTED), (dict(levels=P(x)), E_UNSUPPORTED)):
+        assert code("poisson_noise", **change) == want, change
+    for change, want in ((dict(k=65), E_SHAPE), (dict(mask_out=P(out)), E_UNSUPPORTED)):
+        assert code("sepblur", **change) == want, change
+    torch.cuda.synchronize()
+    assert bool((out == 7.0).all()) and bool((aux == 7.0).all()) and bool((x == 0.0).all()) and bool((levels == 7).all())   # nothing was launched

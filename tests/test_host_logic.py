@@ -765,3 +765,20 @@ def test_lin320_host_packing_and_launch_rules():
     assert plan(M=192) < 0 and plan(N=96) < 0 and plan(K=640) < 0 and plan(same=True) < 0 and plan(N=2048) < 0
     assert plan(N=960, vt=True, res=True) < 0 and plan(N=960, vt=True, rpi=48) < 0 and plan(N=960, vt=True, ldo=320) < 0
     assert plan(gn=True, ln=1) < 0 and plan(gn=True, rpi=192) < 0 and plan(M=384, gn=True, rpi=256) < 0
+
+
+def test_object_dependencies_are_derived_from_the_include_lines():
+    """build.object_deps against the table it replaces, and the wall between the glue units and the MFMA units"""
+    from edtr_amd import build
+    listed = {"attention.hip": ["attn_v3_loop.inc"], "elementwise.hip": ["noise_elem.h"], "rng.hip": ["noise_elem.h", "philox.h"],
+              "degrade.hip": ["philox.h"], "degrade2.hip": ["philox.h"]}         # the hand-written table of before
+    glue = ["elementwise.hip", "rng.hip", "imageio.hip", "degrade.hip", "degrade2.hip", "labels.hip", "boxes.hip"]
+    mfma = ["igemm.hip", "halo512.hip", "attention.hip", "attn512.hip", "norm.hip", "swin.hip", "ffn.hip", "lin320.hip"]
+    assert sorted(glue + mfma) == sorted(build.SOURCES)
+    deps = {src: [os.path.basename(d) for d in build.object_deps(src)] for src in build.SOURCES}
+    for src in build.SOURCES:
+        assert deps[src][0] == src and len(set(deps[src])) == len(deps[src])
+        assert set(listed.get(src, []) + ["common.h", "edtr_hip.h"]) <= set(deps[src]), src
+        assert all(os.path.isfile(d) for d in build.object_deps(src))
+    assert "attn_v3_loop.inc" in deps["attention.hip"]                           # reached through its #define, not a quoted line
+    assert all("glue.h" in deps[src] for src in glue) and not any("glue.h" in deps[src] for src in mfma)
