@@ -11,6 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libedtr_hip.so")
 SOURCES = ["igemm.hip", "halo512.hip", "attention.hip", "attn512.hip", "norm.hip", "elementwise.hip", "swin.hip", "ffn.hip", "lin320.hip", "rng.hip", "imageio.hip", "degrade.hip", "degrade2.hip", "labels.hip", "boxes.hip"]
+# units that include glue.h and are newer than the glue / MFMA table tests/test_host_logic.py pins SOURCES to; compiled and linked alike
+GLUE_SOURCES = ["coco.hip"]
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 ABI_HEADER = os.path.join(INCLUDE, "edtr_hip.h")
 ARCH = "gfx950"
@@ -91,7 +93,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     objs = []
     relink = force
     jobs = []
-    for src in SOURCES:
+    for src in SOURCES + GLUE_SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
         # -Werror=pass-failed: a `#pragma unroll` the optimizer could not honour is an ERROR — in round 4 such a loop around the

@@ -18,17 +18,7 @@ constexpr int kLimit = 1 << 24;
 __device__ __forceinline__ float larger(float a, float b) { return a > b ? a : b; }        // b where either is NaN
 __device__ __forceinline__ float smaller(float a, float b) { return a < b ? a : b; }
 
-__device__ __forceinline__ uint64_t lanes_below(int lane) { return (1ull << lane) - 1ull; }
-
 // ---- non-maximum suppression -----------------------------------------------------------------------------------------------------
-
-// uint32 whose unsigned order is the order torch sorts fp32 scores in: every NaN is one largest key, -0.0 and 0.0 are one key
-__device__ __forceinline__ uint32_t score_key(float s) {
-    if (s != s) return 0xffffffffu;
-    if (s == 0.0f) return 0x80000000u;
-    const uint32_t u = __float_as_uint(s);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // order[rank(i)] = i with rank(i) = #{j : key j > key i} + #{j < i : key j == key i}: a stable descending sort by counting.
 // A lane owns candidate i; the j side passes through LDS 256 keys at a time (every read is a broadcast).  Tiles are aligned with

@@ -1,4 +1,4 @@
-// What the fp32 / uint8 glue kernels share (elementwise.hip, rng.hip, imageio.hip, degrade.hip, degrade2.hip, labels.hip, boxes.hip; no
+// What the fp32 / uint8 glue kernels share (elementwise.hip, rng.hip, imageio.hip, degrade.hip, degrade2.hip, labels.hip, boxes.hip, coco.hip; no
 // MFMA translation unit includes this file): the grid of a grid-stride launch, the alignment predicates and the batch check of the
 // host side, and the device helpers whose roundings the numpy restatements repeat bit for bit.  ONE definition each: a rounding rule
 // that lived in three files could be fixed in one and drift in the other two.
@@ -80,6 +80,18 @@ __device__ __forceinline__ float bilinear_blend(const float* src, int ih, int iw
     const float top = add_rn(mul_rn(wx0, r0[x0]), mul_rn(tx, r0[x1]));
     const float bot = add_rn(mul_rn(wx0, r1[x0]), mul_rn(tx, r1[x1]));
     return add_rn(mul_rn(wy0, top), mul_rn(ty, bot));
+}
+
+// the lanes of a wave below `lane`, as a ballot mask: popcount(vote & lanes_below(lane)) is a lane's place in an ordered compaction
+__device__ __forceinline__ uint64_t lanes_below(int lane) { return (1ull << lane) - 1ull; }
+
+// uint32 whose unsigned order is the order torch sorts fp32 scores in: every NaN is one largest key, -0.0 and 0.0 are one key
+// (boxes.score_keys; the NMS rank and the per-label rank of the detection scores count with it)
+__device__ __forceinline__ uint32_t score_key(float s) {
+    if (s != s) return 0xffffffffu;
+    if (s == 0.0f) return 0x80000000u;
+    const uint32_t u = __float_as_uint(s);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
 // the 8-bit level of v in [0, 1] (round half to even, clamped), and v rounded to the levels and back

@@ -18,6 +18,7 @@ LOGITS_F32, LOGITS_F16, LOGITS_BF16 = 0, 1, 2               # EDTR_LOGITS_*: log
 SEG_MAX_CLASSES = 32        # EDTR_SEG_MAX_CLASSES: the largest n of edtr_seg_confusion
 NMS_MAX_BOXES = 32768       # EDTR_NMS_MAX_BOXES: the largest n of edtr_boxes_nms
 BOX_SHIFT, BOX_MUL, BOX_DIV, BOX_CLIP = 1, 2, 4, 8          # EDTR_BOX_*: flags of edtr_boxes_transform
+COCO_MAX_DET, COCO_MAX_GT, COCO_MAX_LABELS, COCO_MAX_THRESHOLDS, COCO_KEEP = 1024, 1024, 256, 10, 100     # EDTR_COCO_*: caps of edtr_coco_match
 
 DECLARED_SYMBOLS = [
     "edtr_abi_version", "edtr_error_string", "edtr_device_info", "edtr_igemm", "edtr_flash_attn64",
@@ -35,6 +36,7 @@ DECLARED_SYMBOLS = [
     "edtr_degrade_poisson_noise", "edtr_degrade_sepblur", "edtr_degrade_usm_apply",
     "edtr_seg_confusion", "edtr_label_resize_nearest", "edtr_label_window", "edtr_label_colorize",
     "edtr_boxes_rank", "edtr_boxes_nms", "edtr_boxes_candidates", "edtr_boxes_filter_shift", "edtr_boxes_transform", "edtr_boxes_bilinear_scale",
+    "edtr_coco_match",
 ]
 
 
@@ -308,6 +310,8 @@ def load() -> C.CDLL:
     lib.edtr_boxes_filter_shift.argtypes = [vp, vp, vp, i32, f32, f32, f32, vp, vp, vp, vp, i32, vp]
     lib.edtr_boxes_transform.argtypes = [vp, vp, i32, i32, f32, f32, f32, f32, f32, f32, vp]
     lib.edtr_boxes_bilinear_scale.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, f32, vp]
+    # detection scores (edtr_hip.h "Detection scores")
+    lib.edtr_coco_match.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp]
     if lib.edtr_abi_version() != 10:
         raise RuntimeError("libedtr_hip.so ABI version mismatch")
     _lib = lib

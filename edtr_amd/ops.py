@@ -941,6 +941,26 @@ def make_boxes_bilinear_scale(*, src, dst, rscale_h: float, rscale_w: float, nam
     return Rec(L.load().edtr_boxes_bilinear_scale, args, (src, dst), name, 0.0, 4.0 * (src.numel() + dst.numel()))
 
 
+# -- detection scores (edtr_hip.h "Detection scores"; the caller and the host restatement are edtr_amd/coco.py) -----------------------
+def make_coco_match(*, det_boxes, det_scores, det_labels, count, gt_boxes, gt_labels, gt_area, gt_crowd, n_labels: int, image_id: int,
+                    thresholds, areas, rec: dict, det_offset, capacity: int, gt_offset, gt_capacity: int, name="coco.match") -> Rec:
+    """One image's detections (fp32 ``det_boxes`` [n, 4], ``det_scores`` [n], ``det_labels`` [n], of which the int32 [1] device ``count``
+    exist, or all for None) matched against its ground truth (``gt_boxes`` [g, 4], ``gt_labels``, fp32 ``gt_area``, uint8 ``gt_crowd``) and
+    appended to the record arrays ``rec`` (`coco.Records`; at least ``capacity`` / ``gt_capacity`` rows) at the device offsets, which are
+    moved on.  Labels: both int64 or both int32."""
+    n, g = det_scores.shape[0], gt_area.shape[0]
+    if capacity > rec["match"].numel() or gt_capacity > rec["gt_ignore"].numel():
+        raise ValueError("the record arrays are shorter than the capacities")
+    if det_labels.dtype != gt_labels.dtype or det_labels.dtype not in (torch.int64, torch.int32):
+        raise TypeError("labels must be int64 or int32, the same for detections and ground truth")
+    args = (ptr(det_boxes), ptr(det_scores), ptr(det_labels), n, ptr(count), ptr(gt_boxes), ptr(gt_labels), ptr(gt_area), ptr(gt_crowd), g,
+            int(det_labels.dtype == torch.int64), int(n_labels), int(image_id), ptr(thresholds), thresholds.numel(), ptr(areas),
+            ptr(rec["image"]), ptr(rec["label"]), ptr(rec["score"]), ptr(rec["rank"]), ptr(rec["match"]), ptr(rec["ignore"]), ptr(det_offset),
+            int(capacity), ptr(rec["gt_image"]), ptr(rec["gt_label"]), ptr(rec["gt_ignore"]), ptr(gt_offset), int(gt_capacity))
+    keep = (det_boxes, det_scores, det_labels, count, gt_boxes, gt_labels, gt_area, gt_crowd, thresholds, areas, rec, det_offset, gt_offset)
+    return Rec(L.load().edtr_coco_match, args, keep, name, 0.0, 28.0 * n + 26.0 * g)
+
+
 def make_cast16(*, dtype, src: torch.Tensor, rows: int, C: int, dst: torch.Tensor, name="cast16") -> Rec:
     args = (dt_code(dtype), ptr(src), rows, C, src.stride(0), ptr(dst), dst.stride(0))
     return Rec(L.load().edtr_cast16, args, (src, dst), name, 0.0, 6.0 * rows * C)

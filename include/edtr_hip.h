@@ -1029,6 +1029,50 @@ int edtr_boxes_transform(const float* src, float* dst, int n, int flags, float d
 int edtr_boxes_bilinear_scale(const float* src, float* dst, int planes, int ih, int iw, int oh, int ow, float rscale_h, float rscale_w,
                               edtr_stream_t stream);
 
+/* ---- Detection scores: COCO matching into a running record, for mAP with no host sync in the loop (additive to ABI 10) --------------
+ * The reference's detection test hands every image's detections to CocoEvaluator.update (main/det/test_edtr.py:138-190,
+ * utils/detection.py:422-480) and reports mAP@[0.5:0.95] and mAP@0.5.  One call here is COCOeval.evaluateImg for one image, every
+ * label, IoU threshold and area range at once; accumulate and summarize run on the host from one copy at the end
+ * (edtr_amd/coco.py, which restates the launch in numpy: the normative rule is written out there).
+ * Detections: boxes fp32 [n][4] xyxy (16-byte aligned), scores fp32 [n], labels; with `count` (int32, device, the form the max_out
+ * launches return) rows at or past *count do not exist and are never read.  Ground truth: boxes fp32 [g][4], labels, area fp32 [g],
+ * crowd uint8 [g].  labels: int32, or int64 with labels_i64 = 1, for both.  thresholds: fp64 [n_thr] on the device; areas: fp64
+ * [4][2] = (lo, hi) per range, on the device.
+ *   coordinates  w = x2 - x1 and h = y2 - y1 in fp32; everything after in fp64, each operation rounded (no contraction)
+ *   IoU          iw = min(dx + dw, gx + gw) - max(dx, gx), ih alike; 0 if iw <= 0 or ih <= 0; else i = iw ih, u = da for a crowd and
+ *                (da + ga) - i otherwise with da = dw dh, ga = gw gh; iou = i / u
+ *   rank         per label, by the key of edtr_boxes_rank descending, equal keys by index; ranks 0 .. 99 are matched
+ *   ground truth ignored in range a iff crowd or area outside [lo_a, hi_a]; walked not-ignored first, then ignored, each in input order
+ *   walk         per (t, a), detections in rank order: best = min(thr_t, 1 - 1e-10), m = none; for each ground truth in order: skip it if
+ *                matched at this (t, a) and no crowd; stop if m is not ignored and this one is; skip it if iou < best; else best = iou,
+ *                m = this (an equal IoU moves m on).  A matched detection takes m's ignore flag and marks m; an unmatched one is
+ *                ignored iff its own area da lies outside [lo_a, hi_a].
+ * Detection records (structure of arrays, `capacity` rows), row *det_offset + i for detection i: image = image_id; label, or -1
+ * outside [0, n_labels); score; rank within (image, label), -1 for label -1; match and ignore: bit 4 t + a, both zero for rank >= 100
+ * and for label -1.  Ground-truth records (`gt_capacity` rows), row *gt_offset + j: image, label (or -1), ignore: bit a.
+ * Both offsets (int32, device) are moved on by a dependent one-workgroup launch, by the rows that exist and by g; nothing is written
+ * at or past a capacity, and the offset moves on all the same, so the host sees an overflow after its one copy.
+ * Two launches: one wave64 workgroup per label (ballot compaction and a counting rank in LDS, one row of IoUs per detection, lane
+ * 4 t + a walking the ground truths with its own matched-set bits, the two ballots being the record words) plus one workgroup for the
+ * fields that do not depend on the matching; then the offsets.  Every record word has exactly one writer: no atomics, no waiting
+ * between workgroups.  n = 0 and g = 0 together launch nothing.
+ * Errors: a NULL table, record or offset pointer, or a NULL input whose extent is positive, EDTR_E_NULL; n < 0, g < 0, n_labels <= 0,
+ * n_thr <= 0 or a capacity <= 0 EDTR_E_SHAPE; n > EDTR_COCO_MAX_DET, g > EDTR_COCO_MAX_GT, n_labels > EDTR_COCO_MAX_LABELS, n_thr >
+ * EDTR_COCO_MAX_THRESHOLDS or a capacity > 2^30 EDTR_E_UNSUPPORTED; labels_i64 not 0 / 1 EDTR_E_DTYPE; boxes not aligned to 16 bytes,
+ * the others to their element EDTR_E_ALIGN.
+ * replaces: CocoEvaluator.update -> COCOeval.evaluateImg, maskUtils.iou, convert_to_xywh (utils/detection.py:422-480, 576-578). */
+#define EDTR_COCO_MAX_DET 1024
+#define EDTR_COCO_MAX_GT 1024
+#define EDTR_COCO_MAX_LABELS 256
+#define EDTR_COCO_MAX_THRESHOLDS 10
+#define EDTR_COCO_KEEP 100
+int edtr_coco_match(const float* det_boxes, const float* det_scores, const void* det_labels, int n, const int32_t* count,
+                    const float* gt_boxes, const void* gt_labels, const float* gt_area, const uint8_t* gt_crowd, int g, int labels_i64,
+                    int n_labels, int image_id, const double* thresholds, int n_thr, const double* areas, int32_t* rec_image,
+                    int32_t* rec_label, float* rec_score, int32_t* rec_rank, uint64_t* rec_match, uint64_t* rec_ignore,
+                    int32_t* det_offset, int capacity, int32_t* gt_image, int32_t* gt_label, uint8_t* gt_ignore, int32_t* gt_offset,
+                    int gt_capacity, edtr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * hipGraph capture of a launch sequence issued on `stream` (one denoise step, or a whole batch).
  * ---------------------------------------------------------------------------------------- */
