@@ -19,6 +19,7 @@ SEG_MAX_CLASSES = 32        # EDTR_SEG_MAX_CLASSES: the largest n of edtr_seg_co
 NMS_MAX_BOXES = 32768       # EDTR_NMS_MAX_BOXES: the largest n of edtr_boxes_nms
 BOX_SHIFT, BOX_MUL, BOX_DIV, BOX_CLIP = 1, 2, 4, 8          # EDTR_BOX_*: flags of edtr_boxes_transform
 COCO_MAX_DET, COCO_MAX_GT, COCO_MAX_LABELS, COCO_MAX_THRESHOLDS, COCO_KEEP = 1024, 1024, 256, 10, 100     # EDTR_COCO_*: caps of edtr_coco_match
+CLS_MAX_CLASSES, CLS_MAX_KEEP, CLS_MAX_TOPK, CLS_FD_CHUNK, CLS_FD_MAX_ELEMS = 65536, 8, 4, 4096, 1 << 28       # EDTR_CLS_*: caps of edtr_cls_*
 
 DECLARED_SYMBOLS = [
     "edtr_abi_version", "edtr_error_string", "edtr_device_info", "edtr_igemm", "edtr_flash_attn64",
@@ -37,6 +38,7 @@ DECLARED_SYMBOLS = [
     "edtr_seg_confusion", "edtr_label_resize_nearest", "edtr_label_window", "edtr_label_colorize",
     "edtr_boxes_rank", "edtr_boxes_nms", "edtr_boxes_candidates", "edtr_boxes_filter_shift", "edtr_boxes_transform", "edtr_boxes_bilinear_scale",
     "edtr_coco_match",
+    "edtr_cls_rank", "edtr_cls_fdist", "edtr_cls_commit", "edtr_cls_normalize", "edtr_cls_window",
 ]
 
 
@@ -312,6 +314,12 @@ def load() -> C.CDLL:
     lib.edtr_boxes_bilinear_scale.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, f32, vp]
     # detection scores (edtr_hip.h "Detection scores")
     lib.edtr_coco_match.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp]
+    # classification (edtr_hip.h "Classification"): topk_host is a ctypes int32 array, mean_host / std_host ctypes float arrays
+    lib.edtr_cls_rank.argtypes = [i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp]
+    lib.edtr_cls_fdist.argtypes = [i32, vp, vp, i32, i32, vp, vp]
+    lib.edtr_cls_commit.argtypes = [vp, vp, vp, i32, vp, i32, C.POINTER(i32), i32, vp, vp, vp, i32, i32, vp]
+    lib.edtr_cls_normalize.argtypes = [vp, vp, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp]
+    lib.edtr_cls_window.argtypes = [vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
     if lib.edtr_abi_version() != 10:
         raise RuntimeError("libedtr_hip.so ABI version mismatch")
     _lib = lib

@@ -961,6 +961,67 @@ def make_coco_match(*, det_boxes, det_scores, det_labels, count, gt_boxes, gt_la
     return Rec(L.load().edtr_coco_match, args, keep, name, 0.0, 28.0 * n + 26.0 * g)
 
 
+# -- classification (edtr_hip.h "Classification"; the callers and the host restatements are edtr_amd/cls.py) ---------------------------
+def make_cls_rank(*, logits, labels, keep: int, rec_label, rec_rank, rec_top, offset, capacity: int, name="cls.rank") -> Rec:
+    """The order behind topk for ``logits`` [B, C] (fp32 / fp16 / bf16): the rank of int32 ``labels`` [B] (or None) into ``rec_rank``,
+    the first ``keep`` classes into ``rec_top`` [capacity, keep], the labels into ``rec_label`` (or None), at the rows from the int32
+    [1] device ``offset`` (None: 0) and below ``capacity``."""
+    B, C = logits.shape
+    if logits.dtype not in _LOGITS_DT:
+        raise TypeError(f"logits must be float32, float16 or bfloat16, got {logits.dtype}")
+    if labels is not None and (labels.dtype != torch.int32 or labels.numel() != B):
+        raise TypeError("labels must be int32, one per row")
+    if (rec_rank is not None and capacity > rec_rank.numel()) or (keep > 0 and capacity * keep > rec_top.numel()):
+        raise ValueError("the record arrays are shorter than the capacity")
+    args = (_LOGITS_DT[logits.dtype], ptr(logits), ptr(labels), B, C, int(keep), ptr(rec_label), ptr(rec_rank), ptr(rec_top), ptr(offset),
+            int(capacity))
+    return Rec(L.load().edtr_cls_rank, args, (logits, labels, rec_label, rec_rank, rec_top, offset), name, 0.0,
+               float(logits.element_size() * logits.numel() * (1 + int(keep))))
+
+
+def make_cls_fdist(*, a, b, partials, name="cls.fdist") -> Rec:
+    """fp64 ``partials`` [B, ceil(n / lib.CLS_FD_CHUNK)] = the chunk sums of |a - b| over the n elements of every image of ``a``, ``b``
+    [B, ...] (fp32 / fp16 / bf16, the same for both)"""
+    B = a.shape[0]
+    n = a.numel() // B
+    if a.dtype not in _LOGITS_DT or b.dtype != a.dtype or a.shape != b.shape:
+        raise TypeError("the two feature tensors must have one shape and one of float32, float16 and bfloat16")
+    if partials.dtype != torch.float64 or partials.numel() < B * ((n + L.CLS_FD_CHUNK - 1) // L.CLS_FD_CHUNK):
+        raise ValueError("partials takes one fp64 word per image and chunk")
+    args = (_LOGITS_DT[a.dtype], ptr(a), ptr(b), B, n, ptr(partials))
+    return Rec(L.load().edtr_cls_fdist, args, (a, b, partials), name, 0.0, 2.0 * a.element_size() * a.numel())
+
+
+def make_cls_commit(*, rec_rank, rec_fd, rec_batch, B: int, partials, n: int, topk: Sequence[int], batch_n, batch_correct, offsets,
+                    capacity: int, batch_capacity: int, name="cls.commit") -> Rec:
+    """Closes a batch of ``B`` images: counts rank < k for every k of ``topk`` into the batch row, finalises the feature distances from
+    ``partials`` (None: NaN), and moves the int32 [2] device ``offsets`` (images, batches) on."""
+    topk_host = (ct.c_int32 * max(len(topk), 1))(*[int(k) for k in topk])
+    if capacity > rec_fd.numel() or capacity > rec_batch.numel() or batch_capacity > batch_n.numel():
+        raise ValueError("the record arrays are shorter than the capacities")
+    args = (ptr(rec_rank), ptr(rec_fd), ptr(rec_batch), int(B), ptr(partials), int(n), topk_host, len(topk), ptr(batch_n), ptr(batch_correct),
+            ptr(offsets), int(capacity), int(batch_capacity))
+    return Rec(L.load().edtr_cls_commit, args, (rec_rank, rec_fd, rec_batch, partials, topk_host, batch_n, batch_correct, offsets), name, 0.0, 16.0 * B)
+
+
+def make_cls_normalize(*, x, out, mean: Sequence[float], std: Sequence[float], name="cls.normalize") -> Rec:
+    """``out`` = (``x`` - mean_c) / std_c on fp32 [B, 3, H, W], each operation rounded; ``out`` may be ``x``"""
+    B, ch, H, W = x.shape
+    m_host, s_host = (ct.c_float * 3)(*[float(v) for v in mean]), (ct.c_float * 3)(*[float(v) for v in std])
+    args = (ptr(x), ptr(out), B, ch, H, W, m_host, s_host)
+    return Rec(L.load().edtr_cls_normalize, args, (x, out, m_host, s_host), name, 0.0, 8.0 * x.numel())
+
+
+def make_cls_window(*, src, dst, out_hw, y0: int, x0: int, hflip: bool, vflip: bool, transpose: bool, fill: int, name="cls.window") -> Rec:
+    """uint8 ``src`` [h, w, C] -> ``dst``: the ``out_hw`` = (H, W) crop at (y0, x0), flipped, ``fill`` outside the source; ``dst`` is
+    [H, W, C], or [W, H, C] under ``transpose``."""
+    (h, w, ch), (H, W) = src.shape, out_hw
+    if tuple(dst.shape) != ((W, H, ch) if transpose else (H, W, ch)):
+        raise ValueError(f"dst is {tuple(dst.shape)} for a {H} x {W} crop with transpose = {bool(transpose)}")
+    args = (ptr(src), h, w, ch, ptr(dst), int(H), int(W), int(y0), int(x0), int(bool(hflip)), int(bool(vflip)), int(bool(transpose)), int(fill))
+    return Rec(L.load().edtr_cls_window, args, (src, dst), name, 0.0, 2.0 * dst.numel())
+
+
 def make_cast16(*, dtype, src: torch.Tensor, rows: int, C: int, dst: torch.Tensor, name="cast16") -> Rec:
     args = (dt_code(dtype), ptr(src), rows, C, src.stride(0), ptr(dst), dst.stride(0))
     return Rec(L.load().edtr_cast16, args, (src, dst), name, 0.0, 6.0 * rows * C)

@@ -1073,6 +1073,76 @@ int edtr_coco_match(const float* det_boxes, const float* det_scores, const void*
                     int32_t* det_offset, int capacity, int32_t* gt_image, int32_t* gt_label, uint8_t* gt_ignore, int32_t* gt_offset,
                     int gt_capacity, edtr_stream_t stream);
 
+/* ---- Classification: top-k rank, feature distance and the data set's geometry, with no host sync in the loop (additive to ABI 10) ---
+ * The reference's classification test normalises the restored batch for its classifier, scores calculate_accuracy(pred, label,
+ * topk=(1, 5)) and, with --calc-fd, F.l1_loss(feat_res, feat_gt, reduction='none').mean(dim=(1, 2, 3)) (main/cls/test_edtr.py:127-162,
+ * utils/classification.py:45-61); its data set crops, flips and transposes the ground truth (datasets/classification.py:65-96).
+ * edtr_amd/cls.py restates every launch in numpy and writes the rules out; the kernels are tested against it by equality.  Records are
+ * structures of arrays that a running pair of offsets (int32 [2] on the device: images, batches) appends to; nothing is written at or
+ * past a capacity, and the offsets move on all the same, so the host sees an overflow after its one copy.  Every output word has
+ * one writer: no atomics, no waiting between workgroups. */
+#define EDTR_CLS_MAX_CLASSES 65536
+#define EDTR_CLS_MAX_KEEP 8
+#define EDTR_CLS_MAX_TOPK 4
+#define EDTR_CLS_FD_CHUNK 4096
+#define EDTR_CLS_FD_MAX_ELEMS (1 << 28)
+/* The order behind topk for every row of logits [B][C] (fp32 / fp16 / bf16 by logits_dtype, EDTR_LOGITS_*; 16-bit values are widened
+ * exactly).  With key(v) the uint32 key of edtr_boxes_rank (every NaN one largest key, -0.0 and 0.0 one key):
+ *   order   class j precedes class i iff key(v_j) > key(v_i), or the keys are equal and j < i
+ *   rank    rec_rank[row] = the number of classes that precede class labels[b]; C when labels[b] lies outside [0, C)
+ *   top     rec_top[row K + m], m < K = the class with exactly m predecessors; -1 for m >= C
+ *   label   rec_label[row] (optional) = labels[b]
+ * with row = *offset + b (offset: int32 on the device, or NULL for 0); a row at or past `capacity` is not written.  labels (int32 [B],
+ * device) may be NULL: rank and label are then not written (the argmax of 2-D targets is this launch with K = 1).  On rows without
+ * equal keys the order is torch.topk(K, 1, True, True)'s, whose order among equal values is unspecified; torch's CPU max / argmax
+ * (the first NaN, else the first maximum) is top[., 0].  One launch, one wave64 workgroup per row: the predecessors of the label by
+ * ballot and popcount, the K places by K rounds of a wave-wide (greatest key, least index) selection below the place taken last.
+ * Errors: NULL logits, labels without rec_rank or K > 0 without rec_top EDTR_E_NULL; B, C, capacity <= 0, K < 0, or neither labels nor
+ * K EDTR_E_SHAPE; B > 65535, C > EDTR_CLS_MAX_CLASSES, K > EDTR_CLS_MAX_KEEP, capacity > 2^30 EDTR_E_UNSUPPORTED; unknown logits_dtype
+ * EDTR_E_DTYPE; a pointer not aligned to its element EDTR_E_ALIGN.
+ * replaces: output.topk(maxk, 1, True, True), pred.eq(target[None]), target.max(dim=1)[1], utils/classification.py:50-55. */
+int edtr_cls_rank(int logits_dtype, const void* logits, const int32_t* labels, int B, int C, int K, int32_t* rec_label,
+                  int32_t* rec_rank, int32_t* rec_top, const int32_t* offset, int capacity, edtr_stream_t stream);
+/* partials [B][chunks] (fp64, device; chunks = ceil(n / EDTR_CLS_FD_CHUNK)) = the chunk sums of |a - b| over the n elements of
+ * every image of a, b [B][n] (fp32 / fp16 / bf16 by dtype, EDTR_LOGITS_*).  Each difference is formed in fp32 — widen, subtract,
+ * fabsf — and added in fp64 in an order that depends on n alone: one 256-lane workgroup per (image, chunk), lane l adds elements l,
+ * l + 256, ... of its chunk in that order, and the tree s = 128, 64, ..., 1 with sum[l] += sum[l + s] over the 256 lane sums gives
+ * the partial.  edtr_cls_commit finalises.
+ * Errors: NULL EDTR_E_NULL; B <= 0 or n <= 0 EDTR_E_SHAPE; B > 65535 or n > EDTR_CLS_FD_MAX_ELEMS EDTR_E_UNSUPPORTED; unknown dtype
+ * EDTR_E_DTYPE; a, b not aligned to an element or partials to 8 bytes EDTR_E_ALIGN.
+ * replaces: F.l1_loss(feat_res, feat_gt, reduction='none').mean(dim=(1, 2, 3)), main/cls/test_edtr.py:153. */
+int edtr_cls_fdist(int dtype, const void* a, const void* b, int B, int n, double* partials, edtr_stream_t stream);
+/* The dependent one-workgroup launch that closes a batch of B images whose ranks lie at rows offsets[0] ... of rec_rank:
+ *   batch row  batch_n[offsets[1]] = B; batch_correct[offsets[1] n_topk + t] = #{rows of the batch : rank < topk_host[t]}
+ *   fd         rec_fd[row] = fp32(sum of the image's partials in chunk order in fp64 / n in fp64); NaN with partials NULL
+ *   batch      rec_batch[row] = offsets[1]
+ *   offsets    offsets[0] += B, offsets[1] += 1
+ * topk_host: n_topk <= EDTR_CLS_MAX_TOPK ints on the HOST, each in [1, EDTR_CLS_MAX_KEEP]; n_topk = 0 counts nothing (rec_rank,
+ * topk_host and batch_correct may then be NULL).  Rows at or past `capacity` / `batch_capacity` are not written or counted.
+ * Errors: a NULL record, batch or offsets pointer EDTR_E_NULL; B, a capacity <= 0, n_topk < 0, a topk entry <= 0, or partials with
+ * n <= 0 EDTR_E_SHAPE; B > 65535, n_topk > EDTR_CLS_MAX_TOPK, a topk entry > EDTR_CLS_MAX_KEEP, a capacity > 2^30 or n >
+ * EDTR_CLS_FD_MAX_ELEMS EDTR_E_UNSUPPORTED; a pointer not aligned to its element EDTR_E_ALIGN.
+ * replaces: correct[:k].flatten().sum(), utils/classification.py:57-60, and the list appends of main/cls/test_edtr.py:151-153. */
+int edtr_cls_commit(const int32_t* rec_rank, float* rec_fd, int32_t* rec_batch, int B, const double* partials, int n,
+                    const int32_t* topk_host, int n_topk, int32_t* batch_n, int32_t* batch_correct, int32_t* offsets, int capacity,
+                    int batch_capacity, edtr_stream_t stream);
+/* out = (x - mean_c) / std_c on fp32 [B][3][H][W], the subtraction and the division each correctly rounded: torchvision's Normalize
+ * (sub_ then div_) with fp32 constants.  mean_host / std_host: three floats each on the HOST.  out may be x.  Errors: those of every
+ * fp32 batch ("Low-quality inputs"); NULL constants EDTR_E_NULL; a NaN constant or a zero std EDTR_E_SHAPE.
+ * replaces: Normalize / inv_normalize, model/resnet.py:17-27, 293-294. */
+int edtr_cls_normalize(const float* x, float* out, int B, int channels, int H, int W, const float* mean_host, const float* std_host,
+                       edtr_stream_t stream);
+/* edtr_label_window plus the transpose.  crop (r, c) = src (y0 + r, x0 + c) for r < H, c < W, `fill` outside src [h][w][channels]
+ * (uint8, channels 1 or 3); then both flips on the crop's indices, then the transpose:
+ *   transpose 0  dst [H][W]:  dst (y, x) = crop (y', x'),  y' = H - 1 - y under vflip, x' = W - 1 - x under hflip
+ *   transpose 1  dst [W][H]:  dst (y, x) = crop (x', y'),  x' = H - 1 - x under vflip, y' = W - 1 - y under hflip
+ * One gather; with the transpose a 32 x 32 tile goes through LDS so that reads and writes both run along rows.  Errors: as
+ * edtr_label_window; transpose not 0 / 1 EDTR_E_DTYPE.
+ * replaces: center_crop_arr / random_crop_arr and augment (both flips, then img.transpose(1, 0, 2)), datasets/classification.py:82-93,
+ * datasets/augment.py:57-68. */
+int edtr_cls_window(const uint8_t* src, int h, int w, int channels, uint8_t* dst, int H, int W, int y0, int x0, int hflip, int vflip,
+                    int transpose, int fill, edtr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * hipGraph capture of a launch sequence issued on `stream` (one denoise step, or a whole batch).
  * ---------------------------------------------------------------------------------------- */
