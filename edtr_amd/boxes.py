@@ -136,9 +136,11 @@ def softmax_reference(logits, dtype=F32) -> np.ndarray:
     return (e / e.sum(axis=-1, keepdims=True, dtype=dtype)).astype(dtype)
 
 
-def decode_reference(rel_codes, proposals, weights=BOX_WEIGHTS, bbox_xform_clip: float = BBOX_XFORM_CLIP, dtype=F32) -> np.ndarray:
+def decode_reference(rel_codes, proposals, weights=BOX_WEIGHTS, bbox_xform_clip: float = BBOX_XFORM_CLIP, dtype=F32, exp=np.exp) -> np.ndarray:
     """`BoxCoder.decode_single` (model/util.py:702-743) in its operation order: [P, 4 C] codes and [P, 4] proposals -> [P, C, 4].
-    The deltas are divided by the weights, dw and dh cut at ``bbox_xform_clip``, and the only step that is not exact arithmetic is exp."""
+    The deltas are divided by the weights, dw and dh cut at ``bbox_xform_clip``, and the only step that is not exact arithmetic is
+    ``exp`` (numpy's unless another is handed in: two exponentials that are each within an ulp differ in the last bit for a good
+    third of their arguments)."""
     r = np.asarray(rel_codes, dtype=dtype)
     p = np.asarray(proposals, dtype=dtype)
     if r.ndim != 2 or p.ndim != 2 or p.shape[1] != 4 or r.shape[0] != p.shape[0] or r.shape[1] % 4:
@@ -151,7 +153,7 @@ def decode_reference(rel_codes, proposals, weights=BOX_WEIGHTS, bbox_xform_clip:
     dw, dh = np.where(dw > clip, clip, dw), np.where(dh > clip, clip, dh)
     with np.errstate(over="ignore", invalid="ignore"):
         pcx, pcy = dx * widths + ctr_x, dy * heights + ctr_y
-        half_w, half_h = dtype(0.5) * (np.exp(dw).astype(dtype) * widths), dtype(0.5) * (np.exp(dh).astype(dtype) * heights)
+        half_w, half_h = dtype(0.5) * (exp(dw).astype(dtype) * widths), dtype(0.5) * (exp(dh).astype(dtype) * heights)
         return np.stack([pcx - half_w, pcy - half_h, pcx + half_w, pcy + half_h], axis=2).astype(dtype)
 
 

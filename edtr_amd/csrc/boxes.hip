@@ -174,25 +174,18 @@ __global__ void __launch_bounds__(256) det_candidates_kernel(CandParams a) {
         for (int c = lane; c < a.C; c += 64) s = add_rn(s, expf(add_rn(row[c], -m)));
         s = wave_sum(s);
         const f32x4 pr = *reinterpret_cast<const f32x4*>(a.proposals + 4 * (int64_t)p);
-        const float width = add_rn(pr.z, -pr.x), height = add_rn(pr.w, -pr.y);
-        const float ctr_x = add_rn(pr.x, mul_rn(0.5f, width)), ctr_y = add_rn(pr.y, mul_rn(0.5f, height));
         for (int c0 = 1; c0 < a.C; c0 += 64) {
             const int c = c0 + lane;
             bool flag = false;
             if (c < a.C) {
                 const float score = div_rn(expf(add_rn(row[c], -m)), s);
                 const f32x4 r = *reinterpret_cast<const f32x4*>(a.regression + ((int64_t)p * a.C + c) * 4);
-                const float dx = div_rn(r.x, a.wx), dy = div_rn(r.y, a.wy);
-                float dw = div_rn(r.z, a.ww), dh = div_rn(r.w, a.wh);
-                dw = dw > a.xform_clip ? a.xform_clip : dw;
-                dh = dh > a.xform_clip ? a.xform_clip : dh;
-                const float pcx = add_rn(mul_rn(dx, width), ctr_x), pcy = add_rn(mul_rn(dy, height), ctr_y);
-                const float hw = mul_rn(0.5f, mul_rn(expf(dw), width)), hh = mul_rn(0.5f, mul_rn(expf(dh), height));
+                const f32x4 d = decode_box(pr, r, a.wx, a.wy, a.ww, a.wh, a.xform_clip);
                 f32x4 o;
-                o.x = clamp_to(add_rn(pcx, -hw), a.img_w);
-                o.y = clamp_to(add_rn(pcy, -hh), a.img_h);
-                o.z = clamp_to(add_rn(pcx, hw), a.img_w);
-                o.w = clamp_to(add_rn(pcy, hh), a.img_h);
+                o.x = clamp_to(d.x, a.img_w);
+                o.y = clamp_to(d.y, a.img_h);
+                o.z = clamp_to(d.z, a.img_w);
+                o.w = clamp_to(d.w, a.img_h);
                 const int64_t k = (int64_t)p * (a.C - 1) + (c - 1);
                 *reinterpret_cast<f32x4*>(a.cand_boxes + 4 * k) = o;
                 a.cand_scores[k] = score;

@@ -1,4 +1,4 @@
-// What the fp32 / uint8 glue kernels share (elementwise.hip, rng.hip, imageio.hip, degrade.hip, degrade2.hip, labels.hip, boxes.hip, coco.hip, cls.hip; no
+// What the fp32 / uint8 glue kernels share (elementwise.hip, rng.hip, imageio.hip, degrade.hip, degrade2.hip, labels.hip, boxes.hip, coco.hip, cls.hip, rois.hip; no
 // MFMA translation unit includes this file): the grid of a grid-stride launch, the alignment predicates and the batch check of the
 // host side, and the device helpers whose roundings the numpy restatements repeat bit for bit.  ONE definition each: a rounding rule
 // that lived in three files could be fixed in one and drift in the other two.
@@ -92,6 +92,24 @@ __device__ __forceinline__ uint32_t score_key(float s) {
     if (s == 0.0f) return 0x80000000u;
     const uint32_t u = __float_as_uint(s);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// BoxCoder.decode_single (model/util.py:702-743) for one box and one code, in the reference's operation order: the deltas divided by
+// the weights, dw and dh cut at xform_clip, the centre moved and the side scaled by expf, the corners centre -/+ half a side.  Not
+// clipped.  (boxes.decode_reference; the detector head's candidates and the RPN's both decode with it.)
+__device__ __forceinline__ f32x4 decode_box(f32x4 pr, f32x4 r, float wx, float wy, float ww, float wh, float xform_clip) {
+#pragma clang fp contract(off)
+    const float width = add_rn(pr.z, -pr.x), height = add_rn(pr.w, -pr.y);
+    const float ctr_x = add_rn(pr.x, mul_rn(0.5f, width)), ctr_y = add_rn(pr.y, mul_rn(0.5f, height));
+    const float dx = div_rn(r.x, wx), dy = div_rn(r.y, wy);
+    float dw = div_rn(r.z, ww), dh = div_rn(r.w, wh);
+    dw = dw > xform_clip ? xform_clip : dw;
+    dh = dh > xform_clip ? xform_clip : dh;
+    const float pcx = add_rn(mul_rn(dx, width), ctr_x), pcy = add_rn(mul_rn(dy, height), ctr_y);
+    const float hw = mul_rn(0.5f, mul_rn(expf(dw), width)), hh = mul_rn(0.5f, mul_rn(expf(dh), height));
+    f32x4 o;
+    o.x = add_rn(pcx, -hw), o.y = add_rn(pcy, -hh), o.z = add_rn(pcx, hw), o.w = add_rn(pcy, hh);
+    return o;
 }
 
 // the 8-bit level of v in [0, 1] (round half to even, clamped), and v rounded to the levels and back

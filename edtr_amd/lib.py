@@ -20,6 +20,7 @@ NMS_MAX_BOXES = 32768       # EDTR_NMS_MAX_BOXES: the largest n of edtr_boxes_nm
 BOX_SHIFT, BOX_MUL, BOX_DIV, BOX_CLIP = 1, 2, 4, 8          # EDTR_BOX_*: flags of edtr_boxes_transform
 COCO_MAX_DET, COCO_MAX_GT, COCO_MAX_LABELS, COCO_MAX_THRESHOLDS, COCO_KEEP = 1024, 1024, 256, 10, 100     # EDTR_COCO_*: caps of edtr_coco_match
 CLS_MAX_CLASSES, CLS_MAX_KEEP, CLS_MAX_TOPK, CLS_FD_CHUNK, CLS_FD_MAX_ELEMS = 65536, 8, 4, 4096, 1 << 28       # EDTR_CLS_*: caps of edtr_cls_*
+RPN_MAX_LEVELS, RPN_MAX_PRE_NMS, ROI_MAX_TAPS = 8, 4096, 64          # EDTR_RPN_* / EDTR_ROI_*: caps of edtr_rpn_* and edtr_roi_align
 
 DECLARED_SYMBOLS = [
     "edtr_abi_version", "edtr_error_string", "edtr_device_info", "edtr_igemm", "edtr_flash_attn64",
@@ -39,6 +40,7 @@ DECLARED_SYMBOLS = [
     "edtr_boxes_rank", "edtr_boxes_nms", "edtr_boxes_candidates", "edtr_boxes_filter_shift", "edtr_boxes_transform", "edtr_boxes_bilinear_scale",
     "edtr_coco_match",
     "edtr_cls_rank", "edtr_cls_fdist", "edtr_cls_commit", "edtr_cls_normalize", "edtr_cls_window",
+    "edtr_rpn_anchors", "edtr_rpn_select", "edtr_rpn_candidates", "edtr_roi_align",
 ]
 
 
@@ -320,6 +322,11 @@ def load() -> C.CDLL:
     lib.edtr_cls_commit.argtypes = [vp, vp, vp, i32, vp, i32, C.POINTER(i32), i32, vp, vp, vp, i32, i32, vp]
     lib.edtr_cls_normalize.argtypes = [vp, vp, i32, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp]
     lib.edtr_cls_window.argtypes = [vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+    # region proposals and RoI pooling (edtr_hip.h): pointer tables, level tables and scales are ctypes arrays on the host
+    lib.edtr_rpn_anchors.argtypes = [C.POINTER(i32), i32, vp, vp, vp]
+    lib.edtr_rpn_select.argtypes = [i32, C.POINTER(vp), C.POINTER(i32), i32, i32, i32, vp, vp]
+    lib.edtr_rpn_candidates.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), i32, i32, i32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp]
+    lib.edtr_roi_align.argtypes = [i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(f32), i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, vp]
     if lib.edtr_abi_version() != 10:
         raise RuntimeError("libedtr_hip.so ABI version mismatch")
     _lib = lib

@@ -1022,6 +1022,70 @@ def make_cls_window(*, src, dst, out_hw, y0: int, x0: int, hflip: bool, vflip: b
     return Rec(L.load().edtr_cls_window, args, (src, dst), name, 0.0, 2.0 * dst.numel())
 
 
+# -- region proposals and RoI pooling (edtr_hip.h; the callers and the host restatements are edtr_amd/rois.py) -----------------------
+def _level_table(levels):
+    """int32 [L][5] on the host from [(H, W, A, stride_h, stride_w)]"""
+    flat = [int(v) for row in levels for v in row]
+    return (ct.c_int32 * max(len(flat), 1))(*flat)
+
+
+def _pointer_table(tensors):
+    return (ct.c_void_p * max(len(tensors), 1))(*[ptr(t) for t in tensors])
+
+
+def _one_dtype(tensors, what: str) -> int:
+    if not tensors or tensors[0].dtype not in _LOGITS_DT or any(t.dtype != tensors[0].dtype for t in tensors):
+        raise TypeError(f"{what} must all be float32, all float16 or all bfloat16")
+    return _LOGITS_DT[tensors[0].dtype]
+
+
+def make_rpn_anchors(*, levels, cells, anchors, name="rois.anchors") -> Rec:
+    """fp32 ``anchors`` [sum H W A, 4] from ``levels`` = [(H, W, A, stride_h, stride_w)] and the fp32 device ``cells`` [sum A, 4]"""
+    table = _level_table(levels)
+    return Rec(L.load().edtr_rpn_anchors, (table, len(levels), ptr(cells), ptr(anchors)), (table, cells, anchors), name, 0.0, 16.0 * anchors.shape[0])
+
+
+def make_rpn_select(*, objectness, levels, pre_nms_top_n: int, selected, name="rois.select") -> Rec:
+    """int32 ``selected`` [N, sum min(pre_nms_top_n, H W A)]: per image and level the logical indices of the greatest ``objectness``
+    (a list of contiguous [N, A, H, W] tensors of one dtype), in topk order"""
+    dt, table, ptrs = _one_dtype(objectness, "objectness"), _level_table(levels), _pointer_table(objectness)
+    N = objectness[0].shape[0]
+    args = (dt, ptrs, table, len(levels), N, int(pre_nms_top_n), ptr(selected))
+    nbytes = 5.0 * sum(o.element_size() * o.numel() for o in objectness)
+    return Rec(L.load().edtr_rpn_select, args, (ptrs, table, tuple(objectness), selected), name, 0.0, nbytes)
+
+
+def make_rpn_candidates(*, objectness, deltas, levels, pre_nms_top_n: int, cells, selected, image_sizes, xform_clip: float, min_size: float,
+                        score_thresh: float, boxes, probs, level, counts, name="rois.candidates") -> Rec:
+    """The selected elements of ``objectness`` / ``deltas`` (lists of [N, A, H, W] / [N, 4 A, H, W]) decoded against their anchors,
+    clipped to the fp32 device ``image_sizes`` [N, 2] and filtered, compacted per image into ``boxes`` [N, M, 4], ``probs`` and ``level``
+    (int32) [N, M]; ``counts`` int32 [N]."""
+    dt, table = _one_dtype(list(objectness) + list(deltas), "objectness and bbox_deltas"), _level_table(levels)
+    po, pd = _pointer_table(objectness), _pointer_table(deltas)
+    N = objectness[0].shape[0]
+    args = (dt, po, pd, table, len(levels), N, int(pre_nms_top_n), ptr(cells), ptr(selected), ptr(image_sizes), float(xform_clip),
+            float(min_size), float(score_thresh), ptr(boxes), ptr(probs), ptr(level), ptr(counts))
+    keep = (po, pd, table, tuple(objectness), tuple(deltas), cells, selected, image_sizes, boxes, probs, level, counts)
+    return Rec(L.load().edtr_rpn_candidates, args, keep, name, 0.0, 48.0 * selected.numel())
+
+
+def make_roi_align(*, features, scales, rois, batch_index, out, sampling_ratio: int, k_min: int, k_max: int, canonical_scale: float,
+                   canonical_level: float, name="rois.roi_align") -> Rec:
+    """fp32 ``out`` [K, C, P, P] = MultiScaleRoIAlign of ``features`` (a list of contiguous [N, C, H, W] tensors of one dtype) at the fp32
+    ``rois`` [K, 4] of the images ``batch_index`` (int32 [K]); ``scales``: one host float per level"""
+    dt, ptrs = _one_dtype(features, "features"), _pointer_table(features)
+    hw = [int(v) for f in features for v in f.shape[-2:]]
+    hw_host, sc_host = (ct.c_int32 * len(hw))(*hw), (ct.c_float * len(features))(*[float(v) for v in scales])
+    N, C = features[0].shape[:2]
+    K, P = out.shape[0], out.shape[-1]
+    args = (dt, ptrs, hw_host, sc_host, len(features), N, C, ptr(rois), ptr(batch_index), K, P, int(sampling_ratio), int(k_min), int(k_max),
+            float(canonical_scale), float(canonical_level), ptr(out))
+    keep = (ptrs, hw_host, sc_host, tuple(features), rois, batch_index, out)
+    nbytes = 4.0 * out.numel() * (1 + 4 * int(sampling_ratio) ** 2)
+    return Rec(L.load().edtr_roi_align, args, keep, name, 9.0 * out.numel() * int(sampling_ratio) ** 2, nbytes)
+
+
+
 def make_cast16(*, dtype, src: torch.Tensor, rows: int, C: int, dst: torch.Tensor, name="cast16") -> Rec:
     args = (dt_code(dtype), ptr(src), rows, C, src.stride(0), ptr(dst), dst.stride(0))
     return Rec(L.load().edtr_cast16, args, (src, dst), name, 0.0, 6.0 * rows * C)

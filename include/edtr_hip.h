@@ -1143,6 +1143,67 @@ int edtr_cls_normalize(const float* x, float* out, int B, int channels, int H, i
 int edtr_cls_window(const uint8_t* src, int h, int w, int channels, uint8_t* dst, int H, int W, int y0, int x0, int hflip, int vflip,
                     int transpose, int fill, edtr_stream_t stream);
 
+/* ---- Region proposals and RoI pooling: the non-learned steps inside the detector (additive to ABI 10) -------------------------------
+ * The reference's Faster R-CNN (model/faster_rcnn.py) runs, between its learned parts, AnchorGenerator.forward (:514-589),
+ * RegionProposalNetwork.filter_proposals (:2068-2134, 2199-2213) and MultiScaleRoIAlign, the last two through compiled torchvision
+ * operators.  edtr_amd/rois.py restates every launch in numpy and writes the rules out; the launches equal the restatements bit for bit
+ * except where expf (decoding, sigmoid) and log2f (the level of a roi) enter.  The RPN head's outputs are read as the head wrote them:
+ * per level l, objectness [N][A_l][H_l][W_l] and deltas [N][4 A_l][H_l][W_l] (channel 4 a + c), fp32 / fp16 / bf16 by dtype
+ * (EDTR_LOGITS_*; 16-bit values are widened exactly).  The LOGICAL index of an element of a level is i = (y W + x) A + a, the row
+ * concat_box_prediction_layers would have moved it to.  levels_host: int32 [L][5] on the HOST = H, W, A, stride_h, stride_w per level;
+ * objectness_host / deltas_host / features_host: L device pointers in a HOST array; cells: fp32 [sum A_l][4] on the device, the cell
+ * anchors of every level in level order.  Every output word has one writer; no global and no floating-point atomics.
+ * Common errors (nothing is launched): a NULL pointer EDTR_E_NULL; L, N, pre_nms_top_n, H, W or A <= 0, a negative stride
+ * EDTR_E_SHAPE; L > EDTR_RPN_MAX_LEVELS, pre_nms_top_n > EDTR_RPN_MAX_PRE_NMS, H W A >= 2^24, H stride_h or W stride_w >= 2^24,
+ * N > 65535 EDTR_E_UNSUPPORTED; unknown dtype EDTR_E_DTYPE; cells and boxes not aligned to 16 bytes, the others to their element
+ * EDTR_E_ALIGN. */
+#define EDTR_RPN_MAX_LEVELS 8
+#define EDTR_RPN_MAX_PRE_NMS 4096
+#define EDTR_ROI_MAX_TAPS 64
+/* anchors [sum H W A][4] (fp32): anchor i of a level = (float(x stride_w) + cell[a][0], float(y stride_h) + cell[a][1],
+ * float(x stride_w) + cell[a][2], float(y stride_h) + cell[a][3]).  For callers and tests: the proposal launches form anchors from
+ * the index and read no anchor tensor.
+ * replaces: AnchorGenerator.grid_anchors, model/faster_rcnn.py:540-569. */
+int edtr_rpn_anchors(const int32_t* levels_host, int L, const float* cells, float* anchors, edtr_stream_t stream);
+/* selected [N][sum take_l] (int32), take_l = min(pre_nms_top_n, H_l W_l A_l): for every image and level the take_l level-local logical
+ * indices of the greatest objectness, by the key of edtr_boxes_rank descending (every NaN first, -0.0 == 0.0), equal keys by ascending
+ * logical index — torch.topk wherever torch defines the order.  One 1024-lane workgroup per (level, image): a radix select on the
+ * 32-bit key (four 8-bit passes in memory order; histograms by integer adds in LDS) finds the threshold key and how many elements
+ * equal to it to take, an ordered ballot compaction in logical order gathers them into LDS, and a counting rank there orders them.
+ * replaces: permute_and_flatten, ob.topk(pre_nms_top_n, dim=1), model/faster_rcnn.py:2068-2077, 2231-2260. */
+int edtr_rpn_select(int dtype, const void* const* objectness_host, const int32_t* levels_host, int L, int N, int pre_nms_top_n,
+                    int32_t* selected, edtr_stream_t stream);
+/* For every selected element, in level order and then selection order: the anchor from its index; BoxCoder.decode_single with weights
+ * (1, 1, 1, 1) and xform_clip (the arithmetic of edtr_boxes_candidates); prob = 1 / (1 + expf(-logit)); the corners clamped to
+ * [0, w] x [0, h] of image_sizes [N][2] (fp32 h, w on the device); kept iff x2 - x1 >= min_size && y2 - y1 >= min_size && prob >=
+ * score_thresh.  boxes [N][sum take][4], probs and level (int32) [N][sum take] receive the kept ones of each image in order from its
+ * row's start, counts [N] (int32) their number.  One workgroup per image, ordered ballot compaction.
+ * replaces: BoxCoder.decode, the gathers by top_n_idx, torch.sigmoid, clip_boxes_to_image, remove_small_boxes and the score filter,
+ * model/faster_rcnn.py:2105-2123, 2211. */
+int edtr_rpn_candidates(int dtype, const void* const* objectness_host, const void* const* deltas_host, const int32_t* levels_host, int L,
+                        int N, int pre_nms_top_n, const float* cells, const int32_t* selected, const float* image_sizes,
+                        float xform_clip, float min_size, float score_thresh, float* boxes, float* probs, int32_t* level,
+                        int32_t* counts, edtr_stream_t stream);
+/* MultiScaleRoIAlign as one launch: out [K][C][P][P] (fp32) from features [N][C][H_l][W_l] per level (fp32 / fp16 / bf16 by dtype),
+ * rois [K][4] (fp32 xyxy in image coordinates, 16-byte aligned) and batch_index [K] (int32: the image of each roi).
+ *   level   with L > 1: s = sqrtf((x2 - x1) (y2 - y1)); t = floorf((canonical_level + log2f(s / canonical_scale)) + 1e-6f) clamped to
+ *           [k_min, k_max] (NaN: k_min); level = t - k_min.  With L == 1 there is no mapper.
+ *   pool    roi_align with aligned = False: the four coordinates times scales_host[level]; roi_w = max(x2 - x1, 1), bin_w = roi_w / P
+ *           (h alike); sample (iy, ix) of bin (ph, pw): y = (y1 + ph bin_h) + ((iy + 0.5) bin_h) / S, x alike; a sample with y < -1,
+ *           y > H, x < -1 or x > W adds nothing; else y = max(y, 0), y_low = (int)y, and y_low >= H - 1 gives y_low = y_high = H - 1,
+ *           y = y_low, otherwise y_high = y_low + 1; ly = y - y_low, hy = 1 - ly (x alike); the sample is
+ *           (((hy hx) v11 + (hy lx) v12) + (ly hx) v21) + (ly lx) v22, added to the sum with iy outer and ix inner; out = sum / (S S).
+ *           Every step one rounded fp32 operation, no product contracted with a sum.
+ * level_hw_host: int32 [L][2] and scales_host: fp32 [L], on the HOST.  One workgroup per (roi, 64 channels): the P S tap positions of
+ * each axis go through LDS once, then a lane owns output elements in storage order.
+ * Errors: NULL EDTR_E_NULL; a non-positive extent, scale or canonical_scale, or k_max - k_min != L - 1 with L > 1 EDTR_E_SHAPE;
+ * L > EDTR_RPN_MAX_LEVELS, N > 65535, P S > EDTR_ROI_MAX_TAPS, an extent >= 2^24 EDTR_E_UNSUPPORTED; unknown dtype EDTR_E_DTYPE; rois
+ * not aligned to 16 bytes, the others to their element EDTR_E_ALIGN.
+ * replaces: torchvision.ops.MultiScaleRoIAlign (LevelMapper, roi_align), model/faster_rcnn.py:9. */
+int edtr_roi_align(int dtype, const void* const* features_host, const int32_t* level_hw_host, const float* scales_host, int L, int N,
+                   int C, const float* rois, const int32_t* batch_index, int K, int P, int S, int k_min, int k_max,
+                   float canonical_scale, float canonical_level, float* out, edtr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * hipGraph capture of a launch sequence issued on `stream` (one denoise step, or a whole batch).
  * ---------------------------------------------------------------------------------------- */
