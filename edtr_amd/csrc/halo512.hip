@@ -567,6 +567,51 @@ __global__ void __launch_bounds__(512, 1) igemm_halo512_kernel(const edtr_igemm_
     chunk_body(nchunk - 1, std::true_type{});
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (g == 0) __builtin_amdgcn_s_barrier();           // re-align the two wave groups
+    // ---- K tail (edtr_hip.h: a3): C3 more columns read at the output pixel itself, i.e. the centre tap of C3 / 32 more chunks.
+    // Not part of the counted schedule above: a plain double-buffered loop with full waits (chunk t + 1 flies while chunk t is
+    // multiplied) over the same patch buffers and ring slots 0 / 1, with ld3 in the patch addresses.  No GroupNorm here: a_gn
+    // normalises the 9-tap operand only.
+    if (p.a3 != nullptr) {
+        const int ntail = p.C3 / CK;
+        const u32x4 srd_3 = srd_of(p.a3);
+        __syncthreads();                                // every wave's look-ahead DMAs (zeros) have landed, nobody reads the buffers
+        int lane_t = lane;                              // (opaque: keeps the tail's addresses out of the main loop's register file)
+        asm volatile("" : "+v"(lane_t));
+#pragma unroll
+        for (int j = 0; j < NPP; ++j) {
+            const int u = (wave + 8 * j) * 64 + lane_t, pp = u >> 2, slot = u & 3;
+            const int py = pp / PW, px = pp - py * PW;
+            const int iy = sy0 + py, ix = sx0 + px;
+            const bool ok = pp < PPIX && iy >= 0 && iy < p.IH && ix >= 0 && ix < p.IW;
+            voff_p[j] = ok ? (uint32_t)(((((int64_t)img * p.IH + iy) * p.IW + ix) * p.ld3 + (slot ^ key8(px)) * 8) * 2) : kOob;
+        }
+        auto stage_tail = [&](int t, int par) {
+#pragma unroll
+            for (int j = 0; j < NPP; ++j) dma(voff_p[j], srd_3, (uint32_t)(t * CK * 2), smem_base + par * PATCHB + (wave + 8 * j) * 1024);
+            dma(voff_w, srd_w, (uint32_t)((9 * Cin + t * CK) * 2), smem_base + W_BASE + par * WTAP + wave * 1024);
+        };
+        stage_tail(0, 0);
+        for (int t = 0; t < ntail; ++t) {
+            const int par = t & 1;
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();                            // chunk t has landed for every wave; the other buffers are free
+            if (t + 1 < ntail) stage_tail(t + 1, par ^ 1);
+            const char* pa = smem + par * PATCHB;
+            const char* pb = smem + W_BASE + par * WTAP + b_rd;
+#pragma unroll
+            for (int nb = 0; nb < 4; ++nb) bfr[nb] = *reinterpret_cast<const U4*>(pb + nb * 1024);
+#pragma unroll
+            for (int sub = 0; sub < 2; ++sub) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) afr[j] = *reinterpret_cast<const U4*>(pa + a_rd[1] + (j + 1) * PROWB + sub * 1024);   // tap (1, 1)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int nb = 0; nb < 4; ++nb) acc[sub * 4 + j][nb] = T::mfma16(bfr[nb], afr[j], acc[sub * 4 + j][nb]);
+            }
+        }
+        __syncthreads();                                // the epilogue's residual DMAs reuse the buffers
+    }
     H5_STAMP(3);
 
     direct_epilogue<T, 8, RED>(p, acc, smem, smem_base, lane, wave, wc, (int64_t)m0 + 4 * q * p.OW, n0, img, tm);
@@ -1128,6 +1173,49 @@ __global__ void __launch_bounds__(512, 1) igemm_halo160_kernel(const edtr_igemm_
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (g == 0) __builtin_amdgcn_s_barrier();           // re-align the two wave groups
+    // ---- K tail (edtr_hip.h: a3; as in tile 17): the centre tap of C3 / 32 more chunks read from a3, double-buffered over the two
+    // patch buffers and ring slots 0 / 1, full waits
+    if (p.a3 != nullptr) {
+        const int ntail = p.C3 / CK;
+        const u32x4 srd_3 = srd_of(p.a3);
+        __syncthreads();                                // every wave's look-ahead DMAs (zeros) have landed, nobody reads the buffers
+        int lane_t = lane;                              // (opaque: keeps the tail's addresses out of the main loop's register file)
+        asm volatile("" : "+v"(lane_t));
+#pragma unroll
+        for (int j = 0; j < NPP; ++j) {
+            const int u = (wave + 8 * j) * 64 + lane_t, pp = u >> 2, slot = u & 3;
+            const int py = pp / PW, px = pp - py * PW;
+            const int iy = sy0 + py, ix = sx0 + px;
+            const bool ok = pp < PPIX && iy >= 0 && iy < p.IH && ix >= 0 && ix < p.IW;
+            voff_p[j] = ok ? (uint32_t)(((((int64_t)img * p.IH + iy) * p.IW + ix) * p.ld3 + (slot ^ key8(px)) * 8) * 2) : kOob;
+        }
+        auto stage_tail = [&](int t, int par) {
+#pragma unroll
+            for (int j = 0; j < NPP; ++j) {
+                const int piece = wave + 8 * j;
+                dma(voff_p[j], srd_3, (uint32_t)(t * CK * 2), smem_base + (piece < 21 ? P_BASE + par * PATCHB + piece * 1024 : DUMP));
+            }
+            dma(voff_w[0], srd_w, (uint32_t)((9 * Cin + t * CK) * 2), smem_base + W_BASE + par * WSL + wave * 1024);
+            if (nwp == 2) dma(voff_w[1], srd_w, (uint32_t)((9 * Cin + t * CK) * 2), smem_base + W_BASE + par * WSL + (wave + 8) * 1024);
+        };
+        stage_tail(0, 0);
+        for (int t = 0; t < ntail; ++t) {
+            const int par = t & 1;
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();                            // chunk t has landed for every wave; the other buffers are free
+            if (t + 1 < ntail) stage_tail(t + 1, par ^ 1);
+            U4 bfr[10], afr[2];
+            const char* pb = smem + par * WSL + b_rd;
+#pragma unroll
+            for (int nb = 0; nb < 10; ++nb) bfr[nb] = *reinterpret_cast<const U4*>(pb + nb * 1024);
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb) afr[mb] = *reinterpret_cast<const U4*>(smem + par * PATCHB + a_rd[1] + (mb + 1) * PROWB);   // tap (1, 1)
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                for (int nb = 0; nb < 10; ++nb) acc[mb][nb] = T::mfma16(bfr[nb], afr[mb], acc[mb][nb]);
+        }
+    }
 
     // ---- epilogue straight from the accumulators: acc[mb][nb][i] = pixel (row 2 wave + mb, column l15), channel n0 + 40 lq + 4 nb + i
     int lane_e = lane;

@@ -2006,6 +2006,9 @@ template <int V> using IC = std::integral_constant<int, V>;
 //          slot c ^ ((px ^ (py & 1)) & 7): an MFMA row block is TWO image rows of 8 pixels, and the row parity in the key keeps
 //          the 16 lanes of a ds_read_b128 group on 16 distinct 16-byte bank slots (10 pixels per patch row is even, so the
 //          column key alone would put (y, x) and (y + 1, x) on the same slot).
+//      4 = GEO 0 with a K tail (edtr_hip.h: a3) behind the chunk loop and without the fused input GroupNorm: an instantiation of its
+//          own because GEO 0 fills the register file to the last VGPR — the tail's few live values would spill there, and a launch
+//          without a tail keeps running exactly the kernel it ran before.  (GEO 2 has the room: its tail is in the one kernel.)
 template <typename T, int GEO>
 __global__ void __launch_bounds__(512, 1) igemm_halo_kernel(const edtr_igemm_params p) {
     constexpr bool UP2 = GEO == 1, IMG8 = GEO == 2, SUBPIX = GEO == 3;
@@ -2282,6 +2285,75 @@ __global__ void __launch_bounds__(512, 1) igemm_halo_kernel(const edtr_igemm_par
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (g == 0) __builtin_amdgcn_s_barrier();           // re-align the two wave groups
     __syncthreads();
+    // ---- K tail (a3: the 1x1 skip convolution of a width-changing ResBlock as C3 more columns of this product, centre tap only).
+    // The look-ahead DMAs of the loop above (chunks >= cend: zeros) have landed and every wave is past its last fragment read, so
+    // the patch buffers and ring slots 0 / 1 are free.  A plain double-buffered loop over this split's share of the C3 / 64 tail
+    // chunks: chunk t + 1 flies while chunk t is multiplied, every wait is a full one (no counted schedule here).  The patch
+    // addresses are the 9-tap ones with ld3 for ld1 (halo pixels are staged but never read: the centre tap stays inside the patch).
+    if constexpr (GEO == 4 || IMG8) {
+        const int ntail = p.a3 != nullptr ? p.C3 / BK : 0;
+        const int tbeg = (int)blockIdx.y * ntail / nsplit, tend = ((int)blockIdx.y + 1) * ntail / nsplit;
+        if (tbeg < tend) {
+            const u32x4 srd_3 = make_srd(p.a3);
+            // (an OPAQUE copy of the lane index: otherwise the compiler works the tail's addresses out at kernel entry and carries
+            //  them — spilled — through the main loop, whose register file is full)
+            int lane_t = lane;
+            asm volatile("" : "+v"(lane_t));
+#pragma unroll
+            for (int j = 0; j < NPP; ++j) {
+                const int u = (wave + 8 * j) * 64 + lane_t, pp = u >> 3, slot = u & 7;
+                if constexpr (IMG8) {
+                    const int i = pp / 100, rem = pp - i * 100, py = rem / 10, px = rem - py * 10;
+                    const int iy = py - 1, ix = px - 1;
+                    const bool ok = pp < 400 && iy >= 0 && iy < 8 && ix >= 0 && ix < 8;
+                    const int c = slot ^ ((px ^ (py & 1)) & 7);
+                    voff_p[j] = ok ? (uint32_t)(((((int64_t)(img + i) * 8 + iy) * 8 + ix) * p.ld3 + c * 8) * 2) : kOobOffset;
+                } else {
+                    const int py = pp / PW, px = pp - py * PW;
+                    const int iy = sy0 + py, ix = sx0 + px;
+                    const bool ok = pp < PW * PW && iy >= 0 && iy < p.IH && ix >= 0 && ix < p.IW;
+                    const int c = slot ^ (px & 7);
+                    voff_p[j] = ok ? (uint32_t)(((((int64_t)img * p.IH + iy) * p.IW + ix) * p.ld3 + c * 8) * 2) : kOobOffset;
+                }
+            }
+            auto stage_tail = [&](int t, int par) {
+#pragma unroll
+                for (int j = 0; j < NPP; ++j) {
+                    const uint32_t dst = (IMG8 && lds_p[j] == 0xFFFFFFFFu) ? (uint32_t)SCRATCH : (uint32_t)(par * PATCHB) + lds_p[j];
+                    dma16_buf(voff_p[j], srd_3, (uint32_t)(t * BK * 2), smem_base + dst);
+                }
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    dma16_buf(voff_w[j], srd_w, (uint32_t)((9 * Cin + t * BK) * 2), smem_base + B_BASE + par * BTAP + (wave + 8 * j) * 1024);
+            };
+            stage_tail(tbeg, 0);
+            for (int t = tbeg; t < tend; ++t) {
+                const int par = (t - tbeg) & 1;
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();                   // chunk t has landed for every wave; nobody reads the other buffers any more
+                if (t + 1 < tend) stage_tail(t + 1, par ^ 1);
+                const char* pa = smem + par * PATCHB;
+                const char* pb = smem + B_BASE + par * BTAP + b_rd;
+#pragma unroll
+                for (int nb = 0; nb < 4; ++nb) bfr[nb] = *reinterpret_cast<const U4*>(pb + nb * 2048);
+#pragma unroll
+                for (int sub = 0; sub < 2; ++sub) {
+#pragma unroll
+                    for (int mb = 0; mb < 4; ++mb) {         // the main loop's fragment reads of tap (1, 1)
+                        if constexpr (IMG8)
+                            afr[mb] = *reinterpret_cast<const U4*>(pa + a_rd[1 + 3] + (sub * 100 + (2 * mb + 1) * 10) * 128);
+                        else
+                            afr[mb] = *reinterpret_cast<const U4*>(pa + a_rd[1] + (sub * 4 + mb + 1) * PROW);
+                    }
+#pragma unroll
+                    for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+                        for (int nb = 0; nb < 4; ++nb) acc[sub * 4 + mb][nb] = T::mfma16(bfr[nb], afr[mb], acc[sub * 4 + mb][nb]);
+                }
+            }
+            __syncthreads();                       // the epilogue's staging tile overwrites the buffers
+        }
+    }
     EDTR_STAMP(3);
 
     // ---- epilogue: the two K halves meet in the fp32 staging tile [256 pixels][128 channels], 528-byte rows (129 KiB).  The product
@@ -2421,6 +2493,7 @@ int dispatch(const edtr_igemm_params& p, int tile, bool spatial, hipStream_t s, 
         if (dry) return tile;
         if (igemm_halo_img8(p)) return launch_halo<T, 2>(p, s);
         if (p.upsample2x == 2) return launch_halo<T, 3>(p, s);
+        if (p.a3) return launch_halo<T, 4>(p, s);
         return p.upsample2x ? launch_halo<T, 1>(p, s) : launch_halo<T, 0>(p, s);
     }
     if (tile >= 3 && tile <= 14) {
@@ -2556,8 +2629,19 @@ static int igemm_run(const edtr_igemm_params* pp, edtr_stream_t stream, bool dry
     if (p.zdiv <= 0) p.zdiv = 1;
     if (p.C2 > 0 && !p.a2) return EDTR_E_NULL;
     if (p.C2 < 0 || p.C1 <= 0) return EDTR_E_SHAPE;
-    if (p.K != p.taps * (p.C1 + p.C2)) return EDTR_E_SHAPE;
+    if (!p.a3 || p.C3 == 0) { p.a3 = nullptr; p.C3 = 0; p.ld3 = 0; }     // no K tail
+    if (p.C3 < 0) return EDTR_E_SHAPE;
+    if (p.K != p.taps * (p.C1 + p.C2) + p.C3) return EDTR_E_SHAPE;
     const bool spatial = p.OH > 0;
+    if (p.a3) {     // K tail: the halo tiles' plain 3x3 / stride 1 / pad 1 geometry only (the tile is checked once it is chosen)
+        if (p.taps != 9 || !spatial || p.stride != 1 || p.pad_t != 1 || p.pad_l != 1 || p.upsample2x || p.C2 != 0 || (p.C3 & 63) ||
+            (p.C1 & 63) || p.a_wrap != 0 || p.Z != 1 || p.act == EDTR_ACT_GEGLU)
+            return EDTR_E_UNSUPPORTED;
+        if (p.ld3 < p.C3 || p.ldw < p.K) return EDTR_E_SHAPE;
+        if ((p.ld3 & 7) || !aligned16(p.a3)) return EDTR_E_ALIGN;
+        if (((int64_t)p.M * p.ld3 + p.C3) * 2 >= 0xF0000000LL) return EDTR_E_UNSUPPORTED;    // 32-bit buffer offsets
+    }
+    const int ksel = p.K - p.C3;      // the tile rules below see the 9-tap product: a tail does not move a convolution to another tile
     if (p.taps == 9 && !spatial) return EDTR_E_SHAPE;
     if (spatial) {
         if (p.OW <= 0 || p.IH <= 0 || p.IW <= 0 || p.stride <= 0) return EDTR_E_SHAPE;
@@ -2637,9 +2721,9 @@ static int igemm_run(const edtr_igemm_params* pp, edtr_stream_t stream, bool dry
         // one resident round).  Measured faster than the 128-wide grid whenever >= 200 tiles exist, except the
         // short-K GEMMs whose N the 128-wide grid also divides (two-pass epilogue).
         const int64_t nb160 = (int64_t)((p.M + 127) / 128) * (p.N / 160) * p.Z;
-        if (pp_ok && !(no_auto & (1 << 8)) && p.N % 160 == 0 && nb160 >= 200 && (p.N % 128 != 0 || p.K >= 640))
+        if (pp_ok && !(no_auto & (1 << 8)) && p.N % 160 == 0 && nb160 >= 200 && (p.N % 128 != 0 || ksel >= 640))
             tile = 8;
-        else if (pp_ok && !(no_auto & (1 << 6)) && p.K >= 1024 && nb256 >= 120 && p.N * 5 >= nbn256 * 256 * 4)
+        else if (pp_ok && !(no_auto & (1 << 6)) && ksel >= 1024 && nb256 >= 120 && p.N * 5 >= nbn256 * 256 * 4)
             tile = 6;
         // Halo tile: 3x3 / stride 1 convolutions on 16-pixel-aligned images.  Measured on the MI355X against the tile chosen above
         // (profiles/r02/halo_tile_experiments.log): 1.16-1.27x over the 128x128 loop on the N = 128 convolutions of the VAE's 512x512
@@ -2758,6 +2842,9 @@ static int igemm_run(const edtr_igemm_params* pp, edtr_stream_t stream, bool dry
     if ((p.row_stats || p.vt_out) && (tile == 16 || tile == 17 || tile == 20 || tile == 21)) return EDTR_E_UNSUPPORTED;
     if (p.act == EDTR_ACT_GEGLU && tile == 2) tile = 1;  // value/gate pairing needs two 32-column MFMA tiles per wave
     if (tile >= 3 && !dma_ok && !((tile == 17 || tile == 20 || tile == 21) && p.C2 == 0 && (p.C1 & 31) == 0)) return EDTR_E_UNSUPPORTED;      // (tiles 17 / 20 walk 32-channel chunks)
+    if (p.a3) {             // K tail: tile 16 in its plain 16 x 16-patch and 8 x 8-image forms (no a_gn there), tiles 17 and 20
+        if (!((tile == 16 && !p.a_gn) || tile == 17 || tile == 20)) return EDTR_E_UNSUPPORTED;
+    }
     if (p.gn_partial) {
         const int sr = p.gn_slot_rows > 0 ? p.gn_slot_rows : 128;
         if (p.gn_ld < 0 || (p.gn_ld > 0 && p.gn_ld < p.N)) return EDTR_E_SHAPE;

@@ -215,6 +215,29 @@ class WeightStore:
                    (cop, kh * kw * cip))
         return ref, self.vec(prefix + "bias", cop, bias_scale)
 
+    def conv_tail(self, prefix: str, skip_prefix: str, cin_pad: Optional[int] = None, tail_pad: Optional[int] = None,
+                  bias_scale: float = 1.0) -> Tuple[WRef, torch.Tensor]:
+        """(WRef of [Np, 9*Cinp + C3p], bias f32 [Np]): the 3x3 convolution ``prefix`` with the 1x1 convolution ``skip_prefix`` packed
+        behind it as a K tail (edtr_hip.h: a3) — column 9*Cinp + c of row n is W_skip[n, c]; the bias is the fp32 sum of the two
+        biases, formed before any scaling."""
+        co, ci, kh, kw = self.shape_of(prefix + "weight")
+        co3, c3, kh3, kw3 = self.shape_of(skip_prefix + "weight")
+        if (kh, kw, kh3, kw3) != (3, 3, 1, 1) or co3 != co:
+            raise ValueError(f"{prefix} + {skip_prefix}: a K tail joins a 3x3 and a 1x1 convolution of the same output width")
+        cip, c3p, cop = cin_pad or round_up(ci, 8), tail_pad or round_up(c3, 8), round_up(co, 8)
+
+        def build(parts):
+            w9 = ops.pack_conv_weight(self._p(prefix + "weight"), self.dtype, cin_pad=cin_pad, parts=parts)
+            w1 = ops.pack_conv_weight(self._p(skip_prefix + "weight"), self.dtype, cin_pad=tail_pad, parts=parts)
+            return torch.cat([w9, w1], dim=1).contiguous()
+
+        ref = WRef(self, ("conv_tail", prefix, skip_prefix, cin_pad, tail_pad), build, (cop, 9 * cip + c3p))
+        key = ("vec_sum", prefix + "bias", skip_prefix + "bias", cop, float(bias_scale))
+        if key not in self.cache:
+            v = ops.pad_bias(self._p(prefix + "bias").reshape(-1) + self._p(skip_prefix + "bias").reshape(-1), cop)
+            self.cache[key] = (v * bias_scale if bias_scale != 1.0 else v).contiguous()
+        return ref, self.cache[key]
+
     def conv_subpixel(self, prefix: str, cin_pad: Optional[int] = None, bias_scale: float = 1.0) -> Tuple[WRef, torch.Tensor]:
         """(WRef of the four pre-summed phase matrices [4 * Np, 4 * Cinp], bias f32 [Np]) of a nearest-2x upsample convolution in
         its sub-pixel form (ops.pack_conv_weight_subpixel)."""
@@ -588,7 +611,7 @@ class Emitter:
                 from ``policy`` (edtr_amd/precision.py)."""
 
     def __init__(self, prog: Program, arena: Arena, store: WeightStore, dtype: torch.dtype, precision: str = "fast",
-                 policy=None):
+                 policy=None, ktail: bool = True):
         from .precision import ConstPolicy, mixed_policy
         self.prog, self.arena, self.store = prog, arena, store
         if precision not in ("fast", "high", "mixed"):
@@ -631,6 +654,10 @@ class Emitter:
         pol_split = getattr(self.policy, "attn_split", None)
         self.attn_split = int(os.environ.get("EDTR_AMD_ATTN_SPLIT", "2" if precision == "high" else str(pol_split or 0))) if self.hp else 0
         self._mirrors: List[Tuple[torch.Tensor, torch.Tensor]] = []
+        # fast modes: the 1x1 skip convolution of a width-changing ResBlock rides in conv2 as a K tail (conv(..., tail=)) wherever the
+        # halo tile of that shape takes one.  ``ktail=False``: a fast SECTION of a parity mode (hybrid), whose margin stays as measured;
+        # EDTR_KTAIL=0: the A/B switch
+        self.ktail = precision == "fast" and bool(ktail) and ops.ktail_enabled()
         self.last_gnp = None
         self.last_gn_slot = 128
         self.last_row_stats = None
@@ -927,13 +954,39 @@ class Emitter:
         self.arena.free(tmp)
         return qk, vt, N
 
+    def tail_ok(self, x: Act, prefix: str, skip_x: Act) -> bool:
+        """Can the 3x3 convolution ``prefix`` of ``x`` take the 1x1 convolution of ``skip_x`` (same pixels) as a K tail?  Fast modes
+        with the switch on (Emitter.ktail), whole 64-channel chunks on both operands, and edtr_igemm_plan's word that the halo tile
+        it picks for this shape runs a tail (the split-K count and the fused input GroupNorm are the ones conv() will pass)."""
+        if not self.ktail or self.invariant or x.C % 64 or skip_x.C % 64 or (x.B, x.H, x.W) != (skip_x.B, skip_x.H, skip_x.W):
+            return False
+        if isinstance(x.t, OpN) or isinstance(skip_x.t, OpN) or x.t.dtype != self.dtype or skip_x.t.dtype != self.dtype:
+            return False
+        N = round_up(self.store.shape_of(prefix + "weight")[0], 8)
+        splitk = ops.choose_splitk(x.rows, N, 9 * x.C, img8=(x.H, x.W) == (8, 8))[1]
+        gnin = x.gn_in is not None and ops.gn_in_conv_ok(x.B, x.H, x.W, x.C, N, splitk, x.ld)
+        tile = ops.ktail_plan(self.dtype, x.B, x.H, x.W, x.C, x.ld, N, skip_x.C, skip_x.ld, splitk, gnin)
+        # tile 16's 16 x 16-patch form with a tail three times as wide as the 3x3's input (the 32 x 32 decoder block 1920 -> 640):
+        # measured slower than the launch it replaces (+37.2 us in the loop against 32.6 us, profiles/ktail) — the tail loop runs
+        # its K-tiles at about half the main loop's rate; up to twice the width it wins (+20.7 against 25.1 us)
+        if tile == 16 and (x.H, x.W) != (8, 8) and skip_x.C > 2 * x.C:
+            return False
+        return tile > 0
+
     def conv(self, x: Act, prefix: str, *, taps=9, stride=1, pad_tl=1, ups=False, rowvec=None, residual=None,
-             out=None, out_f32=False, alpha=1.0, name=None, stats=False, feeds=None, mirror=False, gnp_into=None) -> Act:
+             out=None, out_f32=False, alpha=1.0, name=None, stats=False, feeds=None, mirror=False, gnp_into=None,
+             tail: Optional[Tuple[Act, str]] = None) -> Act:
         """3x3 (or 1x1) convolution of an NHWC activation with the packed weight ``prefix``.  ``feeds`` (mixed mode): the output is
         BRANCH-INTERNAL — its only consumer is a normalisation that feeds the named one-part GEMM classes, which round it to fp16
-        anyway — so it is stored as fp16 instead of joining the fp32 stream (Emitter.branch16)."""
+        anyway — so it is stored as fp16 instead of joining the fp32 stream (Emitter.branch16).  ``tail`` = (activation, prefix of a
+        1x1 convolution): that convolution is summed into this one as a K tail (edtr_hip.h: a3; the caller has asked tail_ok)."""
         name = name or ("conv3x3" if taps == 9 else "conv1x1")
-        w, bias = self.store.conv(prefix, cin_pad=x.C, bias_scale=alpha)      # the epilogue applies alpha before the bias
+        if tail is not None:
+            if residual is not None or taps != 9 or stride != 1 or pad_tl != 1 or ups or self.hp or alpha != 1.0:
+                raise RuntimeError(f"{name}: a K tail rides in a plain 3x3 convolution of the fast modes, in place of its residual")
+            w, bias = self.store.conv_tail(prefix, tail[1], cin_pad=x.C, tail_pad=tail[0].C)
+        else:
+            w, bias = self.store.conv(prefix, cin_pad=x.C, bias_scale=alpha)      # the epilogue applies alpha before the bias
         N = w.shape[0]
         if taps == 9:
             LH, LW = (x.H * 2, x.W * 2) if ups else (x.H, x.W)
@@ -959,7 +1012,8 @@ class Emitter:
                     raise RuntimeError(f"{name}: a deferred GroupNorm reached a convolution that cannot apply it")
                 xn = x.gn_apply()
                 y = self.conv(xn, prefix, taps=taps, stride=stride, pad_tl=pad_tl, ups=ups, rowvec=rowvec, residual=residual, out=out,
-                              out_f32=out_f32, alpha=alpha, name=name, stats=stats, feeds=feeds, mirror=mirror, gnp_into=gnp_into)
+                              out_f32=out_f32, alpha=alpha, name=name, stats=stats, feeds=feeds, mirror=mirror, gnp_into=gnp_into,
+                              tail=tail)
                 self.free(xn)
                 return y
         a, tmp = x.t, None
@@ -1013,7 +1067,8 @@ class Emitter:
             splitk=splitk, workspace=ws, name=name,
             **(into if into is not None else dict(gn_partial=gnp, gn_slot_rows=gn_slot if splitk > 1 else 0)),
             w_phase_stride=(N * wt.stride(0)) if subpix else 0,
-            out16=m16, a_wrap=x.C if parts == ops.PARTS_2W else 0, a_gn=x.gn_in, a_gn_silu=x.gn_silu))
+            out16=m16, a_wrap=x.C if parts == ops.PARTS_2W else 0, a_gn=x.gn_in, a_gn_silu=x.gn_silu,
+            a3=tail[0].t if tail is not None else None, C3=tail[0].C if tail is not None else 0))
         self.arena.free(ws)
         self.arena.free(tmp)
         return Act(out, x.B, OH, OW, N, gnp, gn_slot=gn_slot)

@@ -77,6 +77,7 @@ class IgemmParams(C.Structure):
         ("a_wrap", C.c_int32),
         ("a_gn", C.c_void_p), ("a_gn_silu", C.c_int32),
         ("gn_slot_rows", C.c_int32), ("gn_ld", C.c_int32),
+        ("a3", C.c_void_p), ("C3", C.c_int32), ("ld3", C.c_int32),
     ]
 
 

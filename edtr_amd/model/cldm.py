@@ -247,7 +247,7 @@ class CldmEngine:
 
         # ---- step program
         self.step_prog = Program("cldm.step")
-        em = Emitter(self.step_prog, self.arena, store, dt, mode, pol)
+        em = Emitter(self.step_prog, self.arena, store, dt, mode, pol, ktail=owner.precision == "fast")
         hw = h * w
         cin_c = ca.in_channels + ca.hint_channels
         x8c = em.new(B * hw, arch_round8(cin_c))
@@ -260,7 +260,7 @@ class CldmEngine:
         tab_u, offs_u = nets.emit_time_rows(em, "unet.", ua, self.t_in, B)
         # ControlNet (lane 1, own arena) is independent of the UNet encoder + middle block (lane 0): two graph branches
         self.arena_cn = Arena(dev)
-        em_cn = Emitter(self.step_prog, self.arena_cn, store, dt, mode, pol)
+        em_cn = Emitter(self.step_prog, self.arena_cn, store, dt, mode, pol, ktail=owner.precision == "fast")
         self.step_prog.fork()
         self.step_prog.set_lane(1)
         ctrl = nets.emit_controlnet(em_cn, "controlnet.", ca, Act(x8c, B, h, w, x8c.shape[1]), tab_c, offs_c, self.kv_c,
@@ -298,7 +298,7 @@ class _PartEngineBase:
         self.arena = Arena(dev)
         self.prog = Program(name)
         mode, dt = part._mode()
-        em = Emitter(self.prog, self.arena, store, dt, mode, part._policy())
+        em = Emitter(self.prog, self.arena, store, dt, mode, part._policy(), ktail=part.precision == "fast")
         f32 = torch.float32
         self.x_in = torch.zeros((B, a.in_channels, h, w), dtype=f32, device=dev)
         self.t_in = torch.zeros((B,), dtype=torch.int64, device=dev)
@@ -400,7 +400,7 @@ class VaeEngine:
         self.prog = Program(f"vae.{kind}" + (".tiled" if tile_size else ""))
         self.nan_probe = None      # tiled form: (rows, cols) index tensors of the first output pixel of every tile
         self.noise_in = None       # encoder with sample=True: the N(0, 1) draw of DiagonalGaussianDistribution.sample()
-        em = Emitter(self.prog, self.arena, store, dt, mode, _policy_for(owner, section))
+        em = Emitter(self.prog, self.arena, store, dt, mode, _policy_for(owner, section), ktail=owner.precision == "fast")
         if kind == "encode" and os.environ.get("EDTR_AMD_BRANCH16_ENC", "1") == "0":
             # mixed mode, A/B switch: the ENCODER with its branch-internal tensors in fp32.  z_pre (the conditioning of every denoise step
             # and the start of the trajectory) is 6.9e-4 from the reference instead of 8.0e-4 of its 1e-3 budget, the final latent /

@@ -108,14 +108,20 @@ def emit_resblock(em: Emitter, P: str, l: Layer, x: Act, table: torch.Tensor, of
     em.free(n1)
     n2 = em.group_norm(h, p + "out_layers.0.", 1e-5, True, feeds=("res.conv2",), conv_n=l.cout, take=True)
     em.free(h)
-    if l.cin != l.cout:
+    # a width-changing block's 1x1 skip convolution: K more columns of conv2's own product (its centre tap) wherever the halo tile takes
+    # a K tail at this shape — no launch, no 16-bit round trip of the skip tensor; otherwise a launch of its own and conv2's residual
+    tail = (x, p + "skip_connection.") if l.cin != l.cout and em.tail_ok(n2, p + "out_layers.3.", x) else None
+    if tail is not None:
+        skip = None
+    elif l.cin != l.cout:
         skip = em.conv(x, p + "skip_connection.", taps=1, name="res.skip1x1").t
     else:
         skip = x.t
-    y = em.conv(n2, p + "out_layers.3.", residual=skip, out=out, name="res.conv2", stats=out is None, mirror=mirror, gnp_into=gnp_into)
+    y = em.conv(n2, p + "out_layers.3.", residual=skip, out=out, name="res.conv2", stats=out is None, mirror=mirror, gnp_into=gnp_into,
+                tail=tail)
     into_done = em.gnp_into_done
     em.free(n2)
-    if l.cin != l.cout:
+    if l.cin != l.cout and tail is None:
         em.free(skip)
     em.gnp_into_done = into_done
     return y
@@ -407,13 +413,16 @@ def _g_vae_resblock(em: Emitter, p: str, l: VaeLayer, x: Act):
     em.free(n1)
     n2 = yield from _g_norm(em, h, p + "norm2.", True, ("vae.conv2",), conv_n=l.cout, take=True)
     em.free(h)
-    if l.cin != l.cout:
+    tail = (x, p + "nin_shortcut.") if l.cin != l.cout and em.tail_ok(n2, p + "conv2.", x) else None      # (emit_resblock: the skip as a K tail)
+    if tail is not None:
+        skip = None
+    elif l.cin != l.cout:
         skip = em.conv(x, p + "nin_shortcut.", taps=1, name="vae.nin_shortcut").t
     else:
         skip = x.t
-    y = em.conv(n2, p + "conv2.", residual=skip, name="vae.conv2", stats=True)
+    y = em.conv(n2, p + "conv2.", residual=skip, name="vae.conv2", stats=True, tail=tail)
     em.free(n2)
-    if l.cin != l.cout:
+    if l.cin != l.cout and tail is None:
         em.free(skip)
     return y
 

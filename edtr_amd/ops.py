@@ -72,9 +72,14 @@ def make_igemm(*, dtype: torch.dtype, a1: torch.Tensor, w: torch.Tensor, out: to
                row_stats: Optional[torch.Tensor] = None, ln_stats: Optional[torch.Tensor] = None, ln_C: int = 0, ln_valid: int = 0,
                ln_eps: float = 1e-5, ln_c1: Optional[torch.Tensor] = None, ln_c2: Optional[torch.Tensor] = None,
                w_phase_stride: int = 0, out16: Optional[torch.Tensor] = None, a_wrap: int = 0, a_gn: Optional[torch.Tensor] = None,
-               a_gn_silu: bool = True, gn_slot_rows: int = 0, gn_ld: int = 0, name: str = "igemm") -> Rec:
+               a_gn_silu: bool = True, gn_slot_rows: int = 0, gn_ld: int = 0, a3: Optional[torch.Tensor] = None, C3: int = 0,
+               name: str = "igemm") -> Rec:
     p = L.IgemmParams()
-    p.dtype, p.taps, p.M, p.N, p.K = dt_code(dtype), taps, M, N, taps * (C1 + C2)
+    if a3 is None:
+        C3 = 0
+    p.dtype, p.taps, p.M, p.N, p.K = dt_code(dtype), taps, M, N, taps * (C1 + C2) + C3
+    if a3 is not None:                    # K tail of a 3x3 convolution: C3 more columns read at the output pixel itself (the 1x1 skip)
+        p.a3, p.C3, p.ld3 = ptr(a3), C3, a3.stride(0)
     p.n_valid, p.Z, p.zdiv = n_valid, Z, zdiv
     p.a1, p.a2, p.C1, p.C2, p.ld1, p.ld2 = ptr(a1), ptr(a2), C1, C2, ld1, ld2
     p.a_zs_outer, p.a_zs_inner = a_zs
@@ -110,16 +115,42 @@ def make_igemm(*, dtype: torch.dtype, a1: torch.Tensor, w: torch.Tensor, out: to
     # algorithmic HBM bytes: every operand once (a conv reads its input image once, not once per tap)
     a_rows = (M // (p.OH * p.OW)) * p.IH * p.IW if spatial else M
     n_out = N // 2 if act == L.ACT_GEGLU else N
-    nbytes = Z * (2.0 * a_rows * (C1 + C2) + 2.0 * N * p.K + (4.0 if out_f32 else 2.0) * M * n_out
+    nbytes = Z * (2.0 * a_rows * (C1 + C2) + 2.0 * M * C3 + 2.0 * N * p.K + (4.0 if out_f32 else 2.0) * M * n_out
                   + ((4.0 if residual_f32 else 2.0) * M * n_out if residual is not None else 0.0))
     rec = Rec(L.load().edtr_igemm, (ct.byref(p),), (p, a1, a2, w, out, bias_n, bias_m, rowvec, residual, workspace,
-                                                    gn_partial, vt_out, row_stats, ln_stats, ln_c1, ln_c2, out16, a_gn), name, flops, nbytes)
+                                                    gn_partial, vt_out, row_stats, ln_stats, ln_c1, ln_c2, out16, a_gn, a3), name, flops, nbytes)
     rec.tag = (f"taps{taps} M{M} N{N} K{p.K} Z{Z}" + (f" C2={C2}" if C2 else "") + (f" s{p.stride}" if spatial and p.stride != 1 else "")
                + ((" up2" if p.upsample2x == 1 else " up2sp") if spatial and p.upsample2x else "") + (f" sk{splitk}" if splitk > 1 else "") + (f" act{act}" if act else "")
                + (" f32" if out_f32 else "") + (" gnp" if gn_partial is not None else "") + (" vT" if vt_out is not None else "")
                + (" ln" if ln_stats is not None else "") + (" rs" if row_stats is not None else "")
-               + (" m16" if out16 is not None else "") + (" 2w" if a_wrap else "") + (" gnin" if a_gn is not None else ""))
+               + (" m16" if out16 is not None else "") + (" 2w" if a_wrap else "") + (" gnin" if a_gn is not None else "")
+               + (" kt" if a3 is not None else ""))
     return rec
+
+
+def ktail_plan(dtype: torch.dtype, B: int, H: int, W: int, C1: int, ld1: int, N: int, C3: int, ld3: int, splitk: int = 1,
+               a_gn: bool = False) -> int:
+    """edtr_igemm_plan for the 3x3 / stride 1 / pad 1 convolution of a [B, H, W, C1] activation with a K tail of C3 columns and the
+    library's own tile choice: the tile that would run (16 / 17 / 20), or < 0 where no tile takes the tail at that shape.  Shapes
+    only (the pointers are placeholders), no launch, no device."""
+    p = L.IgemmParams()
+    M, fake = B * H * W, 0x1000
+    p.dtype, p.taps, p.M, p.N, p.K, p.Z, p.zdiv = dt_code(dtype), 9, M, N, 9 * C1 + C3, 1, 1
+    p.a1, p.C1, p.ld1, p.a3, p.C3, p.ld3 = fake, C1, ld1, fake, C3, ld3
+    p.IH, p.IW, p.OH, p.OW, p.stride, p.pad_t, p.pad_l = H, W, H, W, 1, 1, 1
+    p.w, p.ldw, p.out, p.ldc, p.alpha, p.bias_n = fake, 9 * C1 + C3, fake, N, 1.0, fake
+    p.rows_per_image, p.splitk = H * W, splitk
+    if splitk > 1:
+        p.workspace, p.workspace_bytes = fake, splitk * M * N * 4
+    if a_gn:
+        p.a_gn, p.a_gn_silu = fake, 1
+    return int(L.load().edtr_igemm_plan(ct.byref(p)))
+
+
+def ktail_enabled() -> bool:
+    """EDTR_KTAIL=0 keeps the 1x1 skip convolutions of the width-changing ResBlocks as launches of their own (A/B runs); the default
+    folds them into conv2 as a K tail (edtr_hip.h: a3) wherever the halo tile of that shape takes one."""
+    return os.environ.get("EDTR_KTAIL", "1") != "0"
 
 
 LN_FOLD_MAX_BATCH = 4     # UNet / ControlNet LayerNorm fold: on by default up to this batch size (engine.Emitter.ln_fold_ok has the measurements)

@@ -88,6 +88,14 @@ int edtr_device_info(int* compute_units, int64_t* hbm_bytes, char* arch_name, in
  *   form, see w_phase_stride);  channels c < C1 come from a1 (pixel stride
  *   ld1), the rest from a2 (pixel stride ld2) — the fused channel concat.
  *   taps == 1 and OH == 0: plain row-major matrix, A(z, m, k) = a1[z][m*ld1 + k] (concat too).
+ *   K tail (a3 != NULL and C3 > 0; taps == 9, stride 1, pad 1, no upsample, C2 == 0): K = 9*C1 + C3, and columns
+ *   k >= 9*C1 read a3[pixel(m)*ld3 + (k - 9*C1)] — the output pixel itself, no halo, no padding: a 1x1
+ *   convolution of a second tensor summed into the same fp32 accumulator (the skip connection of a
+ *   width-changing ResBlock, reference model/unet.py:219-223, model/vae.py:103-114, whose product is then
+ *   never rounded to 16 bits or stored).  The weight rows are [9*C1 | C3] (ldw >= K), bias_n is the sum of the
+ *   two biases.  a_gn applies to the 9-tap operand only.  Halo tiles 16 (16 x 16 patches and the 8 x 8-image
+ *   form, split-K allowed: every split takes its proportional share of the C3/64 tail chunks), 17 and 20;
+ *   C3 % 64 == 0, ld3 % 8 == 0; any other tile, stride, upsample, concat or a_wrap is EDTR_E_UNSUPPORTED.
  * W operand: row-major [N][K] (K contiguous, i.e. conv weights packed [Cout][ky][kx][Cin]).
  *   Rows n >= n_valid read as zero.
  * z (grid.z) offsets: operand_offset = (z / zdiv) * zs_outer + (z % zdiv) * zs_inner (elements).
@@ -221,6 +229,10 @@ typedef struct edtr_igemm_params {
     int32_t gn_ld;          /* channels per gn_partial slot (ABI 10): 0 = N; > N when the output is a column slice of a concatenation whose
                                halves share one buffer of slots — gn_partial then points at this launch's first column inside a slot
                                (slot s, column n of this launch at gn_partial[(s * gn_ld + n) * 2]); edtr_add_stats writes the other half */
+    /* K tail of a 3x3 convolution (additive in ABI 10; see "K tail" in the A-operand comment above): C3 more columns read at the
+     * output pixel itself from a3 (pixel stride ld3).  a3 == NULL or C3 == 0: no tail. */
+    const void* a3;
+    int32_t C3, ld3;
 } edtr_igemm_params;
 
 int edtr_igemm(const edtr_igemm_params* p, edtr_stream_t stream);
