@@ -63,10 +63,7 @@ __global__ void __launch_bounds__(256) filter2d_kernel(const float* x, const flo
 
 // ---- F.interpolate(size=, align_corners=False) -------------------------------------------------------------------------------------
 
-// ATen's area_pixel_compute_source_index: scale * (dst + 0.5) - 0.5, each step rounded to fp32
-__device__ __forceinline__ float source_index(float scale, int dst) {
-    return add_rn(mul_rn(scale, add_rn((float)dst, 0.5f)), -0.5f);
-}
+// (the source coordinate is glue.h's source_index)
 
 // the cubic convolution weights for A = -0.75 (A + 2 = 1.25, A + 3 = 2.25, 5 A = -3.75, 8 A = -6, 4 A = -3: all exact)
 __device__ __forceinline__ float cubic1(float v) {      // |v| <= 1: ((A + 2) v - (A + 3)) v v + 1

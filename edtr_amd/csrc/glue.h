@@ -69,17 +69,28 @@ __device__ __forceinline__ void index_lambda(float src, int n, int& idx, float& 
     t = fminf(fmaxf(add_rn(src, -(float)idx), 0.0f), 1.0f);
 }
 
+// ATen's area_pixel_compute_source_index for align_corners = False: scale * (dst + 0.5) - 0.5, each step rounded to fp32
+// (F.interpolate(size=) of degrade.hip and the coarse-logits launch of labels.hip; bilinear clamps the result at 0, bicubic does not)
+__device__ __forceinline__ float source_index(float scale, int dst) {
+    return add_rn(mul_rn(scale, add_rn((float)dst, 0.5f)), -0.5f);
+}
+
+// the bilinear blend of the four taps v[row][column] under the two lambdas, columns first: seven products and sums, each rounded
+__device__ __forceinline__ float blend_taps(float v00, float v01, float v10, float v11, float ty, float tx) {
+#pragma clang fp contract(off)
+    const float wy0 = add_rn(1.0f, -ty), wx0 = add_rn(1.0f, -tx);
+    const float top = add_rn(mul_rn(wx0, v00), mul_rn(tx, v01));
+    const float bot = add_rn(mul_rn(wx0, v10), mul_rn(tx, v11));
+    return add_rn(mul_rn(wy0, top), mul_rn(ty, bot));
+}
+
 // F.interpolate(mode="bilinear") from the point where the two index_lambda results are known: the four taps of plane `src` [ih][iw],
 // columns blended first.  (How the source coordinate is formed differs between the callers and stays with them.)
 __device__ __forceinline__ float bilinear_blend(const float* src, int ih, int iw, int y0, float ty, int x0, float tx) {
-#pragma clang fp contract(off)
     const int y1 = y0 + (y0 < ih - 1 ? 1 : 0), x1 = x0 + (x0 < iw - 1 ? 1 : 0);
-    const float wy0 = add_rn(1.0f, -ty), wx0 = add_rn(1.0f, -tx);
     const float* r0 = src + (int64_t)y0 * iw;
     const float* r1 = src + (int64_t)y1 * iw;
-    const float top = add_rn(mul_rn(wx0, r0[x0]), mul_rn(tx, r0[x1]));
-    const float bot = add_rn(mul_rn(wx0, r1[x0]), mul_rn(tx, r1[x1]));
-    return add_rn(mul_rn(wy0, top), mul_rn(ty, bot));
+    return blend_taps(r0[x0], r0[x1], r1[x0], r1[x1], ty, tx);
 }
 
 // the lanes of a wave below `lane`, as a ballot mask: popcount(vote & lanes_below(lane)) is a lane's place in an ordered compaction

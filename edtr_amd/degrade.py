@@ -148,6 +148,20 @@ def _check_size(size) -> Tuple[int, int]:
     return oh, ow
 
 
+def bilinear_planes_reference(x: np.ndarray, oh: int, ow: int) -> np.ndarray:
+    """The bilinear branch of `resize_reference` on fp32 [B, C, ih, iw] with any number of planes (`labels.upsample_logits_reference`
+    blends logit planes with it): the source index clamped at 0, `_index_lambda`, columns blended first, every step rounded."""
+    ih, iw = x.shape[2:]
+    y0, ty = _index_lambda(np.maximum(_source_index(ih, oh), F32(0)), ih)
+    x0, tx = _index_lambda(np.maximum(_source_index(iw, ow), F32(0)), iw)
+    y1, x1 = y0 + (y0 < ih - 1), x0 + (x0 < iw - 1)
+    wy0, wx0 = (F32(1) - ty)[:, None], F32(1) - tx
+    ty = ty[:, None]
+    top = wx0 * x[:, :, y0][:, :, :, x0] + tx * x[:, :, y0][:, :, :, x1]
+    bot = wx0 * x[:, :, y1][:, :, :, x0] + tx * x[:, :, y1][:, :, :, x1]
+    return (wy0 * top + ty * bot).astype(F32)
+
+
 def resize_reference(x, size, mode: str) -> np.ndarray:
     """F.interpolate(x, size=size, mode=mode) (align_corners=False, no antialias) with edtr_hip.h's operation order."""
     x = _batch(x)
@@ -167,16 +181,9 @@ def resize_reference(x, size, mode: str) -> np.ndarray:
                         s = s + x[:, :, yy, xx]
                 out[:, :, i, j] = s / F32((ye[i] - ys[i]) * (xe[j] - xs[j]))
         return out
-    sy, sx = _source_index(ih, oh), _source_index(iw, ow)
     if mode == "bilinear":
-        y0, ty = _index_lambda(np.maximum(sy, F32(0)), ih)
-        x0, tx = _index_lambda(np.maximum(sx, F32(0)), iw)
-        y1, x1 = y0 + (y0 < ih - 1), x0 + (x0 < iw - 1)
-        wy0, wx0 = (F32(1) - ty)[:, None], F32(1) - tx
-        ty = ty[:, None]
-        top = wx0 * x[:, :, y0][:, :, :, x0] + tx * x[:, :, y0][:, :, :, x1]
-        bot = wx0 * x[:, :, y1][:, :, :, x0] + tx * x[:, :, y1][:, :, :, x1]
-        return (wy0 * top + ty * bot).astype(F32)
+        return bilinear_planes_reference(x, oh, ow)
+    sy, sx = _source_index(ih, oh), _source_index(iw, ow)
     y0, ty = _index_lambda(sy, ih)
     x0, tx = _index_lambda(sx, iw)
     wy, wx = _cubic_weights(ty), _cubic_weights(tx)

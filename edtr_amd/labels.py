@@ -1,10 +1,10 @@
 """Segmentation labels on the device: what sits between the restored image and the figure the reference's segmentation test reports
 (main/seg/test_edtr.py:139-174), and the geometry its data sets apply to image and mask together (datasets/segmentation.py:82-114,
-207-215).  A label map is uint8 [H, W] (255 = "ignore"), an image uint8 [h, w, 3]; the four launches are include/edtr_hip.h "Label
+207-215).  A label map is uint8 [H, W] (255 = "ignore"), an image uint8 [h, w, 3]; the five launches are include/edtr_hip.h "Label
 maps" (kernels in csrc/labels.hip).  The task networks stay outside: `evaluate` takes logits from any callable.
 
 Three layers, as in `degrade`:
-  * `resize_nearest`, `window`, `confusion`, `colorize`: thin wrappers over the launches (torch tensors on the device, the caller's
+  * `resize_nearest`, `window`, `confusion`, `coarse_confusion`, `colorize`: thin wrappers over the launches (torch tensors on the device, the caller's
     stream).  With inputs already on the device nothing waits for the device; a numpy input is uploaded first (one host -> device
     copy), and `confusion`'s ``sizes`` travel in a pinned, non-blocking upload;
   * `*_reference`: the numpy restatement of each.  They are the NORMATIVE definition: the kernels are tested against them by
@@ -14,7 +14,9 @@ Three layers, as in `degrade`:
     crop and flip from ``numpy.random.default_rng([seed, image_id, GEOMETRY_WORD])`` — a stream of its own, so that
     `degrade.draw_params` / `draw_params2` return what they returned before.
 
-`prepare_pair` / `paired_mask` are the data sets' `load_items`, `evaluate` the test loop's tail."""
+`prepare_pair` / `paired_mask` are the data sets' `load_items`, `evaluate` the test loop's tail.  `coarse_confusion` takes the logits
+at the network's stride and scores their bilinear upsample (model/deeplabv3.py:44-47) without storing it; `assemble_segmenter` puts
+the reference's segmenter together from its learned parts so that it ends there (`CoarseLogits`)."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -111,6 +113,53 @@ def confusion_reference(logits, target, n: Optional[int] = None, sizes=None, ret
     inds = n * target[keep].astype(np.int64) + pred[keep]
     mat = np.bincount(inds, minlength=n * n).reshape(n, n).astype(np.int64)
     return (mat, pred) if return_pred else mat
+
+
+LOGIT_TYPES = ("float32", "float16", "bfloat16")
+
+
+def _round_to(v: np.ndarray, dtype: str) -> np.ndarray:
+    """fp32 ``v`` rounded to nearest even to ``dtype`` and widened back to fp32 (bfloat16 in integer arithmetic on the bits; a NaN
+    stays a NaN)"""
+    if dtype == "float32":
+        return v
+    with np.errstate(over="ignore"):
+        if dtype == "float16":
+            return v.astype(np.float16).astype(np.float32)
+    u = np.ascontiguousarray(v).view(np.uint32)
+    r = ((u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) & np.uint32(0xFFFF0000)).view(np.float32)
+    return np.where(np.isnan(v), np.float32(np.nan), r)
+
+
+def upsample_logits_reference(coarse, size, dtype: str = "float32") -> np.ndarray:
+    """fp32 [B, n, H, W]: what `F.interpolate(coarse, size=size, mode="bilinear", align_corners=False)` hands to argmax, by the
+    written rule of `degrade.resize_reference` (ATen's fp32 arithmetic, every product and sum rounded) for any number of planes.
+    ``dtype`` is the type the logits are held in: "float16" / "bfloat16" values (given as fp16, or as fp32 that holds them — bf16
+    travels widened) are widened exactly, blended in fp32, and the blend is rounded once to that type, which is what makes many more
+    ties than fp32 has."""
+    from . import degrade
+    if dtype not in LOGIT_TYPES:
+        raise ValueError(f"dtype must be one of {LOGIT_TYPES}, got {dtype!r}")
+    x = np.asarray(coarse)
+    if x.ndim != 4 or x.dtype not in (np.float32, np.float16) or 0 in x.shape:
+        raise ValueError(f"expected fp32 / fp16 logits [B, n, ih, iw], got {x.dtype} {x.shape}")
+    x = np.ascontiguousarray(x.astype(np.float32))
+    if dtype != "float32" and not np.array_equal(_round_to(x, dtype), x, equal_nan=True):
+        raise ValueError(f"the logits hold values that are not {dtype} values")
+    H, W = _hw(size)
+    with np.errstate(invalid="ignore", over="ignore"):
+        return _round_to(degrade.bilinear_planes_reference(x, H, W), dtype)
+
+
+def coarse_confusion_reference(coarse, target, size=None, n: Optional[int] = None, sizes=None, return_pred: bool = False,
+                               dtype: str = "float32"):
+    """`confusion_reference` of `upsample_logits_reference`: ``coarse`` [B, n, ih, iw] stands for its upsample to ``size`` (default:
+    the extent of ``target`` uint8 [B, H, W]).  NORMATIVE for `coarse_confusion`: the launch equals it word for word, mat and pred."""
+    target = np.asarray(target)
+    if target.ndim != 3:
+        raise ValueError(f"expected a uint8 target [B, H, W], got {target.shape}")
+    return confusion_reference(upsample_logits_reference(coarse, target.shape[1:] if size is None else size, dtype), target, n, sizes,
+                               return_pred)
 
 
 def compute_iou(mat) -> np.ndarray:
@@ -356,19 +405,18 @@ def window(x, out_hw, origin=(0, 0), hflip: bool = False, vflip: bool = False, f
     return dst[:, :, 0] if flat else dst
 
 
-def confusion(logits, target, n: int = 21, sizes=None, mat=None, return_pred: bool = False, max_blocks: int = 0):
-    """`confusion_reference` on the device, one launch: ``logits`` a contiguous fp32 / fp16 / bf16 [B, n, H, W] tensor, ``target`` uint8
-    [B, H, W].  ``mat`` (int64 [n, n] on the device) is ADDED to and returned; without it a zeroed one is made.  ``max_blocks`` caps
-    the grid (0: the default cap).  Returns mat, or (mat, pred uint8 [B, H, W]) with ``return_pred``; nothing is brought to the host,
-    and with ``target`` on the device the call does not wait for it (a host ``target`` is uploaded first)."""
+def _confusion_args(what: str, logits, target, n, sizes, mat, return_pred: bool, full: bool):
+    """The argument checks `confusion` and `coarse_confusion` share; returns (target on the device, sizes, mat, pred or None).
+    ``full``: the target's extent must be the logits' (else any [B, H, W] is taken)."""
     import torch
-    from . import ops
     if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.ndim != 4 or not logits.is_contiguous():
-        raise TypeError("confusion takes a contiguous [B, n, H, W] logits tensor on the device")
+        raise TypeError(f"{what} takes a contiguous [B, n, H, W] logits tensor on the device")
     if logits.shape[1] != int(n):
         raise ValueError(f"{logits.shape[1]} logit planes for n = {n}")
     target = torch.as_tensor(target)
-    if target.dtype != torch.uint8 or tuple(target.shape) != (logits.shape[0],) + tuple(logits.shape[2:]):
+    fits = target.ndim == 3 and target.shape[0] == logits.shape[0] and (tuple(target.shape[1:]) == tuple(logits.shape[2:]) if full
+                                                                         else 0 not in target.shape)
+    if target.dtype != torch.uint8 or not fits:
         raise ValueError(f"target must be uint8 [B, H, W] matching the logits, got {target.dtype} {tuple(target.shape)}")
     target = target.to(logits.device).contiguous()
     if sizes is not None:
@@ -380,7 +428,28 @@ def confusion(logits, target, n: int = 21, sizes=None, mat=None, return_pred: bo
     elif mat.dtype != torch.int64 or tuple(mat.shape) != (int(n), int(n)) or not mat.is_contiguous() or mat.device != logits.device:
         raise TypeError(f"mat must be a contiguous int64 [{n}, {n}] tensor on the logits' device")
     pred = torch.empty(target.shape, dtype=torch.uint8, device=logits.device) if return_pred else None
+    return target, sizes, mat, pred
+
+
+def confusion(logits, target, n: int = 21, sizes=None, mat=None, return_pred: bool = False, max_blocks: int = 0):
+    """`confusion_reference` on the device, one launch: ``logits`` a contiguous fp32 / fp16 / bf16 [B, n, H, W] tensor, ``target`` uint8
+    [B, H, W].  ``mat`` (int64 [n, n] on the device) is ADDED to and returned; without it a zeroed one is made.  ``max_blocks`` caps
+    the grid (0: the default cap).  Returns mat, or (mat, pred uint8 [B, H, W]) with ``return_pred``; nothing is brought to the host,
+    and with ``target`` on the device the call does not wait for it (a host ``target`` is uploaded first)."""
+    from . import ops
+    target, sizes, mat, pred = _confusion_args("confusion", logits, target, n, sizes, mat, return_pred, full=True)
     ops.launch(ops.make_seg_confusion(logits=logits, target=target, mat=mat, sizes=sizes, pred=pred, max_blocks=int(max_blocks)))
+    return (mat, pred) if return_pred else mat
+
+
+def coarse_confusion(coarse, target, n: int = 21, sizes=None, mat=None, return_pred: bool = False, max_blocks: int = 0):
+    """`coarse_confusion_reference` on the device, one launch: `confusion` of the bilinear upsample of ``coarse`` (a contiguous fp32 /
+    fp16 / bf16 [B, n, ih, iw] tensor at the network's stride) to the extent of ``target`` (uint8 [B, H, W]), without the [B, n, H, W]
+    tensor ever being stored.  A 16-bit ``coarse`` is compared as `F.interpolate` would return it: blended in fp32, rounded to its
+    type.  ``sizes``, ``mat``, ``return_pred``, ``max_blocks``, the return value and what does not wait for the device: as `confusion`."""
+    from . import ops
+    target, sizes, mat, pred = _confusion_args("coarse_confusion", coarse, target, n, sizes, mat, return_pred, full=False)
+    ops.launch(ops.make_seg_confusion_coarse(coarse=coarse, target=target, mat=mat, sizes=sizes, pred=pred, max_blocks=int(max_blocks)))
     return (mat, pred) if return_pred else mat
 
 
@@ -441,11 +510,45 @@ def paired_mask(mask_u8, gt_hw, center_crop=None, device=None):
     return window(resize_nearest(mask_u8, (H, W), device=device), c, origin, fill=IGNORE)
 
 
+@dataclass
+class CoarseLogits:
+    """Logits still at the network's stride: ``logits`` [B, n, ih, iw] on the device and the extent ``size`` = (H, W) their bilinear
+    upsample (`F.interpolate(..., size=size, mode="bilinear", align_corners=False)`) would have.  `coarse_confusion` scores them
+    without that upsample being stored; `evaluate` takes one wherever it takes logits."""
+    logits: object
+    size: Tuple[int, int]
+
+    def __post_init__(self):
+        self.size = _hw(self.size)
+        if getattr(self.logits, "ndim", 0) != 4:
+            raise TypeError("CoarseLogits holds a [B, n, ih, iw] tensor")
+
+
+def assemble_segmenter(backbone, classifier, feature: str = "C5", normalize: bool = True):
+    """The body of the reference's `_SimpleSegmentationModel.forward` (model/deeplabv3.py:36-47) from its learned parts, without the
+    aux head and without the final upsample: a callable from a contiguous fp32 [1, 3, h, w] device tensor to `CoarseLogits` of
+    extent (h, w).  ``normalize``: `cls.normalize` with the ImageNet constants first (the reference's segmenters normalise inside
+    their forward; the input itself is not written); then ``backbone`` — a torch module that returns the feature tensor or a mapping
+    that holds it under ``feature`` — and ``classifier``, both plain torch and the user's.  No [B, n, h, w] tensor is allocated: what
+    `evaluate` does with the result is one `coarse_confusion` launch."""
+    def segnet(x):
+        import torch
+        from . import cls
+        with torch.no_grad():
+            size = tuple(x.shape[-2:])
+            feats = backbone(cls.normalize(x) if normalize else x)
+            return CoarseLogits(classifier(feats[feature] if hasattr(feats, "keys") else feats), size)
+
+    return segnet
+
+
 def evaluate(images, masks, segnet, n_classes: int = 21, return_preds: bool = False, palette=None):
     """The tail of the reference's segmentation test: for every image (fp32 [3, h, w] or [1, 3, h, w] on the device, as
     `evalutil.restore_dataset` returns them) one call of ``segnet`` — any callable from [1, 3, h, w] fp32 to logits [1, n, h, w], or to
     a mapping with key "out" as torchvision's models return — and one `confusion` launch into a shared matrix against the uint8
-    [h, w] mask; with ``return_preds`` also the argmax and its colour map.  One device -> host copy at the end; masks that are not on
+    [h, w] mask; with ``return_preds`` also the argmax and its colour map.  Where ``segnet`` returns `CoarseLogits` (itself or
+    under "out"; `assemble_segmenter` does), the launch is `coarse_confusion` against the mask, whose extent must be the one the
+    coarse logits stand for.  One device -> host copy at the end; masks that are not on
     the device yet cost one upload each, so hand device tensors in where the loop must not touch the host.  Returns
     {"mat": int64 [n, n], "iou": fp32 [n], "miou": float (in percent)} (and "preds", "colors": lists of device tensors)."""
     import torch
@@ -456,13 +559,17 @@ def evaluate(images, masks, segnet, n_classes: int = 21, return_preds: bool = Fa
     for img, mask in zip(images, masks):
         x = img if img.ndim == 4 else img[None]
         out = segnet(x)
-        logits = (out["out"] if hasattr(out, "keys") else out).contiguous()
+        out = out["out"] if hasattr(out, "keys") else out
+        coarse = isinstance(out, CoarseLogits)
+        logits = (out.logits if coarse else out).contiguous()
         m = torch.as_tensor(mask)
         if m.ndim != 2:
             raise ValueError(f"a mask is a uint8 [h, w] label map, got {tuple(m.shape)}")
+        if coarse and tuple(m.shape) != out.size:
+            raise ValueError(f"coarse logits that stand for {out.size[0]} x {out.size[1]} against a {m.shape[0]} x {m.shape[1]} mask")
         if mat is None:
             mat = torch.zeros((int(n_classes), int(n_classes)), dtype=torch.int64, device=logits.device)
-        res = confusion(logits, m[None], n_classes, mat=mat, return_pred=return_preds)
+        res = (coarse_confusion if coarse else confusion)(logits, m[None], n_classes, mat=mat, return_pred=return_preds)
         if return_preds:
             preds.append(res[1][0])
             colors.append(colorize(res[1][0], palette))

@@ -36,7 +36,7 @@ DECLARED_SYMBOLS = [
     "edtr_tile_gather", "edtr_tile_blend",
     "edtr_degrade_filter2d", "edtr_degrade_resize", "edtr_degrade_gaussian_noise", "edtr_degrade_jpeg",
     "edtr_degrade_poisson_noise", "edtr_degrade_sepblur", "edtr_degrade_usm_apply",
-    "edtr_seg_confusion", "edtr_label_resize_nearest", "edtr_label_window", "edtr_label_colorize",
+    "edtr_seg_confusion", "edtr_seg_confusion_coarse", "edtr_label_resize_nearest", "edtr_label_window", "edtr_label_colorize",
     "edtr_boxes_rank", "edtr_boxes_nms", "edtr_boxes_candidates", "edtr_boxes_filter_shift", "edtr_boxes_transform", "edtr_boxes_bilinear_scale",
     "edtr_coco_match",
     "edtr_cls_rank", "edtr_cls_fdist", "edtr_cls_commit", "edtr_cls_normalize", "edtr_cls_window",
@@ -305,6 +305,7 @@ def load() -> C.CDLL:
     lib.edtr_degrade_usm_apply.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]
     # label maps (edtr_hip.h "Label maps"): sizes_host is a ctypes int32 array (or None)
     lib.edtr_seg_confusion.argtypes = [i32, vp, vp, i32, i32, i32, i32, C.POINTER(i32), vp, vp, vp, i32, vp]
+    lib.edtr_seg_confusion_coarse.argtypes = [i32, vp, i32, i32, i32, i32, vp, i32, i32, C.POINTER(i32), vp, vp, vp, i32, vp]
     lib.edtr_label_resize_nearest.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp]
     lib.edtr_label_window.argtypes = [vp, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.edtr_label_colorize.argtypes = [vp, i32, i32, i32, vp, vp, vp]

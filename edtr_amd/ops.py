@@ -882,6 +882,15 @@ def make_degrade_usm_apply(*, x, blur, soft, out, weight: float, name="degrade.u
 _LOGITS_DT = {torch.float32: L.LOGITS_F32, torch.float16: L.LOGITS_F16, torch.bfloat16: L.LOGITS_BF16}
 
 
+def _seg_sizes(sizes, device):
+    """``sizes`` (None or one (h, w) per image) as the pair the confusion entry points take: a ctypes int32 host array and its device
+    copy, uploaded from pinned memory without waiting"""
+    if sizes is None:
+        return None, None
+    flat = [int(v) for hw in sizes for v in hw]
+    return (ct.c_int32 * len(flat))(*flat), torch.tensor(flat, dtype=torch.int32).pin_memory().to(device, non_blocking=True)
+
+
 def make_seg_confusion(*, logits, target, mat, sizes=None, pred=None, max_blocks: int = 0, name="labels.confusion") -> Rec:
     """int64 ``mat`` [n, n] += the confusion matrix of argmax(``logits`` [B, n, H, W], fp32 / fp16 / bf16) against uint8 ``target``
     [B, H, W]; ``sizes``: None or one (h, w) per image (uploaded here from pinned memory without waiting, and handed to the entry point as a host
@@ -890,14 +899,23 @@ def make_seg_confusion(*, logits, target, mat, sizes=None, pred=None, max_blocks
     B, n, H, W = logits.shape
     if logits.dtype not in _LOGITS_DT:
         raise TypeError(f"logits must be float32, float16 or bfloat16, got {logits.dtype}")
-    sizes_host = dsizes = None
-    if sizes is not None:
-        flat = [int(v) for hw in sizes for v in hw]
-        sizes_host = (ct.c_int32 * len(flat))(*flat)
-        dsizes = torch.tensor(flat, dtype=torch.int32).pin_memory().to(logits.device, non_blocking=True)      # (the host does not wait for it)
+    sizes_host, dsizes = _seg_sizes(sizes, logits.device)
     args = (_LOGITS_DT[logits.dtype], ptr(logits), ptr(target), B, n, H, W, sizes_host, ptr(dsizes), ptr(mat), ptr(pred), int(max_blocks))
     nbytes = float(logits.element_size() * logits.numel() + target.numel() * (2 if pred is not None else 1))
     return Rec(L.load().edtr_seg_confusion, args, (logits, target, sizes_host, dsizes, mat, pred), name, 0.0, nbytes)
+
+
+def make_seg_confusion_coarse(*, coarse, target, mat, sizes=None, pred=None, max_blocks: int = 0, name="labels.coarse_confusion") -> Rec:
+    """`make_seg_confusion` on ``coarse`` [B, n, ih, iw] logits (fp32 / fp16 / bf16) that stand for their bilinear upsample to the
+    extent of uint8 ``target`` [B, H, W]; ``sizes``, ``pred`` and ``max_blocks`` as there."""
+    B, n, ih, iw = coarse.shape
+    _, H, W = target.shape
+    if coarse.dtype not in _LOGITS_DT:
+        raise TypeError(f"logits must be float32, float16 or bfloat16, got {coarse.dtype}")
+    sizes_host, dsizes = _seg_sizes(sizes, coarse.device)
+    args = (_LOGITS_DT[coarse.dtype], ptr(coarse), B, n, ih, iw, ptr(target), H, W, sizes_host, ptr(dsizes), ptr(mat), ptr(pred), int(max_blocks))
+    nbytes = float(coarse.element_size() * coarse.numel() + target.numel() * (2 if pred is not None else 1))
+    return Rec(L.load().edtr_seg_confusion_coarse, args, (coarse, target, sizes_host, dsizes, mat, pred), name, 0.0, nbytes)
 
 
 def make_label_resize_nearest(*, src, dst, y_idx, x_idx, name="labels.resize_nearest") -> Rec:

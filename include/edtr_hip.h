@@ -954,6 +954,27 @@ int edtr_degrade_usm_apply(const float* x, const float* blur, const float* soft,
 int edtr_seg_confusion(int logits_dtype, const void* logits, const uint8_t* target, int B, int n, int H, int W,
                        const int32_t* sizes_host, const int32_t* sizes, int64_t* mat, uint8_t* pred, int max_blocks,
                        edtr_stream_t stream);
+/* edtr_seg_confusion on logits that are still at the network's stride: coarse [B][n][ih][iw] (contiguous, fp32 / fp16 / bf16) stands
+ * for F.interpolate(coarse, size=(H, W), mode="bilinear", align_corners=False), which is blended tile by tile on chip and never
+ * stored.  target, sizes_host / sizes, mat (ADDED to), pred, max_blocks, the argmax and counting rules, "pred is written for every
+ * pixel of every slot" and the error codes in their order are edtr_seg_confusion's; ih, iw <= 0 is EDTR_E_SHAPE like H, W.  Any
+ * ih, iw, H, W >= 1: up-scaling, down-scaling, non-integer ratios.
+ *   value   of plane c at (y, x), in fp32 with every product and sum rounded on its own (no FMA) — the bilinear branch of
+ *           edtr_degrade_resize: scale = float(in) / float(out); src = max(fadd(fmul(scale, fadd(dst, 0.5)), -0.5), 0);
+ *           i0 = min(floor(src), in - 1), i1 = i0 + (i0 < in - 1), t = clamp(fadd(src, -i0), 0, 1) per axis;
+ *           top = fadd(fmul(1 - tx, v[y0][x0]), fmul(tx, v[y0][x1])), bot alike on row y1; value = fadd(fmul(1 - ty, top), fmul(ty, bot))
+ *   16-bit  inputs are widened exactly, blended in fp32 and the blend is rounded to the input's type (nearest even) before the
+ *           comparison, as F.interpolate on a 16-bit tensor hands it to argmax; fp32 input compares the fp32 blend
+ * One launch: 256 lanes own a 16 x 64 tile of output pixels (a lane four consecutive pixels of a row); the (i0, i1, t) of the tile's
+ * rows and columns are formed once, and the coarse patch they span, all n planes, is staged in LDS as fp32 (the planes of one coarse
+ * position side by side, n padded to a multiple of 4: one 16-byte read brings four planes of a tap) while it fits 16 KiB — under
+ * strong down-scaling the same arithmetic reads its taps from memory, with the same result.  A 16-bit blend is rounded once.
+ * Workgroups stride over the tiles and add their histograms to mat once; integer sums: the result does not depend on the grid.
+ * replaces: F.interpolate(x, size=input_shape, mode="bilinear", align_corners=False) -> argmax(1) -> calculate_mat,
+ * model/deeplabv3.py:44-47, main/seg/test_edtr.py:156-159. */
+int edtr_seg_confusion_coarse(int logits_dtype, const void* coarse, int B, int n, int ih, int iw, const uint8_t* target, int H, int W,
+                              const int32_t* sizes_host, const int32_t* sizes, int64_t* mat, uint8_t* pred, int max_blocks,
+                              edtr_stream_t stream);
 /* src [in_h][in_w][channels] -> dst [out_h][out_w][channels], uint8, channels 1 or 3 (EDTR_E_UNSUPPORTED otherwise):
  * dst (y, x) = src (y_idx[y], x_idx[x]) with the int32 tables y_idx [out_h] / x_idx [out_w] on the device.  The host builds them by
  * Pillow's accumulating rule (ImagingScaleAffine: xo = 0.5 s; idx[x] = (int)xo; xo += s, in double, s = in / out), which is not
