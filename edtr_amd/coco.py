@@ -2,7 +2,8 @@
 to `CocoEvaluator.update` (utils/detection.py:422-480) and reports `mAP@[0.5:0.95]` and `mAP@0.5`.  Here the per-image half of that —
 pycocotools' `COCOeval.evaluateImg` for every label, IoU threshold and area range — is one launch per image that appends to a running
 record on the device (include/edtr_hip.h "Detection scores", csrc/coco.hip), and `accumulate` / `summarize` run on the host from ONE
-copy at the end.  The detector stays outside: `evaluate` takes any callable, as `labels.evaluate` takes any `segnet`.
+copy at the end — or on the device as well (`Records.accumulate` / `stats` / `result`, csrc/coco_acc.hip), from which 104 bytes are
+copied.  The detector stays outside: `evaluate` takes any callable, as `labels.evaluate` takes any `segnet`.
 
 pycocotools is not a dependency of this project, so — as with NMS in `boxes` — everything is pinned to the RULE written out below, which
 is `COCOeval.evaluateImg`, `accumulate`, `_summarizeDets` and `maskUtils.iou` for boxes.  `match_reference` is the normative numpy
@@ -47,6 +48,8 @@ MAX_DET, MAX_GT, MAX_LABELS = 1024, 1024, 256     # EDTR_COCO_MAX_*: one image's
 BRANCHES = ("skip_matched", "break", "tie", "eq_thr", "match_ignored", "crowd_again", "unmatched_out")
 DET_FIELDS = (("image", np.int32), ("label", np.int32), ("score", F32), ("rank", np.int32), ("match", np.uint64), ("ignore", np.uint64))
 GT_FIELDS = (("gt_image", np.int32), ("gt_label", np.int32), ("gt_ignore", np.uint8))
+ACC_TILE, ACC_MAX_ROWS = 1024, 1 << 22      # EDTR_COCO_ACC_*: the sort tile of `Records.accumulate` and the most rows it orders
+assert THRESHOLDS[0] == 0.5 and THRESHOLDS[5] == 0.75       # the device's summarize takes AP50 and AP75 at these two indices
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
@@ -334,6 +337,108 @@ def summarize(acc: dict) -> dict:
     return {"stats": stats, "mAP@[0.5:0.95]": 100.0 * float(stats[0]), "mAP@0.5": 100.0 * float(stats[1])}
 
 
+_host_accumulate, _host_summarize = accumulate, summarize
+
+
+def order_keys(scores) -> np.ndarray:
+    """uint32 whose ascending order, ties kept, is `argsort(-scores.astype(F64), kind="mergesort")` — the order `accumulate` puts the
+    scores in.  A greater score has a smaller key; +0.0 and -0.0 share one; +inf has the smallest, -inf the greatest of the numbers;
+    every NaN has the one key after all of them.  NOT `boxes.score_keys`, which is ascending and puts the NaNs first in a descending
+    sort."""
+    s = np.ascontiguousarray(np.asarray(scores, dtype=F32).reshape(-1))
+    u = s.view(np.uint32)
+    key = np.where(u & np.uint32(0x80000000), u, ~(u | np.uint32(0x80000000)))
+    key = np.where(s == 0, np.uint32(0x7FFFFFFF), key)
+    return np.where(np.isnan(s), np.uint32(0xFFFFFFFF), key).astype(np.uint32)
+
+
+def accumulate_order_reference(records: dict, n_labels: int) -> dict:
+    """THE ORDER of `accumulate` (normative for `edtr_coco_order`).  For each (k, a, M) `accumulate` takes the images in ascending id,
+    in each the detections of label k with rank < M in rank order, and sorts them stably by `order_keys`.  A stable sort of a filtered
+    subsequence is the subsequence of the stable sort, so ONE order of all rows serves every (a, M, t): the rows with 0 <= label <
+    ``n_labels`` and 0 <= rank < KEEP, ascending by the composite key (label, `order_keys`(score), image, rank).  (image, label, rank) is
+    unique per row, so the key is a strict total order and the result does not depend on the sorting algorithm.
+    {"order": int32 [n_kept] row indices in key order, "seg_start": int32 [n_labels + 1]: label k's rows are order[seg_start[k] :
+    seg_start[k + 1]]}."""
+    label, rank = np.asarray(records["label"]), np.asarray(records["rank"])
+    rows = np.nonzero((label >= 0) & (label < int(n_labels)) & (rank >= 0) & (rank < KEEP))[0]
+    keys = order_keys(np.asarray(records["score"])[rows])
+    order = rows[np.lexsort((rank[rows], np.asarray(records["image"])[rows], keys, label[rows]))].astype(np.int32)
+    seg_start = np.searchsorted(label[order], np.arange(int(n_labels) + 1), side="left").astype(np.int32)
+    return {"order": order, "seg_start": seg_start}
+
+
+def accumulate_ordered_reference(records: dict, n_labels: int, order: Optional[dict] = None) -> dict:
+    """`accumulate` again, as `edtr_coco_accumulate` computes it: ONE forward walk of each label's segment of the order, no per-row
+    array of precisions.  Per (k, a, t, M), over the segment's rows with rank < M: the j-th true positive, with fp_j false positives
+    before it, has P_j = j / ((fp_j + j) + spacing(1)) and rc_j = j / npig in fp64.  `accumulate`'s pr falls between true positives
+    and `searchsorted(rc, recThr[r], "left")` lands on one, so after the envelope from the right
+        precision[r] = max{P_j : rc_j >= recThr[r]},   0 where no j qualifies.
+    recThr rises with r: P_j counts for r < cnt_j = #{r : recThr[r] <= rc_j} (from the fp64 division itself; ceil(recThr npig) is
+    wrong for 14 thresholds at npig = 100), is folded by max into bin cnt_j - 1 of 101, and a suffix maximum over the bins ends it.
+    recall = J / npig with J the true positives.  Equal to `accumulate` bit for bit (tests/test_coco_acc_cpu.py)."""
+    K = int(n_labels)
+    T, R, A, M = len(THRESHOLDS), len(RECALL_THRESHOLDS), len(AREA_RANGES), len(MAX_DETS)
+    precision, recall = -np.ones((T, R, K, A, M)), -np.ones((T, K, A, M))
+    o = accumulate_order_reference(records, K) if order is None else order
+    rank, match, ignore = np.asarray(records["rank"]), np.asarray(records["match"]), np.asarray(records["ignore"])
+    for k in range(K):
+        seg = np.asarray(o["order"])[int(o["seg_start"][k]):int(o["seg_start"][k + 1])]
+        g_ign = np.asarray(records["gt_ignore"])[np.asarray(records["gt_label"]) == k]
+        for a in range(A):
+            npig = int(np.count_nonzero((g_ign >> a) & 1 == 0))
+            if npig == 0:
+                continue
+            for m, max_det in enumerate(MAX_DETS):
+                sel = seg[rank[seg] < max_det]
+                for t in range(T):
+                    bit = np.uint64(4 * t + a)
+                    mt, ig = ((match[sel] >> bit) & np.uint64(1)).astype(bool), ((ignore[sel] >> bit) & np.uint64(1)).astype(bool)
+                    at = np.nonzero(mt & ~ig)[0]
+                    j = np.arange(1, at.size + 1).astype(F64)
+                    fp = np.cumsum(~mt & ~ig)[at].astype(F64)
+                    p, rc = j / ((fp + j) + np.spacing(1)), j / F64(npig)
+                    bins = np.zeros(R)
+                    np.maximum.at(bins, np.searchsorted(RECALL_THRESHOLDS, rc, side="right") - 1, p)
+                    precision[t, :, k, a, m] = np.maximum.accumulate(bins[::-1])[::-1]
+                    recall[t, k, a, m] = F64(at.size) / F64(npig)
+    return {"precision": precision, "recall": recall}
+
+
+def summarize_ordered_reference(acc: dict) -> dict:
+    """`summarize` with a summation order of its own that the shape alone decides (np.mean's pairwise order is numpy's private
+    business); `edtr_coco_summarize` equals this bit for bit.  For each statistic, over its slice x [t, r, k] (a recall statistic
+    has one r):
+      s_tk = the entries > -1 added over r in index order, from 0;  s_k = s_tk added over t in index order, from 0;
+      S = s_k added over k in index order, from 0;  the statistic = S / count of the entries > -1, or -1 where that is 0.
+    Within 1e-10 of `summarize`: two sums of at most 10 * 101 * 256 terms in [0, 1], each within n 2^-53 relative of the exact sum."""
+    def mean(x):                                                # x [t, r, k]
+        keep = x > -1
+        s_tk = np.zeros((x.shape[0], x.shape[2]))
+        for r in range(x.shape[1]):
+            s_tk = s_tk + np.where(keep[:, r], x[:, r], 0.0)
+        s_k = np.zeros(x.shape[2])
+        for t in range(x.shape[0]):
+            s_k = s_k + s_tk[t]
+        total = F64(0.0)
+        for k in range(x.shape[2]):
+            total = total + s_k[k]
+        count = int(np.count_nonzero(keep))
+        return float(total / F64(count)) if count else -1.0
+
+    p, rc, last = np.asarray(acc["precision"]), np.asarray(acc["recall"]), len(MAX_DETS) - 1
+
+    def ap(a, t=slice(None)):
+        return mean(p[t, :, :, a, last])
+
+    def ar(a, m):
+        return mean(rc[:, None, :, a, m])
+
+    stats = np.array([ap(0), ap(0, slice(0, 1)), ap(0, slice(5, 6)), ap(1), ap(2), ap(3), ar(0, 0), ar(0, 1), ar(0, 2), ar(1, 2), ar(2, 2), ar(3, 2)],
+                     dtype=F64)
+    return {"stats": stats, "mAP@[0.5:0.95]": 100.0 * float(stats[0]), "mAP@0.5": 100.0 * float(stats[1])}
+
+
 def scene(rng, n_det: int, n_gt: int, n_labels: int = 1, image_id: int = 0, label_span: Optional[Sequence[int]] = None):
     """A synthetic image's (det, gt) whose IoUs are small rationals, so that ties and threshold hits happen: a 128 x 128 image with
     every corner on a grid of 8.  A box: x0, y0 ~ integers(0, 15), w ~ integers(1, 1 + min(6, 16 - x0)) and h alike, in grid units; with
@@ -416,7 +521,106 @@ class Records:
         self.det_offset, self.gt_offset = self.offsets[0:1], self.offsets[1:2]
         self.thresholds = torch.from_numpy(THRESHOLDS.copy()).to(self.device)
         self.areas = torch.from_numpy(AREA_RANGES.copy()).to(self.device)
+        self.recall_thresholds = torch.from_numpy(RECALL_THRESHOLDS.copy()).to(self.device)
         self.image_ids: set = set()
+        self._acc = None                                        # the buffers of `accumulate`, made at its first call
+        self._acc_fresh = self._stats_fresh = False
+
+    @classmethod
+    def from_host(cls, records: dict, n_labels: int, device=None, capacity: Optional[int] = None, gt_capacity: Optional[int] = None) -> "Records":
+        """Records on the device from records on the host (`DET_FIELDS`, `GT_FIELDS`: what `to_host` and `merge_records` return), with
+        exactly their rows as capacity unless larger ones are given: the multi-rank flow is gather -> `merge_records` -> `from_host` -> `accumulate`.  The rows may
+        come in any order (the key of `accumulate_order_reference` decides), but (image, label, rank) must not repeat among the rows
+        with a label: the order would not be strict."""
+        import torch
+        cols = {name: np.ascontiguousarray(np.asarray(records[name]).astype(dtype).reshape(-1)) for name, dtype in DET_FIELDS + GT_FIELDS}
+        n, g = cols["image"].shape[0], cols["gt_image"].shape[0]
+        if any(cols[name].shape[0] != (n if (name, dtype) in DET_FIELDS else g) for name, dtype in DET_FIELDS + GT_FIELDS):
+            raise ValueError("every detection field takes one value per detection row and every ground-truth field one per ground truth")
+        known = cols["label"] >= 0
+        triples = np.stack([cols["image"][known], cols["label"][known], cols["rank"][known]], axis=1)
+        triples = triples[np.lexsort((triples[:, 2], triples[:, 1], triples[:, 0]))]
+        if np.any(np.all(triples[1:] == triples[:-1], axis=1)):
+            raise ValueError("records repeat an (image, label, rank) row: merge the shards with merge_records first")
+        if (capacity is not None and capacity < n) or (gt_capacity is not None and gt_capacity < g):
+            raise ValueError(f"{n} detection and {g} ground-truth rows do not fit capacities of {capacity} and {gt_capacity}")
+        rec = cls(max(n, 1) if capacity is None else capacity, n_labels, device, gt_capacity=max(g, 1) if gt_capacity is None else gt_capacity)
+        for name, col in cols.items():
+            if col.shape[0]:
+                rec.fields[name][:col.shape[0]].copy_(torch.from_numpy(col.view(np.int64) if col.dtype == np.uint64 else col))
+        rec.offsets.copy_(torch.tensor([n, g], dtype=torch.int32))
+        rec.image_ids = set(cols["image"].tolist()) | set(cols["gt_image"].tolist())
+        return rec
+
+    def _acc_state(self) -> dict:
+        """the output buffers of `accumulate` / `stats` in ONE device buffer, each with 8 guard bytes behind it, and the workspace"""
+        if self._acc is None:
+            import torch
+            from . import lib as L
+            ws = int(L.load().edtr_coco_accumulate_workspace(self.capacity, self.n_labels))
+            if ws <= 0:
+                raise ValueError(f"accumulate on the device orders at most {ACC_MAX_ROWS} rows, these records hold {self.capacity}")
+            T, R, K, A, M = len(THRESHOLDS), len(RECALL_THRESHOLDS), self.n_labels, len(AREA_RANGES), len(MAX_DETS)
+            sizes = (("precision", T * R * K * A * M, torch.float64), ("recall", T * K * A * M, torch.float64), ("stats", 13, torch.float64),
+                     ("order", self.capacity, torch.int32), ("seg_start", K + 1, torch.int32), ("n_kept", 1, torch.int32), ("status", 1, torch.int32))
+            layout, at = {}, 0
+            for name, count, dt in sizes:
+                nbytes = count * (8 if dt == torch.float64 else 4)
+                layout[name] = (at, nbytes, dt)
+                at = _round8(at + nbytes) + 8
+            buffer = torch.full((at,), self.GUARD, dtype=torch.uint8, device=self.device)
+            self._acc = {"buffer": buffer, "layout": layout, "workspace": torch.empty(ws, dtype=torch.uint8, device=self.device)}
+            self._acc.update({name: buffer[at:at + nbytes].view(dt) for name, (at, nbytes, dt) in layout.items()})
+        return self._acc
+
+    def accumulate(self) -> dict:
+        """`accumulate` of everything recorded so far, on the device: {"precision": fp64 [T, R, K, A, M], "recall": fp64 [T, K, A, M]} as
+        device tensors, bit for bit what `accumulate(self.to_host(), n_labels)` returns when each image was recorded once.  The sort of
+        `edtr_coco_order` and the walk of `edtr_coco_accumulate`; no host sync, and no row count reaches the host: an overflow of the
+        capacity shows in `result`.  The tensors are this object's and are overwritten by the next call."""
+        from . import ops
+        st = self._acc_state()
+        ops.launch(ops.make_coco_order(rec=self.fields, det_offset=self.det_offset, capacity=self.capacity, n_labels=self.n_labels,
+                                       workspace=st["workspace"], order=st["order"], seg_start=st["seg_start"], n_kept=st["n_kept"], status=st["status"]))
+        ops.launch(ops.make_coco_accumulate(order=st["order"], seg_start=st["seg_start"], rec=self.fields, capacity=self.capacity,
+                                            gt_offset=self.gt_offset, gt_capacity=self.gt_capacity, n_labels=self.n_labels,
+                                            recall_thresholds=self.recall_thresholds, workspace=st["workspace"], precision=st["precision"],
+                                            recall=st["recall"], status=st["status"]))
+        self._acc_fresh, self._stats_fresh = True, False
+        T, R, K, A, M = len(THRESHOLDS), len(RECALL_THRESHOLDS), self.n_labels, len(AREA_RANGES), len(MAX_DETS)
+        return {"precision": st["precision"].view(T, R, K, A, M), "recall": st["recall"].view(T, K, A, M)}
+
+    def order_to_host(self) -> dict:
+        """what the last `accumulate` sorted, copied to the host (for tests and debugging; `accumulate_order_reference`'s dict plus
+        the status word): {"order": int32 [n_kept], "seg_start": int32 [n_labels + 1], "status": int}"""
+        if self._acc is None or not self._acc_fresh:
+            raise RuntimeError("accumulate() has not run since the last update")
+        n_kept = int(self._acc["n_kept"].cpu()[0])
+        return {"order": self._acc["order"][:n_kept].cpu().numpy(), "seg_start": self._acc["seg_start"].cpu().numpy(),
+                "status": int(self._acc["status"].cpu()[0])}
+
+    def stats(self):
+        """The 12 statistics of `summarize_ordered_reference` as an fp64 [12] device tensor (`edtr_coco_summarize` on the result of
+        `accumulate`, which is run first if an image was recorded since).  No host sync."""
+        from . import ops
+        if not self._acc_fresh:
+            self.accumulate()
+        st = self._acc_state()
+        ops.launch(ops.make_coco_summarize(precision=st["precision"], recall=st["recall"], n_labels=self.n_labels, status=st["status"], out=st["stats"]))
+        self._stats_fresh = True
+        return st["stats"][:12]
+
+    def result(self) -> dict:
+        """{"stats": fp64 [12], "mAP@[0.5:0.95]", "mAP@0.5"} on the host after ONE copy of 104 bytes: the statistics and the status word.
+        Raises RuntimeError, as `to_host` does, if more rows were appended than a capacity holds."""
+        if not self._stats_fresh:
+            self.stats()
+        raw = self._acc["stats"].cpu().numpy()
+        if int(raw[12:].view(np.int64)[0]) != 0:
+            raise RuntimeError(f"more rows were appended than records of {self.capacity} detection and {self.gt_capacity} ground-truth rows hold: "
+                               f"pass a larger capacity")
+        stats = raw[:12].copy()
+        return {"stats": stats, "mAP@[0.5:0.95]": 100.0 * float(stats[0]), "mAP@0.5": 100.0 * float(stats[1])}
 
     def update(self, det: dict, target: dict) -> None:
         """Append one image: ``det`` = {"boxes" fp32 [n, 4], "scores" fp32 [n], "labels" [n]} and optionally "count" (int32 [1] on the
@@ -449,6 +653,7 @@ class Records:
         if area.ndim != 1 or area.shape[0] != g or crowd.ndim != 1 or crowd.shape[0] != g:
             raise ValueError("ground truth takes one area and one crowd flag per box")
         self.image_ids.add(image_id)
+        self._acc_fresh = self._stats_fresh = False
         if n == 0 and g == 0:
             return
         ops.launch(ops.make_coco_match(det_boxes=db, det_scores=ds, det_labels=dl, count=count, gt_boxes=gb, gt_labels=gl, gt_area=area.contiguous(),
@@ -473,14 +678,22 @@ class Records:
         return out
 
 
-def evaluate(images, targets, detnet, n_labels: int, mode: str = "direct", capacity: Optional[int] = None, **detect_kwargs) -> dict:
+def evaluate(images, targets, detnet, n_labels: int, mode: str = "direct", capacity: Optional[int] = None, *, accumulate: str = "host",
+             return_records: bool = False, **detect_kwargs) -> dict:
     """The tail of the reference's detection test (main/det/test_edtr.py:138-190): for every image (fp32 [3, h, w] on the device, as
     `evalutil.restore_dataset` returns them) `boxes.detect(image, detnet, mode, **detect_kwargs)` — in "direct" mode ``detnet([image])`` may
     also return the detection dict {"boxes", "scores", "labels"[, "count"]} itself — and one `Records.update` against the image's target,
     the reference's annotation dict ("boxes", "labels", "area", "iscrowd", "image_id").  No host sync in the loop and ONE device -> host
     copy at the end; targets that are not on the device yet cost one upload each.  ``capacity``: detection rows of the record, by
     default 100 per image (a detector's `detections_per_img`); more raise RuntimeError after the copy.
-    Returns {"stats": fp64 [12], "mAP@[0.5:0.95]", "mAP@0.5" (in percent, the reference's two keys), "precision", "recall", "records"}."""
+    Returns {"stats": fp64 [12], "mAP@[0.5:0.95]", "mAP@0.5" (in percent, the reference's two keys), "precision", "recall", "records"}.
+    ``accumulate``: "host" (the default) copies the records and runs `accumulate` and `summarize` there; "device" runs
+    `Records.accumulate` and `Records.result` instead — precision and recall are bit for bit the same, the statistics are those of
+    `summarize_ordered_reference` (within 1e-10 of `summarize`), and no record leaves the device: "records" is then returned only with
+    ``return_records`` (which the host path always does).  precision and recall are copied to the host for the same keys; a caller
+    that wants the one small copy alone keeps a `Records` and calls `result`."""
+    if accumulate not in ("host", "device"):
+        raise ValueError(f'accumulate is "host" or "device", got {accumulate!r}')
     images, targets = list(images), list(targets)
     if not images or len(images) != len(targets):
         raise ValueError(f"evaluate needs as many targets as images, got {len(targets)} for {len(images)}")
@@ -495,6 +708,12 @@ def evaluate(images, targets, detnet, n_labels: int, mode: str = "direct", capac
             gt_rows = max(1, sum(int(t["boxes"].shape[0]) for t in targets))
             rec = Records(capacity or KEEP * len(images), n_labels, det["boxes"].device, gt_capacity=gt_rows)
         rec.update(det, target)
+    if accumulate == "device":
+        acc = rec.accumulate()
+        out = {**rec.result(), "precision": acc["precision"].cpu().numpy(), "recall": acc["recall"].cpu().numpy()}
+        if return_records:
+            out["records"] = rec.to_host()
+        return out
     records = rec.to_host()
-    acc = accumulate(records, n_labels)
+    acc = _host_accumulate(records, n_labels)
     return {**summarize(acc), "precision": acc["precision"], "recall": acc["recall"], "records": records}

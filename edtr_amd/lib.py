@@ -19,6 +19,7 @@ SEG_MAX_CLASSES = 32        # EDTR_SEG_MAX_CLASSES: the largest n of edtr_seg_co
 NMS_MAX_BOXES = 32768       # EDTR_NMS_MAX_BOXES: the largest n of edtr_boxes_nms
 BOX_SHIFT, BOX_MUL, BOX_DIV, BOX_CLIP = 1, 2, 4, 8          # EDTR_BOX_*: flags of edtr_boxes_transform
 COCO_MAX_DET, COCO_MAX_GT, COCO_MAX_LABELS, COCO_MAX_THRESHOLDS, COCO_KEEP = 1024, 1024, 256, 10, 100     # EDTR_COCO_*: caps of edtr_coco_match
+COCO_ACC_TILE, COCO_ACC_MAX_ROWS = 1024, 1 << 22        # EDTR_COCO_ACC_*: the sort tile and the row cap of edtr_coco_order
 CLS_MAX_CLASSES, CLS_MAX_KEEP, CLS_MAX_TOPK, CLS_FD_CHUNK, CLS_FD_MAX_ELEMS = 65536, 8, 4, 4096, 1 << 28       # EDTR_CLS_*: caps of edtr_cls_*
 RPN_MAX_LEVELS, RPN_MAX_PRE_NMS, ROI_MAX_TAPS = 8, 4096, 64          # EDTR_RPN_* / EDTR_ROI_*: caps of edtr_rpn_* and edtr_roi_align
 
@@ -38,7 +39,7 @@ DECLARED_SYMBOLS = [
     "edtr_degrade_poisson_noise", "edtr_degrade_sepblur", "edtr_degrade_usm_apply",
     "edtr_seg_confusion", "edtr_seg_confusion_coarse", "edtr_label_resize_nearest", "edtr_label_window", "edtr_label_colorize",
     "edtr_boxes_rank", "edtr_boxes_nms", "edtr_boxes_candidates", "edtr_boxes_filter_shift", "edtr_boxes_transform", "edtr_boxes_bilinear_scale",
-    "edtr_coco_match",
+    "edtr_coco_match", "edtr_coco_accumulate_workspace", "edtr_coco_order", "edtr_coco_accumulate", "edtr_coco_summarize",
     "edtr_cls_rank", "edtr_cls_fdist", "edtr_cls_commit", "edtr_cls_normalize", "edtr_cls_window",
     "edtr_rpn_anchors", "edtr_rpn_select", "edtr_rpn_candidates", "edtr_roi_align",
 ]
@@ -318,6 +319,11 @@ def load() -> C.CDLL:
     lib.edtr_boxes_bilinear_scale.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, f32, vp]
     # detection scores (edtr_hip.h "Detection scores")
     lib.edtr_coco_match.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp]
+    lib.edtr_coco_accumulate_workspace.argtypes = [i32, i32]
+    lib.edtr_coco_accumulate_workspace.restype = i64         # bytes; host arithmetic only
+    lib.edtr_coco_order.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, i64, vp, vp, vp, vp, vp]
+    lib.edtr_coco_accumulate.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, i64, vp, vp, vp, vp]
+    lib.edtr_coco_summarize.argtypes = [vp, vp, i32, vp, vp, vp]
     # classification (edtr_hip.h "Classification"): topk_host is a ctypes int32 array, mean_host / std_host ctypes float arrays
     lib.edtr_cls_rank.argtypes = [i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp]
     lib.edtr_cls_fdist.argtypes = [i32, vp, vp, i32, i32, vp, vp]

@@ -1010,6 +1010,50 @@ def make_coco_match(*, det_boxes, det_scores, det_labels, count, gt_boxes, gt_la
     return Rec(L.load().edtr_coco_match, args, keep, name, 0.0, 28.0 * n + 26.0 * g)
 
 
+def _coco_workspace(workspace, capacity: int, n_labels: int) -> int:
+    need = int(L.load().edtr_coco_accumulate_workspace(int(capacity), int(n_labels)))
+    if need <= 0 or workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f"the workspace holds {workspace.numel() * workspace.element_size()} bytes, {capacity} rows of {n_labels} labels take {need}")
+    return workspace.numel() * workspace.element_size()
+
+
+def make_coco_order(*, rec: dict, det_offset, capacity: int, n_labels: int, workspace, order, seg_start, n_kept, status, name="coco.order") -> Rec:
+    """The rows of the record arrays ``rec`` below the device counter ``det_offset`` in the order of `coco.accumulate_order_reference`:
+    row indices into int32 ``order`` [capacity], each label's segment into int32 ``seg_start`` [n_labels + 1], their number into
+    ``n_kept`` and bit 0 of ``status`` for a counter past ``capacity`` (int32 [1] each).  ``workspace``: `edtr_coco_accumulate_workspace`
+    bytes."""
+    if capacity > rec["rank"].numel() or order.numel() < capacity or seg_start.numel() < n_labels + 1:
+        raise ValueError("the record arrays or the outputs are shorter than the capacity")
+    nbytes = _coco_workspace(workspace, capacity, n_labels)
+    args = (ptr(rec["image"]), ptr(rec["label"]), ptr(rec["score"]), ptr(rec["rank"]), ptr(det_offset), int(capacity), int(n_labels),
+            ptr(workspace), nbytes, ptr(order), ptr(seg_start), ptr(n_kept), ptr(status))
+    return Rec(L.load().edtr_coco_order, args, (rec, det_offset, workspace, order, seg_start, n_kept, status), name, 0.0, 52.0 * capacity)
+
+
+def make_coco_accumulate(*, order, seg_start, rec: dict, capacity: int, gt_offset, gt_capacity: int, n_labels: int, recall_thresholds, workspace,
+                         precision, recall, status, name="coco.accumulate") -> Rec:
+    """`coco.accumulate` from ``order`` / ``seg_start`` (`make_coco_order`) and the record arrays: fp64 ``precision`` [10, 101, n_labels, 4, 3]
+    and ``recall`` [10, n_labels, 4, 3], every element written; bit 1 of ``status`` for a ground-truth counter past ``gt_capacity``."""
+    if precision.numel() != 10 * 101 * n_labels * 12 or recall.numel() != 10 * n_labels * 12 or recall_thresholds.numel() != 101:
+        raise ValueError("precision is [10, 101, n_labels, 4, 3], recall [10, n_labels, 4, 3] and the recall thresholds are 101")
+    if capacity > rec["match"].numel() or gt_capacity > rec["gt_ignore"].numel() or order.numel() < capacity or seg_start.numel() < n_labels + 1:
+        raise ValueError("the record arrays or the order are shorter than the capacities")
+    nbytes = _coco_workspace(workspace, capacity, n_labels)
+    args = (ptr(order), ptr(seg_start), ptr(rec["match"]), ptr(rec["ignore"]), ptr(rec["rank"]), int(capacity), ptr(rec["gt_label"]),
+            ptr(rec["gt_ignore"]), ptr(gt_offset), int(gt_capacity), int(n_labels), ptr(recall_thresholds), ptr(workspace), nbytes,
+            ptr(precision), ptr(recall), ptr(status))
+    keep = (order, seg_start, rec, gt_offset, recall_thresholds, workspace, precision, recall, status)
+    return Rec(L.load().edtr_coco_accumulate, args, keep, name, 0.0, 8.0 * (precision.numel() + recall.numel()) + 40.0 * 24.0 * capacity)
+
+
+def make_coco_summarize(*, precision, recall, n_labels: int, status, out, name="coco.summarize") -> Rec:
+    """the 12 statistics of `coco.summarize_ordered_reference` into fp64 ``out`` [13]; out[12] takes ``status`` as an int64"""
+    if out.numel() != 13 or out.dtype != torch.float64 or precision.numel() != 10 * 101 * n_labels * 12 or recall.numel() != 10 * n_labels * 12:
+        raise ValueError("out is fp64 [13], precision [10, 101, n_labels, 4, 3] and recall [10, n_labels, 4, 3]")
+    args = (ptr(precision), ptr(recall), int(n_labels), ptr(status), ptr(out))
+    return Rec(L.load().edtr_coco_summarize, args, (precision, recall, status, out), name, 0.0, 8.0 * (precision.numel() + recall.numel()))
+
+
 # -- classification (edtr_hip.h "Classification"; the callers and the host restatements are edtr_amd/cls.py) ---------------------------
 def make_cls_rank(*, logits, labels, keep: int, rec_label, rec_rank, rec_top, offset, capacity: int, name="cls.rank") -> Rec:
     """The order behind topk for ``logits`` [B, C] (fp32 / fp16 / bf16): the rank of int32 ``labels`` [B] (or None) into ``rec_rank``,

@@ -1105,6 +1105,60 @@ int edtr_coco_match(const float* det_boxes, const float* det_scores, const void*
                     int32_t* rec_label, float* rec_score, int32_t* rec_rank, uint64_t* rec_match, uint64_t* rec_ignore,
                     int32_t* det_offset, int capacity, int32_t* gt_image, int32_t* gt_label, uint8_t* gt_ignore, int32_t* gt_offset,
                     int gt_capacity, edtr_stream_t stream);
+/* The other half, COCOeval.accumulate and _summarizeDets, from the same record with no host sync and no record copy (csrc/coco_acc.hip;
+ * edtr_amd/coco.py restates each launch in numpy: `accumulate`, `accumulate_order_reference`, `summarize_ordered_reference`).  The
+ * host never learns a row count: grids are sized by `capacity`, and lanes and workgroups past min(*det_offset, capacity) leave.  Rows
+ * at or past the capacity do not exist.  No device-wide atomic, no waiting between workgroups.
+ * edtr_coco_accumulate_workspace: the bytes of `workspace` (16-byte aligned) that edtr_coco_order and edtr_coco_accumulate take for
+ * these two arguments; host arithmetic only, 0 for arguments the two refuse.  Two buffers of 16 bytes per row of the capacity rounded
+ * up to EDTR_COCO_ACC_TILE, and 16 bytes per label. */
+#define EDTR_COCO_ACC_TILE 1024
+#define EDTR_COCO_ACC_MAX_ROWS (1 << 22)
+int64_t edtr_coco_accumulate_workspace(int capacity, int n_labels);
+/* The order of accumulate: the rows with 0 <= label < n_labels and 0 <= rank < EDTR_COCO_KEEP, ascending by the composite key
+ *   (label, score class, image, rank)
+ * which is strict ((image, label, rank) is unique per row), so the result does not depend on how it is sorted.  The score class is
+ * numpy's stable argsort of the negated fp64 score: a greater score first, +0.0 and -0.0 equal, +inf first, -inf last of the numbers,
+ * every NaN after all of them and equal to each other (NOT the key of edtr_boxes_rank).  A stable sort of a filtered subsequence is
+ * the subsequence of the stable sort, so this ONE order serves every (area range, maxDets, threshold).
+ * order: int32 [capacity], of which the first *n_kept are written: row indices in key order.  seg_start: int32 [n_labels + 1], label
+ * k's rows are order[seg_start[k] .. seg_start[k + 1]) and seg_start[n_labels] = *n_kept.  status: bit 0 iff *det_offset lies outside
+ * [0, capacity].
+ * 2 + ceil(log2(tiles)) launches, tiles = ceil(capacity / EDTR_COCO_ACC_TILE): each tile keyed (128 bits: the key and the row index)
+ * and sorted in LDS, then merge passes between the two workspace buffers, one workgroup per tile of output with a merge-path split,
+ * then the indices and the segment bounds (a binary search per label).  No pass has to be stable and nothing uses an atomic.
+ * Errors: a NULL pointer EDTR_E_NULL; capacity <= 0, n_labels <= 0 or workspace_bytes too small EDTR_E_SHAPE; capacity >
+ * EDTR_COCO_ACC_MAX_ROWS or n_labels > EDTR_COCO_MAX_LABELS EDTR_E_UNSUPPORTED; workspace not aligned to 16 bytes, the others to
+ * their element EDTR_E_ALIGN; all before any launch.
+ * replaces: the argsort(-dtScores, kind='mergesort') of COCOeval.accumulate, once instead of per (label, area range, maxDets). */
+int edtr_coco_order(const int32_t* rec_image, const int32_t* rec_label, const float* rec_score, const int32_t* rec_rank,
+                    const int32_t* det_offset, int capacity, int n_labels, void* workspace, int64_t workspace_bytes, int32_t* order,
+                    int32_t* seg_start, int32_t* n_kept, int32_t* status, edtr_stream_t stream);
+/* precision fp64 [10][101][n_labels][4][3] and recall fp64 [10][n_labels][4][3] (thresholds, recall thresholds, labels, area ranges,
+ * maxDets 1 / 10 / 100), every element written, -1 where a (label, area range) has no ground truth that is not ignored: bit for bit
+ * coco.accumulate's.  recall_thresholds: fp64 [101] on the device (linspace(0, 1, 101)).  Two launches: the ground truths that are
+ * not ignored per (label, area range) by ballot into the workspace, then one wave64 workgroup per (label, area range, threshold)
+ * that walks the label's segment of `order` once for the three maxDets.  With tp = match & ~ignore and fp = ~match & ~ignore, the
+ * j-th true positive with fp_j false positives before it has P_j = j / ((fp_j + j) + 2^-52) and rc_j = j / npig in fp64;
+ * precision[r] = max{P_j : rc_j >= recall_thresholds[r]}, 0 where there is none (precision only rises at a true positive, and the
+ * reference's search lands on one), folded into 101 LDS bins by the number of thresholds rc_j reaches — from the division itself —
+ * and finished by a suffix maximum; recall = J / npig.  status: bit 1 is set iff *gt_offset lies outside [0, gt_capacity].
+ * Errors: as edtr_coco_order, with gt_capacity <= 0 EDTR_E_SHAPE, gt_capacity > 2^30 EDTR_E_UNSUPPORTED and the fp64 and uint64
+ * arrays aligned to 8 bytes.
+ * replaces: COCOeval.accumulate (utils/detection.py:462-478 -> pycocotools). */
+int edtr_coco_accumulate(const int32_t* order, const int32_t* seg_start, const uint64_t* rec_match, const uint64_t* rec_ignore,
+                         const int32_t* rec_rank, int capacity, const int32_t* gt_label, const uint8_t* gt_ignore,
+                         const int32_t* gt_offset, int gt_capacity, int n_labels, const double* recall_thresholds, void* workspace,
+                         int64_t workspace_bytes, double* precision, double* recall, int32_t* status, edtr_stream_t stream);
+/* The 12 statistics of COCOeval._summarizeDets into out[0 .. 12) (fp64), and *status as an int64 into the 8 bytes of out[12], so that
+ * one copy of 104 bytes fetches both.  Each is the mean of its entries > -1, or -1 without any, summed in an order that depends on the
+ * shape alone (coco.summarize_ordered_reference): per (threshold, label) over the recall thresholds in index order, then over the
+ * thresholds, then over the labels, each from 0; one division by the count.  One launch of 12 workgroups.
+ * Errors: a NULL pointer EDTR_E_NULL; n_labels <= 0 EDTR_E_SHAPE; n_labels > EDTR_COCO_MAX_LABELS EDTR_E_UNSUPPORTED; the fp64
+ * arrays not aligned to 8 bytes or status to 4 EDTR_E_ALIGN.
+ * replaces: COCOeval.summarize -> _summarizeDets (utils/detection.py:462-478 -> pycocotools). */
+int edtr_coco_summarize(const double* precision, const double* recall, int n_labels, const int32_t* status, double* out,
+                        edtr_stream_t stream);
 
 /* ---- Classification: top-k rank, feature distance and the data set's geometry, with no host sync in the loop (additive to ABI 10) ---
  * The reference's classification test normalises the restored batch for its classifier, scores calculate_accuracy(pred, label,

@@ -6,7 +6,11 @@
               it the host path it replaces on the same inputs: the detections copied to the host and `match_reference` there
   evaluate    `coco.evaluate` over 64 synthetic images (100 / 20 / 20 each) with a stub detector that returns prepared detections on
               the device: the loop, the one copy, `accumulate` and `summarize`; and how much of that the host-side `accumulate` +
-              `summarize` are
+              `summarize` are; beside it the same call with `accumulate="device"`
+  accumulate  `Records.accumulate()` + `stats()` + `result()` (the sort, the walk, the 12 statistics and the one copy of 104 bytes,
+              wrapper included) against the path they replace on the same records, `to_host()` + `accumulate` + `summarize` on this
+              host, at 64 images x 100 detections / 20 ground truths / 20 labels (the shape of `evaluate` above), 1000 x 100 / 20 /
+              80 labels and 5000 x 100 / 20 / 80 (500 000 rows); the records are made on the device by `Records.update`
 
 ms per call from device events around windows of at least 0.2 s of back-to-back calls, five windows per case with the cases of a
 group taking turns; the median, the fastest and the slowest window are kept (tools/bench_labels.py's method).  The host path is
@@ -64,7 +68,7 @@ def main() -> int:
               "method": "device events around windows of at least `window_s` seconds of back-to-back calls after `warmup` calls; `windows` "
                         "windows per case; ms = the median window per call, ms_min / ms_max the spread; inputs resident on the device; "
                         "host_path: wall clock of the device -> host copies of one image's detections plus match_reference",
-              "update": {}, "evaluate": {}}
+              "update": {}, "evaluate": {}, "accumulate": {}}
     for d, g, labels in ((100, 20, 20), (1000, 200, 80)):
         det, gt = coco.scene(np.random.default_rng([d, g, labels]), d, g, labels)
         ddet, dgt = on_dev(det, dev), on_dev(gt, dev)
@@ -97,8 +101,38 @@ def main() -> int:
 
     records = evaluate()["records"]
     group = {"whole_call": wall_ms(evaluate), "host_accumulate_summarize": wall_ms(lambda: coco.summarize(coco.accumulate(records, labels)))}
-    group.update(images=n_images, detections=d, ground_truths=g, labels=labels, mAP=evaluate()["mAP@[0.5:0.95]"])
+
+    def evaluate_device():
+        it = iter(prepared)
+        return coco.evaluate(images, targets, lambda _: next(it), n_labels=labels, accumulate="device")
+
+    group["whole_call_device_accumulate"] = wall_ms(evaluate_device)
+    group.update(images=n_images, detections=d, ground_truths=g, labels=labels, mAP=evaluate()["mAP@[0.5:0.95]"],
+                 mAP_device_accumulate=evaluate_device()["mAP@[0.5:0.95]"])
     result["evaluate"][f"{n_images}_images"] = group
+    for n_images, d, g, labels in ((64, 100, 20, 20), (1000, 100, 20, 80), (5000, 100, 20, 80)):
+        rng = np.random.default_rng([n_images, labels])
+        rec = coco.Records(n_images * d, labels, dev, gt_capacity=n_images * g)
+        for i in range(n_images):
+            rec.update(*coco.scene(rng, d, g, labels, image_id=i))
+
+        def device_path():
+            rec.accumulate()
+            rec.stats()
+            return rec.result()
+
+        def host_path():
+            return coco.summarize(coco.accumulate(rec.to_host(), labels))
+
+        acc, got, want = rec.accumulate(), device_path(), coco.accumulate(rec.to_host(), labels)
+        group = measure({"device": device_path})
+        group["host_path"] = wall_ms(host_path)
+        group.update(images=n_images, rows=n_images * d, ground_truths=n_images * g, labels=labels, mAP=got["mAP@[0.5:0.95]"],
+                     speedup=group["host_path"]["ms"] / group["device"]["ms"],
+                     equals_host_path=bool(np.array_equal(acc["precision"].cpu().numpy(), want["precision"])
+                                           and np.array_equal(acc["recall"].cpu().numpy(), want["recall"])
+                                           and np.max(np.abs(got["stats"] - coco.summarize(want)["stats"])) <= 1e-10))
+        result["accumulate"][f"{n_images}_{d}_{g}_{labels}"] = group
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(result, f, indent=1, sort_keys=True)
