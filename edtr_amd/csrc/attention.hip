@@ -750,7 +750,11 @@ extern "C" int edtr_attn_stamps_read(unsigned* dst, int n) {
 }
 #endif
 
-extern "C" int edtr_flash_attn64(const edtr_attn_params* pp, edtr_stream_t stream) {
+// Validation and kernel choice of edtr_flash_attn64 in ONE place: the launch below dispatches on this answer and edtr_flash_attn64_plan
+// returns it, so a test that asserts a plan asserts what the launch runs.  No HIP call.  bpw: the small-Nk kernel's 32-query blocks
+// per workgroup (0 for every other kernel).
+static int attn64_choose(const edtr_attn_params* pp, int* bpw_out) {
+    if (bpw_out) *bpw_out = 0;
     if (!pp) return EDTR_E_NULL;
     const edtr_attn_params& p = *pp;
     if (!p.q || !p.k || !p.vt || !p.out) return EDTR_E_NULL;
@@ -764,23 +768,13 @@ extern "C" int edtr_flash_attn64(const edtr_attn_params* pp, edtr_stream_t strea
     if (!aligned16(p.q) || !aligned16(p.k) || !aligned16(p.vt) || !aligned16(p.out)) return EDTR_E_ALIGN;
     // 32-bit byte offsets inside one (image, head) slice of K and of V^T (buffer addressing)
     if ((int64_t)(p.Nk + 64) * p.k_ld * 2 >= 0xF0000000LL || (int64_t)64 * p.vt_ld * 2 >= 0xF0000000LL) return EDTR_E_UNSUPPORTED;
-    hipStream_t s = static_cast<hipStream_t>(stream);
     if ((p.q_lo != nullptr) != (p.k_lo != nullptr)) return EDTR_E_NULL;        // q and k are split together
     if (p.vt_lo && !p.q_lo) return EDTR_E_UNSUPPORTED;
     if (p.out_f32 && !p.q_lo) return EDTR_E_UNSUPPORTED;                        // fp32 output: the split-operand kernel only
     if (p.q_lo) {      // hi + lo operand pairs: three MFMA products per matrix product (the robust parity mode)
         if (!aligned16(p.q_lo) || !aligned16(p.k_lo) || (p.vt_lo && !aligned16(p.vt_lo))) return EDTR_E_ALIGN;
         if (p.out_f32 && ((p.o_ld & 3) || (p.o_bs & 3))) return EDTR_E_ALIGN;
-        dim3 grid((p.Nq + 127) / 128, p.H, p.B);
-        if (p.dtype == EDTR_BF16) {
-            if (p.vt_lo) hipLaunchKernelGGL((flash_attn64_split_kernel<BF16, true>), grid, dim3(kThreads), 0, s, p);
-            else hipLaunchKernelGGL((flash_attn64_split_kernel<BF16, false>), grid, dim3(kThreads), 0, s, p);
-        } else {
-            if (p.vt_lo) hipLaunchKernelGGL((flash_attn64_split_kernel<F16, true>), grid, dim3(kThreads), 0, s, p);
-            else hipLaunchKernelGGL((flash_attn64_split_kernel<F16, false>), grid, dim3(kThreads), 0, s, p);
-        }
-        EDTR_LAUNCH_CHECK();
-        return EDTR_OK;
+        return p.vt_lo ? EDTR_ATTN_SPLIT_QKPV : EDTR_ATTN_SPLIT_QK;
     }
     static int v2_min_nq = -1;      // the large-N kernel takes over at this many queries (EDTR_ATTN_V3_MIN_NQ, 0 = never)
     if (v2_min_nq < 0) {
@@ -792,13 +786,7 @@ extern "C" int edtr_flash_attn64(const edtr_attn_params* pp, edtr_stream_t strea
         const char* e = getenv("EDTR_ATTN_V3");
         v3_on = (e && e[0] == '0') ? 0 : 1;
     }
-    if (v3_on && p.q_prescaled && !p.causal && v2_min_nq > 0 && p.Nq >= v2_min_nq && p.Nk >= 256 && (p.Nk & 255) == 0) {
-        dim3 grid3(((p.Nq + QB2 - 1) / QB2) * p.H * p.B);
-        if (p.dtype == EDTR_BF16) hipLaunchKernelGGL((flash_attn64_v3_kernel<BF16>), grid3, dim3(kThreads), 0, s, p);
-        else hipLaunchKernelGGL((flash_attn64_v3_kernel<F16>), grid3, dim3(kThreads), 0, s, p);
-        EDTR_LAUNCH_CHECK();
-        return EDTR_OK;
-    }
+    if (v3_on && p.q_prescaled && !p.causal && v2_min_nq > 0 && p.Nq >= v2_min_nq && p.Nk >= 256 && (p.Nk & 255) == 0) return EDTR_ATTN_V3;
     static int smallk_on = -1;      // EDTR_ATTN_SMALLK=0: the generic kernel for the small-Nk (cross-attention) shapes too (A/B runs)
     if (smallk_on < 0) {
         const char* e = getenv("EDTR_ATTN_SMALLK");
@@ -809,16 +797,42 @@ extern "C" int edtr_flash_attn64(const edtr_attn_params* pp, edtr_stream_t strea
         const int64_t total = (int64_t)p.B * p.H * ((p.Nq + 31) / 32);
         int per_wave = (int)(total / (4 * 512));
         per_wave = per_wave < 1 ? 1 : (per_wave > 4 ? 4 : per_wave);
-        const int bpw = 4 * per_wave;
+        if (bpw_out) *bpw_out = 4 * per_wave;
+        return EDTR_ATTN_SMALLK;
+    }
+    return EDTR_ATTN_GENERIC;
+}
+
+extern "C" int edtr_flash_attn64_plan(const edtr_attn_params* pp, int* blocks_per_wg) { return attn64_choose(pp, blocks_per_wg); }
+
+extern "C" int edtr_flash_attn64(const edtr_attn_params* pp, edtr_stream_t stream) {
+    int bpw = 0;
+    const int kernel = attn64_choose(pp, &bpw);
+    if (kernel < 0) return kernel;
+    const edtr_attn_params& p = *pp;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (kernel == EDTR_ATTN_SPLIT_QK || kernel == EDTR_ATTN_SPLIT_QKPV) {
+        dim3 grid((p.Nq + 127) / 128, p.H, p.B);
+        if (p.dtype == EDTR_BF16) {
+            if (kernel == EDTR_ATTN_SPLIT_QKPV) hipLaunchKernelGGL((flash_attn64_split_kernel<BF16, true>), grid, dim3(kThreads), 0, s, p);
+            else hipLaunchKernelGGL((flash_attn64_split_kernel<BF16, false>), grid, dim3(kThreads), 0, s, p);
+        } else {
+            if (kernel == EDTR_ATTN_SPLIT_QKPV) hipLaunchKernelGGL((flash_attn64_split_kernel<F16, true>), grid, dim3(kThreads), 0, s, p);
+            else hipLaunchKernelGGL((flash_attn64_split_kernel<F16, false>), grid, dim3(kThreads), 0, s, p);
+        }
+    } else if (kernel == EDTR_ATTN_V3) {
+        dim3 grid3(((p.Nq + QB2 - 1) / QB2) * p.H * p.B);
+        if (p.dtype == EDTR_BF16) hipLaunchKernelGGL((flash_attn64_v3_kernel<BF16>), grid3, dim3(kThreads), 0, s, p);
+        else hipLaunchKernelGGL((flash_attn64_v3_kernel<F16>), grid3, dim3(kThreads), 0, s, p);
+    } else if (kernel == EDTR_ATTN_SMALLK) {
         dim3 gridk(((p.Nq + 31) / 32 + bpw - 1) / bpw, p.H, p.B);
         if (p.dtype == EDTR_BF16) hipLaunchKernelGGL((flash_attn64_smallk_kernel<BF16>), gridk, dim3(kThreads), 0, s, p, bpw);
         else hipLaunchKernelGGL((flash_attn64_smallk_kernel<F16>), gridk, dim3(kThreads), 0, s, p, bpw);
-        EDTR_LAUNCH_CHECK();
-        return EDTR_OK;
+    } else {
+        dim3 grid(((p.Nq + 127) / 128) * p.H * p.B);        // one dimension: the kernel deals heads, not query blocks, to the XCDs
+        if (p.dtype == EDTR_BF16) hipLaunchKernelGGL((flash_attn64_kernel<BF16>), grid, dim3(kThreads), 0, s, p);
+        else hipLaunchKernelGGL((flash_attn64_kernel<F16>), grid, dim3(kThreads), 0, s, p);
     }
-    dim3 grid(((p.Nq + 127) / 128) * p.H * p.B);        // one dimension: the kernel deals heads, not query blocks, to the XCDs
-    if (p.dtype == EDTR_BF16) hipLaunchKernelGGL((flash_attn64_kernel<BF16>), grid, dim3(kThreads), 0, s, p);
-    else hipLaunchKernelGGL((flash_attn64_kernel<F16>), grid, dim3(kThreads), 0, s, p);
     EDTR_LAUNCH_CHECK();
     return EDTR_OK;
 }

@@ -1348,7 +1348,9 @@ class Emitter:
         return out
 
     def vt_gemm(self, wv, x, *, B, Ntok, Cin, bias_m=None, name="v_transposed", alpha=1.0, out16=True) -> Tuple[torch.Tensor, int]:
-        """V^T[b] = Wv @ x[b]^T  ->  [B, Cout, roundup8(Ntok)] (padding keys exactly zero when bias_m is None).
+        """V^T[b] = Wv @ x[b]^T  ->  [B, Cout, roundup8(Ntok)].  The padding keys are exactly zero when bias_m is None and hold
+        the row's bias otherwise (CLIP, the VAE): finite either way, which is all edtr_flash_attn64 asks of them (edtr_hip.h: a masked
+        key's probability is exactly 0).
         fp32-stream modes: A = the packed weight [Wh | Wh | Wl][:parts], B operand = x as [hi | lo | hi][:parts]
         (wh*xh + wh*xl + wl*xh); the mixed mode writes the fp16 attention operand directly (``out16``), the high mode
         writes fp32 (its MFMA type is bf16) and the attention emitter casts."""

@@ -24,7 +24,7 @@ CLS_MAX_CLASSES, CLS_MAX_KEEP, CLS_MAX_TOPK, CLS_FD_CHUNK, CLS_FD_MAX_ELEMS = 65
 RPN_MAX_LEVELS, RPN_MAX_PRE_NMS, ROI_MAX_TAPS = 8, 4096, 64          # EDTR_RPN_* / EDTR_ROI_*: caps of edtr_rpn_* and edtr_roi_align
 
 DECLARED_SYMBOLS = [
-    "edtr_abi_version", "edtr_error_string", "edtr_device_info", "edtr_igemm", "edtr_flash_attn64",
+    "edtr_abi_version", "edtr_error_string", "edtr_device_info", "edtr_igemm", "edtr_flash_attn64", "edtr_flash_attn64_plan",
     "edtr_gn_stats", "edtr_gn_apply", "edtr_gn_finalize", "edtr_gn_table", "edtr_layernorm", "edtr_softmax_rows", "edtr_nchw_to_nhwc",
     "edtr_nhwc_to_nchw", "edtr_add", "edtr_timestep_embedding", "edtr_sampler_update", "edtr_axpby", "edtr_q_sample", "edtr_split3", "edtr_cast16",
     "edtr_tile_accumulate", "edtr_divide", "edtr_wavelet_level", "edtr_gn_pool", "edtr_copy3d_f32", "edtr_graph_begin", "edtr_graph_end", "edtr_graph_launch",
@@ -230,6 +230,7 @@ def load() -> C.CDLL:
     lib.edtr_igemm.argtypes = [C.POINTER(IgemmParams), vp]
     lib.edtr_igemm_plan.argtypes = [C.POINTER(IgemmParams)]
     lib.edtr_flash_attn64.argtypes = [C.POINTER(AttnParams), vp]
+    lib.edtr_flash_attn64_plan.argtypes = [C.POINTER(AttnParams), C.POINTER(i32)]
     lib.edtr_flash_attn512.argtypes = [C.POINTER(AttnParams), vp]
     lib.edtr_gn_stats.argtypes = [C.POINTER(GnParams), vp]
     lib.edtr_gn_apply.argtypes = [C.POINTER(GnParams), vp]

@@ -216,6 +216,39 @@ def make_flash_attn(*, dtype, q, k, vt, out, B, H, Nq, Nk, q_bs, q_ld, k_bs, k_l
     return rec
 
 
+ATTN_GENERIC, ATTN_SPLIT_QK, ATTN_SPLIT_QKPV, ATTN_SMALLK, ATTN_V3 = 1, 2, 3, 4, 5       # edtr_hip.h: enum edtr_attn_kernel
+
+
+def flash_attn_plan(rec: Rec) -> Tuple[int, int]:
+    """edtr_flash_attn64_plan of a make_flash_attn record: (kernel id or negative error code, the small-Nk kernel's 32-query blocks
+    per workgroup or 0).  The launch dispatches on the same function; no HIP call, no device."""
+    bpw = ct.c_int32(0)
+    code = int(L.load().edtr_flash_attn64_plan(rec.args[0], ct.byref(bpw)))
+    return code, int(bpw.value)
+
+
+def flash_attn_plan_shape(dtype, B: int, H: int, Nq: int, Nk: int, *, causal: bool = False, prescaled: bool = False, split: int = 0,
+                          out_f32: bool = False, q_ld: int = 0, k_ld: int = 0, vt_ld: int = 0, o_ld: int = 0) -> Tuple[int, int]:
+    """flash_attn_plan from shapes alone (the pointers are placeholders; dense strides unless given).  split: 0 = one part,
+    1 = q_lo / k_lo, 2 = and vt_lo."""
+    p = L.AttnParams()
+    C, fake = H * 64, 0x1000
+    q_ld, k_ld, vt_ld, o_ld = q_ld or C, k_ld or C, vt_ld or round_up(Nk, 8), o_ld or C
+    p.dtype, p.B, p.H, p.Nq, p.Nk = dt_code(dtype), B, H, Nq, Nk
+    p.q, p.q_bs, p.q_ld = fake, Nq * q_ld, q_ld
+    p.k, p.k_bs, p.k_ld = fake, Nk * k_ld, k_ld
+    p.vt, p.vt_bs, p.vt_ld = fake, C * vt_ld, vt_ld
+    p.out, p.o_bs, p.o_ld = fake, Nq * o_ld, o_ld
+    p.scale, p.causal, p.q_prescaled, p.out_f32 = 0.125, int(causal), int(prescaled), int(out_f32)
+    if split:
+        p.q_lo = p.k_lo = fake
+    if split > 1:
+        p.vt_lo = fake
+    bpw = ct.c_int32(0)
+    code = int(L.load().edtr_flash_attn64_plan(ct.byref(p), ct.byref(bpw)))
+    return code, int(bpw.value)
+
+
 def flash_attn512_ok(N: int, C: int) -> bool:
     """Does edtr_flash_attn512 take the VAE's single-head attention over N positions of C channels?  (head width 512, whole 32-key
     tiles; EDTR_ATTN512=0 keeps the GEMM -> softmax -> GEMM form for A/B runs)"""

@@ -138,6 +138,33 @@ def elem_ratio(got, ref, absref, out_dtype, k, extra=None):
     return float(r[idx]), info
 
 
+def attn_elem_ratio(got, q, k, v, scale, dtype, out_dtype=None, causal=False, on_block=None) -> float:
+    """Worst element ratio of softmax(scale q k^T) v against the kernel's [.., N, D] heads (q / k / v: the 16-bit values it reads).
+    Two named terms besides the output rounding: the kernel packs P to 16 bits before P V (attention.hip, attn512.hip: pack2 of
+    the fp32 probabilities) -> 2 u_in P|V|; the fp32 logits carry D 2^-22 |scale| |q||k|^T each, which moves the output by at
+    most (P o delta)|V| + rowsum(P o delta) P|V|.  on_block(ratio, where) is called per 1024-query block (the tests record and
+    assert there)."""
+    kd, vd = torch.as_tensor(k).double().cpu(), torch.as_tensor(v).double().cpu()
+    got = torch.as_tensor(got).double().cpu()
+    worst = 0.0
+    for r0 in range(0, q.shape[-2], 1024):           # query blocks: the fp64 score matrices stay small
+        qd = q[..., r0:r0 + 1024, :].double().cpu()
+        logits = (qd @ kd.transpose(-1, -2)) * scale
+        delta = qd.shape[-1] * 2.0 ** -22 * abs(scale) * (qd.abs() @ kd.abs().transpose(-1, -2))
+        if causal:
+            rows = torch.arange(r0, r0 + qd.shape[-2])[:, None]
+            logits = logits.masked_fill(torch.arange(kd.shape[-2])[None, :] > rows, float("-inf"))
+        p = torch.softmax(logits, dim=-1)
+        pv = p @ vd.abs()
+        pd = p * delta
+        extra = {"16-bit P before P V": 2.0 * unit_roundoff(dtype) * pv, "fp32 logits": pd @ vd.abs() + pd.sum(-1, keepdim=True) * pv}
+        r, where = elem_ratio(got[..., r0:r0 + 1024, :], p @ vd, pv, out_dtype or dtype, kd.shape[-2], extra)
+        if on_block is not None:
+            on_block(r, where)
+        worst = max(worst, r)
+    return worst
+
+
 def geglu_err(val, gate, ev, eg):
     """Absolute error bound of val * gelu(gate) when val / gate are off by at most ev / eg: the product rule with GELU's
     Lipschitz constant and the epilogue's erf approximation."""

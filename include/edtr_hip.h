@@ -248,7 +248,9 @@ int edtr_igemm_plan(const edtr_igemm_params* p);
  *   q   : [B][Nq][q_ld]  head h occupies columns h*64 .. h*64+63
  *   k   : [B][Nk][k_ld]  same column convention
  *   vt  : [B][H*64][vt_ld]  V transposed ("key-major"): row h*64+d holds v[:, h*64+d] over the
- *         keys; vt_ld >= roundup8(Nk) and the padding keys must be zero
+ *         keys; vt_ld >= roundup8(Nk).  The padding keys [Nk, roundup8(Nk)) are read and must be
+ *         FINITE (any value: a masked key gets probability exactly 0, so 0 * pad adds nothing,
+ *         but 0 * NaN / Inf would); columns at or beyond roundup8(Nk) are never read
  *   out : [B][Nq][o_ld]
  * ---------------------------------------------------------------------------------------- */
 typedef struct edtr_attn_params {
@@ -276,6 +278,22 @@ typedef struct edtr_attn_params {
 } edtr_attn_params;
 
 int edtr_flash_attn64(const edtr_attn_params* p, edtr_stream_t stream);
+
+/* Which kernel would edtr_flash_attn64 run for these parameters (additive in ABI 10)?  All of edtr_flash_attn64's validation and its
+ * shape rules, no launch and no HIP call (works without a GPU; the pointers are only tested for NULL and alignment): < 0 = the error
+ * edtr_flash_attn64 would return, > 0 = one of the ids below.  edtr_flash_attn64 dispatches on the same function, and the switches
+ * EDTR_ATTN_V3, EDTR_ATTN_V3_MIN_NQ and EDTR_ATTN_SMALLK act on both alike (read once per process).  blocks_per_wg (may be NULL)
+ * receives the 32-query blocks one workgroup of the small-Nk kernel walks (4 / 8 / 12 / 16: one to four per wave, from
+ * B * H * ceil(Nq / 32) / 2048), 0 for every other kernel.  The generic and the large-N kernel deal heads, not query blocks, to the
+ * XCDs when B * H % 8 == 0. */
+enum edtr_attn_kernel {
+    EDTR_ATTN_GENERIC = 1,      /* 128 queries per workgroup, online softmax over 64-key tiles: any shape, the causal mask */
+    EDTR_ATTN_SPLIT_QK = 2,     /* q_lo / k_lo given: three MFMA products per score */
+    EDTR_ATTN_SPLIT_QKPV = 3,   /* and vt_lo: three per output product too */
+    EDTR_ATTN_SMALLK = 4,       /* Nk <= 128, not causal: K / V^T resident in LDS, two-pass softmax */
+    EDTR_ATTN_V3 = 5            /* q_prescaled, not causal, Nq >= 2048 (EDTR_ATTN_V3_MIN_NQ), Nk % 256 == 0: the generated large-N loop */
+};
+int edtr_flash_attn64_plan(const edtr_attn_params* p, int* blocks_per_wg);
 
 /* Fused single-head attention with head width 512 (ABI 9): the VAE's AttnBlock, softmax(q k^T * scale) v over the latent positions.
  * Same parameter block as edtr_flash_attn64 with H == 1 and rows of 512 channels: q [B][Nq][q_ld], k [B][Nk][k_ld],

@@ -12,13 +12,16 @@ C ABI (edtr_amd.ops -> libedtr_hip.so) and compared with a plain torch CPU compu
     (GroupNorm groups, long softmax rows) a per-block check at 1.25 u backs it up, and the swin attention half is held by a
     per-block check only.
 Most igemm outputs (GEMM, split-K, GEGLU / concat, GELU / LeakyReLU, tile orders, conv3x3, the halo tiles through _halo_case)
-also sit in NaN-filled buffers with guard rows and columns (guarded / check_guards): a store past a ragged tail fails."""
+also sit in NaN-filled buffers with guard rows and columns (guarded / check_guards): a store past a ragged tail fails.  The
+attention cases at the launch geometry of a batch-8 run (test_flash_attn64_launch_geometry and its neighbours) guard every operand
+and the output that way (HostileAttn) and assert edtr_flash_attn64_plan's answer before they launch."""
 import math
 
 import pytest
 import torch
 import torch.nn.functional as F
 
+import attn_cases
 from edtr_amd.testing import ACC_F32, GELU_APPROX, LIPSCHITZ, block_rel, geglu_err, geglu_slack, rounded_operand, unit_roundoff
 
 pytestmark = pytest.mark.gpu
@@ -119,26 +122,17 @@ def check_guards(buf, M, N):
 
 
 def attn_elem(got, q, k, v, scale, dtype, out_dtype=None, causal=False):
-    """Element bound of softmax(scale q k^T) v against the kernel's [.., N, D] heads (q / k / v: the 16-bit values it reads).
-    Two named terms besides the output rounding: the kernel packs P to 16 bits before P V (attention.hip, attn512.hip: pack2 of
-    the fp32 probabilities) -> 2 u_in P|V|; the fp32 logits carry D 2^-22 |scale| |q||k|^T each, which moves the output by at
-    most (P o delta)|V| + rowsum(P o delta) P|V|."""
-    kd, vd = k.double().cpu(), v.double().cpu()
-    got = got.double().cpu()
-    worst = 0.0
-    for r0 in range(0, q.shape[-2], 1024):           # query blocks: the fp64 score matrices stay small
-        qd = q[..., r0:r0 + 1024, :].double().cpu()
-        logits = (qd @ kd.transpose(-1, -2)) * scale
-        delta = qd.shape[-1] * 2.0 ** -22 * abs(scale) * (qd.abs() @ kd.abs().transpose(-1, -2))
-        if causal:
-            rows = torch.arange(r0, r0 + qd.shape[-2])[:, None]
-            logits = logits.masked_fill(torch.arange(kd.shape[-2])[None, :] > rows, float("-inf"))
-        p = torch.softmax(logits, dim=-1)
-        pv = p @ vd.abs()
-        pd = p * delta
-        extra = {"16-bit P before P V": 2.0 * unit_roundoff(dtype) * pv, "fp32 logits": pd @ vd.abs() + pd.sum(-1, keepdim=True) * pv}
-        worst = max(worst, elem(got[..., r0:r0 + 1024, :], p @ vd, pv, out_dtype or dtype, kd.shape[-2], extra))
-    return worst
+    """Assert the element bound of softmax(scale q k^T) v against the kernel's [.., N, D] heads (q / k / v: the 16-bit values it
+    reads) and record the worst ratio; the bound and its two named terms are edtr_amd.testing.attn_elem_ratio."""
+    import os
+    from edtr_amd.testing import attn_elem_ratio
+    key = os.environ.get("PYTEST_CURRENT_TEST", "?").split(" ")[0]
+
+    def record(r, where):
+        ELEM[key] = max(ELEM.get(key, 0.0), r)
+        assert r <= 1.0, f"element bound exceeded: ratio {r:.3g} at {where}"
+
+    return attn_elem_ratio(got, q, k, v, scale, dtype, out_dtype, causal, on_block=record)
 
 
 def norm_elem(got, x, gamma, beta, eps, dtype, silu=False):
@@ -2539,6 +2533,204 @@ def test_lin320_rejects_what_it_cannot_run():
         ops.launch(ops.make_lin320(dtype=dtype, x=x, ldx=320, M=256, N=320, w=w, out=x, ldo=320))
     assert not ops.lin320_ok(32768, 320, 640) and not ops.lin320_ok(192, 320, 320) and ops.lin320_ok(32768, 320, 320) and ops.lin320_ok(32768, 960, 320)
     assert ops.lin320_ok(16384, 320, 320, ln=True) and not ops.lin320_ok(16384, 320, 320) and not ops.lin320_ok(16384, 960, 320, ln=True)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The attention kernels at the launch geometry production runs (tests/attn_cases.py has the table): B H % 8 == 0 (heads dealt to
+# the XCDs), 2 and 3 query blocks per wave of the small-Nk kernel with a partial last workgroup, one and three trips of the
+# large-N loop, its re-maximise path for ONE of a wave's two blocks — every case in the "hostile layout" below, with the plan
+# (edtr_flash_attn64_plan: the function the launch dispatches on) asserted before the launch, so that a moved threshold fails the
+# case instead of quietly testing another kernel.
+# ---------------------------------------------------------------------------------------------------------------------
+VT_PAD = 1000.0     # the V^T padding keys [Nk, roundup8(Nk)): finite, not zero (edtr_hip.h; CLIP's V^T carries its bias there)
+
+
+class HostileAttn:
+    """Operands of edtr_flash_attn64 laid out so that every wrong stride or stray access shows: q / k / V^T / out are views into
+    NaN-filled buffers with guard rows between the images and guard columns behind every row.
+      out : [B, Nq + 3, Co + 8]              o_ld = Co + 8, o_bs = (Nq + 3)(Co + 8)           (Co = C)
+      q, k: Nq == Nk and not split: ONE [B, N + 2, 2C + 8] buffer, q in columns 0..C, k in C..2C (the engine's layout);
+            otherwise one [B, N + 2, W + 8] buffer each (W = C, or 2C = [hi | lo] for split operands)
+      vt  : [B, C + 8, W' ] rows of round_up(Nk, 8) + 8 columns per part; columns [Nk, round_up(Nk, 8)) hold VT_PAD
+    q / k / v: [B, N, C] 16-bit tensors on the CPU (hi parts); q_lo / k_lo / v_lo: the low parts of split operands."""
+
+    def __init__(self, ops, d, dtype, q, k, v, q_lo=None, k_lo=None, v_lo=None, out_f32=False):
+        nan = float("nan")
+        B, Nq, C = q.shape
+        Nk = k.shape[1]
+        self.B, self.Nq, self.Nk, self.C = B, Nq, Nk, C
+        split = q_lo is not None
+
+        def rows(x, lo, extra_cols):            # [B, N, C] (+ lo) -> NaN-guarded [B, N + 2, parts C + extra_cols + 8]
+            w = (2 if lo is not None else 1) * C + extra_cols
+            buf = torch.full((B, x.shape[1] + 2, w + 8), nan, dtype=dtype)
+            buf[:, :x.shape[1], :C] = x
+            if lo is not None:
+                buf[:, :x.shape[1], C:2 * C] = lo
+            return buf
+
+        if Nq == Nk and not split:
+            qk = rows(q, None, C)
+            qk[:, :Nk, C:2 * C] = k
+            self.qk = qk.to(d)
+            self.q, self.k = self.qk[:, :, :C], self.qk[:, :, C:]
+            self.q_lo = self.k_lo = None
+        else:
+            self.qbuf, self.kbuf = rows(q, q_lo, 0).to(d), rows(k, k_lo, 0).to(d)
+            self.q, self.k = self.qbuf, self.kbuf
+            self.q_lo, self.k_lo = (self.qbuf[:, :, C:], self.kbuf[:, :, C:]) if split else (None, None)
+        r8 = ops.round_up(Nk, 8)
+        part = r8 + 8
+        vparts = 2 if v_lo is not None else 1
+        vt = torch.full((B, C + 8, vparts * part), nan, dtype=dtype)
+        for i, x in enumerate([v] + ([v_lo] if v_lo is not None else [])):
+            vt[:, :C, i * part:i * part + Nk] = x.transpose(1, 2)
+            vt[:, :C, i * part + Nk:i * part + r8] = VT_PAD
+        self.vtbuf = vt.to(d)
+        self.vt_lo = self.vtbuf[:, :, part:] if v_lo is not None else None
+        self.out_dtype = torch.float32 if out_f32 else dtype
+        self.outbuf = torch.full((B, Nq + 3, C + 8), nan, dtype=self.out_dtype, device=d)
+        self.strides = dict(q_bs=self.q.stride(0), q_ld=self.q.stride(1), k_bs=self.k.stride(0), k_ld=self.k.stride(1),
+                            vt_bs=self.vtbuf.stride(0), vt_ld=self.vtbuf.stride(1), o_bs=self.outbuf.stride(0), o_ld=self.outbuf.stride(1))
+        assert all(s % 8 == 0 for s in self.strides.values())
+
+    def rec(self, ops, dtype, H, **kw):
+        return ops.make_flash_attn(dtype=dtype, q=self.q, k=self.k, vt=self.vtbuf, out=self.outbuf, B=self.B, H=H, Nq=self.Nq, Nk=self.Nk,
+                                   q_lo=self.q_lo, k_lo=self.k_lo, vt_lo=self.vt_lo, out_f32=self.out_dtype == torch.float32,
+                                   **self.strides, **kw)
+
+    def valid_out(self):
+        """The [B, Nq, C] output on the CPU, after checking that it is finite and that every guard row and column is still NaN."""
+        o = self.outbuf.float().cpu()
+        assert torch.isfinite(o[:, :self.Nq, :self.C]).all(), "non-finite values in the valid region"
+        assert torch.isnan(o[:, :self.Nq, self.C:]).all(), "a store landed in the guard columns"
+        assert torch.isnan(o[:, self.Nq:]).all(), "a store landed in the guard rows (past Nq, or a wrong o_bs)"
+        return o[:, :self.Nq, :self.C]
+
+
+def _heads64(t, B, H):
+    return t.double().reshape(B, -1, H, 64).transpose(1, 2)
+
+
+def _attn_gates(got, q, k, v, B, H, scale, dtype, out_dtype=None, causal=False):
+    """The file's three gates against the fp64 softmax attention of the values the kernel reads ([B, N, H * 64] on the CPU)."""
+    qh, kh, vh = _heads64(q, B, H), _heads64(k, B, H), _heads64(v, B, H)
+    logits = qh @ kh.transpose(-1, -2) * scale
+    if causal:
+        logits = logits + torch.triu(torch.full(logits.shape[-2:], float("-inf"), dtype=torch.float64), 1)
+    ref = (torch.softmax(logits, dim=-1) @ vh).transpose(1, 2).reshape(got.shape)
+    assert torch.isfinite(got).all()
+    e = rel(got, ref)
+    r = attn_elem(_heads64(got, B, H), qh, kh, vh, scale, dtype, out_dtype, causal=causal)
+    print(f"\n[attention geometry] rel {e:.3e} worst element ratio {r:.3f}")
+    assert e < TOL[dtype] * 1.5
+    return ref
+
+
+ATTN_CASES = attn_cases.CASES
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("case", ATTN_CASES, ids=[c.name for c in ATTN_CASES])
+def test_flash_attn64_launch_geometry(dtype, case):
+    ops = _ops()
+    d = dev()
+    B, H, Nq, Nk = case.B, case.H, case.Nq, case.Nk
+    C = H * 64
+    amp = 0.42 if case.prescaled else 1.0
+    q, k, v = rnd((B, Nq, C), 700, amp).to(dtype), rnd((B, Nk, C), 701, amp).to(dtype), rnd((B, Nk, C), 702).to(dtype)
+    lay = HostileAttn(ops, d, dtype, q, k, v)
+    rec = lay.rec(ops, dtype, H, scale=0.125, causal=case.causal, prescaled=case.prescaled)
+    assert ops.flash_attn_plan(rec) == (case.kernel, case.bpw), "the launch rules moved: this case no longer reaches its branch"
+    if case.head_map is not None:
+        assert ((B * H) % 8 == 0) == case.head_map
+    ops.launch(rec)
+    torch.cuda.synchronize()
+    _attn_gates(lay.valid_out(), q, k, v, B, H, math.log(2.0) if case.prescaled else 0.125, dtype, causal=case.causal)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("pv", [False, True])
+def test_flash_attn64_split_operands_guarded(dtype, pv):
+    """The split-operand kernels (q_lo / k_lo; with vt_lo and the fp32 output) behind output guards and a finite V^T pad; the
+    reference is fp64 attention of hi + lo, the values the three products see."""
+    ops = _ops()
+    d = dev()
+    B, H, Nq, Nk = attn_cases.SPLIT_SHAPE
+    C = H * 64
+    x32 = [rnd((B, Nq, C), 710), rnd((B, Nk, C), 711), rnd((B, Nk, C), 712)]
+    hi = [x.to(dtype) for x in x32]
+    lo = [(x - h.float()).to(dtype) for x, h in zip(x32, hi)]
+    lay = HostileAttn(ops, d, dtype, hi[0], hi[1], hi[2], q_lo=lo[0], k_lo=lo[1], v_lo=lo[2] if pv else None, out_f32=pv)
+    rec = lay.rec(ops, dtype, H, scale=0.125)
+    assert ops.flash_attn_plan(rec) == (ops.ATTN_SPLIT_QKPV if pv else ops.ATTN_SPLIT_QK, 0)
+    ops.launch(rec)
+    torch.cuda.synchronize()
+    full = [h.double() + l.double() for h, l in zip(hi, lo)]
+    _attn_gates(lay.valid_out(), full[0], full[1], full[2] if pv else hi[2], B, H, 0.125, dtype, torch.float32 if pv else dtype)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_flash_attn64_v3_rescales_one_block_of_a_wave(dtype):
+    """The large-N kernel's out-of-line re-maximise path for ONE of the two 32-query blocks a wave runs in one instruction stream
+    (the vote is per block and tile; tools/gen_attn_v2.py: SUM_LIMIT = 2^14 on a half-row tile sum).  One query of a block A meets
+    a dominating key in a later tile, one query of a block B of another wave meets its in the last tile; their partner blocks must
+    stay on the fast path and come out untouched.  The construction is checked on the fp64 logits before the launch."""
+    ops = _ops()
+    d = dev()
+    B, H, Nq, Nk = 1, 1, 2048, 512
+    q32, k32 = rnd((B, Nq, 64), 720, 0.42), rnd((B, Nk, 64), 721, 0.42)
+    # workgroup = 256 queries, wave w owns rows 64 w .. 64 w + 63 of it: block A the first 32, block B the last 32
+    qa, ka = 0 * 256 + 1 * 64 + 5, 3 * 64 + 8                 # block A of wave 1, workgroup 0; key in the fourth tile
+    qb, kb = 3 * 256 + 2 * 64 + 32 + 9, 7 * 64 + 52           # block B of wave 2, workgroup 3; key in the last tile
+    for qi, kj in ((qa, ka), (qb, kb)):
+        k32[0, kj] = 1.5 * q32[0, qi]
+        q32[0, qi] *= 2.0
+    q, k, v = q32.to(dtype), k32.to(dtype), rnd((B, Nk, 64), 722).to(dtype)
+    L = q[0].double() @ k[0].double().t()                     # log2-domain logits (prescaled)
+    m0 = L[:, :64].max(-1).values                             # the kernel's maximum after the first tile
+    for qi, kj, partner in ((qa, ka, range(qa - qa % 64 + 32, qa - qa % 64 + 64)), (qb, kb, range(qb - qb % 64, qb - qb % 64 + 32))):
+        assert L[qi, kj] - m0[qi] > 14 + 2, "the chosen query does not cross the re-maximise threshold with two octaves to spare"
+        rows = torch.tensor(list(partner))
+        assert qi not in partner and qi // 64 == partner[0] // 64
+        half_tile_sums = torch.exp2(L[rows] - m0[rows, None]).reshape(32, Nk // 32, 32).sum(-1)
+        assert half_tile_sums.max() < 2.0 ** 14 / 4, "the partner block would take the slow path too"
+    lay = HostileAttn(ops, d, dtype, q, k, v)
+    rec = lay.rec(ops, dtype, H, scale=0.125, prescaled=True)
+    assert ops.flash_attn_plan(rec) == (ops.ATTN_V3, 0)
+    ops.launch(rec)
+    torch.cuda.synchronize()
+    got = lay.valid_out()
+    ref = _attn_gates(got, q, k, v, B, H, math.log(2.0), dtype)
+    for qi in (qa, qb):
+        assert (got[0, qi].double() - ref[0, qi]).abs().max() < 0.05
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("out_f32", [False, True])
+def test_flash_attn512_guarded_output(dtype, out_f32):
+    """edtr_flash_attn512 into a NaN-filled [B, N + 3, 512 + 8] buffer (o_ld = 520, guard rows between the images)."""
+    ops = _ops()
+    d = dev()
+    B, N, C = 2, 96, 512
+    ld, ldv = 2 * C, N + 8
+    qk = rnd((B * N, ld), 601).to(dtype)
+    vt = rnd((B * C, ldv), 602).to(dtype)
+    odt = torch.float32 if out_f32 else dtype
+    outbuf = torch.full((B, N + 3, C + 8), float("nan"), dtype=odt, device=d)
+    qd, vd = qk.to(d), vt.to(d)
+    ops.launch(ops.make_flash_attn512(dtype=dtype, q=qd[:, :C], k=qd[:, C:], vt=vd, out=outbuf, B=B, N=N, q_bs=N * ld, q_ld=ld, k_bs=N * ld, k_ld=ld,
+                                      vt_bs=C * ldv, vt_ld=ldv, o_bs=(N + 3) * (C + 8), o_ld=C + 8, scale=1.0 / math.sqrt(C), out_f32=out_f32))
+    torch.cuda.synchronize()
+    o = outbuf.float().cpu()
+    assert torch.isfinite(o[:, :N, :C]).all(), "non-finite values in the valid region"
+    assert torch.isnan(o[:, :N, C:]).all(), "a store landed in the guard columns"
+    assert torch.isnan(o[:, N:]).all(), "a store landed in the guard rows"
+    q, k = qk[:, :C].double().reshape(B, N, C), qk[:, C:].double().reshape(B, N, C)
+    v = vt.double().reshape(B, C, ldv)[:, :, :N].transpose(1, 2)
+    ref = torch.softmax(q @ k.transpose(1, 2) / math.sqrt(C), dim=-1) @ v
+    assert rel(o[:, :N, :C], ref) < TOL[dtype]
+    attn_elem(o[:, :N, :C], q, k, v, 1.0 / math.sqrt(C), dtype, odt)
 
 
 def test_zz_measured_error_envelope():

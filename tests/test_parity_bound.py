@@ -8,7 +8,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from edtr_amd.testing import elem_ratio, block_rel, geglu_slack
+from edtr_amd.testing import attn_elem_ratio, elem_ratio, block_rel, geglu_slack
 
 DTYPES = [torch.bfloat16, torch.float16]
 L2_GATE = {torch.bfloat16: 3.5e-3, torch.float16: 4.4e-4}        # tests/test_gpu_ops.py TOL
@@ -149,3 +149,98 @@ def test_non_finite_output_is_an_infinite_ratio():
     got[2, 5] = float("nan")
     ratio, where = elem_ratio(got, ref, ref, torch.bfloat16, 1)
     assert ratio == float("inf") and where["index"] == (2, 5)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The attention gates of tests/test_gpu_ops.py (attn_elem = edtr_amd.testing.attn_elem_ratio <= 1, plus NaN guards around the
+# output) on an emulated launch with B H = 8: the fp64 reference rounded once to 16 bits passes; what a wrong block map, a store
+# past Nq or a V^T padding key with a non-zero probability would write does not.
+# ---------------------------------------------------------------------------------------------------------------------
+ATTN_SHAPE = (2, 4, 300, 77)          # B, H, Nq, Nk: B H = 8, three 128-query blocks (the last ragged), 3 padding keys
+ATTN_SCALE, VT_PAD = 0.125, 1000.0
+_ATTN = {}
+
+
+def _attn_case(dtype):
+    """(q, k, v heads [B, H, N, 64] of 16-bit values, fp64 reference [B, Nq, H * 64]); computed once per dtype, never modified."""
+    if dtype not in _ATTN:
+        B, H, Nq, Nk = ATTN_SHAPE
+        q, k, v = (_rnd((B, n, H * 64), s).to(dtype).double().reshape(B, n, H, 64).transpose(1, 2) for n, s in ((Nq, 40), (Nk, 41), (Nk, 42)))
+        p = torch.softmax(q @ k.transpose(-1, -2) * ATTN_SCALE, dim=-1)
+        _ATTN[dtype] = (q, k, v, (p @ v).transpose(1, 2).reshape(B, Nq, H * 64))
+    return _ATTN[dtype]
+
+
+def _guarded_launch(out, dtype):
+    """What a kernel leaves in the NaN-filled [B, Nq + 3, C + 8] buffer of the GPU tests when it stores `out` (fp64, rounded here)."""
+    B, Nq, C = out.shape
+    buf = torch.full((B, Nq + 3, C + 8), float("nan"), dtype=dtype)
+    buf[:, :Nq, :C] = out.to(dtype)
+    return buf
+
+
+def _attn_verdict(buf, dtype):
+    """(guards intact, worst element ratio of the valid region): the two checks every new GPU attention case makes."""
+    B, H, Nq, Nk = ATTN_SHAPE
+    q, k, v, _ = _attn_case(dtype)
+    C = H * 64
+    b = buf.float()
+    guards = bool(torch.isnan(b[:, :Nq, C:]).all() and torch.isnan(b[:, Nq:]).all() and torch.isfinite(b[:, :Nq, :C]).all())
+    heads = b[:, :Nq, :C].reshape(B, Nq, H, 64).transpose(1, 2)
+    return guards, attn_elem_ratio(heads, q, k, v, ATTN_SCALE, dtype)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_attention_reference_rounded_once_passes_the_gates(dtype):
+    ref = _attn_case(dtype)[3]
+    guards, ratio = _attn_verdict(_guarded_launch(ref, dtype), dtype)
+    assert guards and ratio < 0.6, ratio
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_attention_block_map_defects_exceed_the_bound(dtype):
+    """A wrong bh of the head-dealing block map (two heads swapped) and a wrong qb (one 128-query block of one head holds its
+    neighbour's rows): both leave the guards alone and exceed the element bound many times over."""
+    ref = _attn_case(dtype)[3]
+    swapped = ref.clone()
+    swapped[0, :, 64:128], swapped[0, :, 128:192] = ref[0, :, 128:192], ref[0, :, 64:128]
+    shifted = ref.clone()
+    shifted[1, 128:256, 192:256] = ref[1, 0:128, 192:256]
+    for name, out in (("heads swapped", swapped), ("query block from its neighbour", shifted)):
+        guards, ratio = _attn_verdict(_guarded_launch(out, dtype), dtype)
+        assert guards and ratio > 3.0, (name, ratio)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_attention_store_past_nq_fails_the_guard_check(dtype):
+    """One 16-byte store (8 elements) one row past Nq: the valid region is untouched — the element bound cannot see it — and the
+    guard rows catch it."""
+    B, H, Nq, Nk = ATTN_SHAPE
+    ref = _attn_case(dtype)[3]
+    buf = _guarded_launch(ref, dtype)
+    buf[1, Nq, 72:80] = ref[1, Nq - 1, 72:80].to(dtype)
+    guards, ratio = _attn_verdict(buf, dtype)
+    assert not guards and ratio < 0.6
+
+
+def test_attention_padding_key_with_a_small_probability_exceeds_the_fp16_bound():
+    """The contract of include/edtr_hip.h — a masked key's probability is exactly 0, so a finite V^T pad is harmless — against a
+    kernel that would give ONE padding key the probability 2^-20 with the pad at VT_PAD = 1000: every output moves by 9.5e-4.
+    That exceeds the element bound for fp16 outputs (measured ratio 1.95).  For bf16 it does not at this size (2u|ref| and the
+    16-bit P term are 8 times larger: 0.29), and neither dtype sees the weaker defect of 2^-20 of the row MAXIMUM's weight, before
+    the normalisation (a row sums to several maxima here: fp16 0.90, bf16 0.20).  This test pins what the bound itself can tell,
+    no more: the figures are printed, only the fp16 one is a requirement."""
+    seen = {}
+    for dtype in DTYPES:
+        q, k, v, ref = _attn_case(dtype)
+        logits = q @ k.transpose(-1, -2) * ATTN_SCALE
+        e = torch.exp(logits - logits.max(-1, keepdim=True).values)
+        leak = 2.0 ** -20
+        as_probability = (e @ v / e.sum(-1, keepdim=True) + leak * VT_PAD) / (1.0 + leak)
+        of_the_maximum = (e @ v + leak * VT_PAD) / (e.sum(-1, keepdim=True) + leak)
+        for name, out in (("probability", as_probability), ("of the maximum", of_the_maximum)):
+            guards, ratio = _attn_verdict(_guarded_launch(out.transpose(1, 2).reshape(ref.shape), dtype), dtype)
+            assert guards
+            seen[(dtype, name)] = ratio
+    print("[vt pad weighted 2^-20 x 1000] " + "; ".join(f"{d} {n}: {r:.2f}" for (d, n), r in seen.items()))
+    assert seen[(torch.float16, "probability")] > 1.0, seen
