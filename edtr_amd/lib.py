@@ -22,6 +22,7 @@ COCO_MAX_DET, COCO_MAX_GT, COCO_MAX_LABELS, COCO_MAX_THRESHOLDS, COCO_KEEP = 102
 COCO_ACC_TILE, COCO_ACC_MAX_ROWS = 1024, 1 << 22        # EDTR_COCO_ACC_*: the sort tile and the row cap of edtr_coco_order
 CLS_MAX_CLASSES, CLS_MAX_KEEP, CLS_MAX_TOPK, CLS_FD_CHUNK, CLS_FD_MAX_ELEMS = 65536, 8, 4, 4096, 1 << 28       # EDTR_CLS_*: caps of edtr_cls_*
 RPN_MAX_LEVELS, RPN_MAX_PRE_NMS, ROI_MAX_TAPS = 8, 4096, 64          # EDTR_RPN_* / EDTR_ROI_*: caps of edtr_rpn_* and edtr_roi_align
+DET_MAX_CHANNELS, DET_MAX_EXTENT, DET_TILE_W, DET_TILE_H = 4, 32768, 256, 16       # EDTR_DET_*: caps and tile of edtr_det_transform
 
 DECLARED_SYMBOLS = [
     "edtr_abi_version", "edtr_error_string", "edtr_device_info", "edtr_igemm", "edtr_flash_attn64", "edtr_flash_attn64_plan",
@@ -42,6 +43,7 @@ DECLARED_SYMBOLS = [
     "edtr_coco_match", "edtr_coco_accumulate_workspace", "edtr_coco_order", "edtr_coco_accumulate", "edtr_coco_summarize",
     "edtr_cls_rank", "edtr_cls_fdist", "edtr_cls_commit", "edtr_cls_normalize", "edtr_cls_window",
     "edtr_rpn_anchors", "edtr_rpn_select", "edtr_rpn_candidates", "edtr_roi_align",
+    "edtr_det_transform",
 ]
 
 
@@ -206,6 +208,11 @@ class ImageDesc(C.Structure):
     ]
 
 
+class DetImage(C.Structure):
+    """edtr_det_image: one image of the detector's ragged input (24 bytes; the header documents every offset)."""
+    _fields_ = [("src", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("oh", C.c_int32), ("ow", C.c_int32)]
+
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -336,6 +343,8 @@ def load() -> C.CDLL:
     lib.edtr_rpn_select.argtypes = [i32, C.POINTER(vp), C.POINTER(i32), i32, i32, i32, vp, vp]
     lib.edtr_rpn_candidates.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), i32, i32, i32, vp, vp, vp, f32, f32, f32, vp, vp, vp, vp, vp]
     lib.edtr_roi_align.argtypes = [i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(f32), i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, vp]
+    # the detector's input transform (edtr_hip.h "Detector input"): descs_host is a ctypes array of DetImage, mean / std ctypes float arrays
+    lib.edtr_det_transform.argtypes = [C.POINTER(DetImage), vp, i32, i32, C.POINTER(f32), C.POINTER(f32), i32, vp, i32, i32, vp]
     if lib.edtr_abi_version() != 10:
         raise RuntimeError("libedtr_hip.so ABI version mismatch")
     _lib = lib

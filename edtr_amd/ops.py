@@ -1211,6 +1211,22 @@ def make_roi_align(*, features, scales, rois, batch_index, out, sampling_ratio: 
     return Rec(L.load().edtr_roi_align, args, keep, name, 9.0 * out.numel() * int(sampling_ratio) ** 2, nbytes)
 
 
+# -- the detector's input transform (edtr_hip.h "Detector input"; the caller and the host restatement are edtr_amd/detinput.py) ---------
+def make_det_transform(*, descs_host, descs, mean: Sequence[float], std: Sequence[float], batch, keep=(), name="detinput.transform") -> Rec:
+    """Every image of a ragged list normalised, resized and padded into its slot of ``batch`` [N, C, H, W] (fp32 / fp16 / bf16) in one
+    launch: ``descs_host`` a ctypes array of `lib.DetImage`, ``descs`` its copy on the device (a uint8 tensor), ``mean`` / ``std`` C host
+    floats each; ``keep``: the source tensors the descriptors point at."""
+    if batch.dtype not in _LOGITS_DT:
+        raise TypeError(f"batch must be float32, float16 or bfloat16, got {batch.dtype}")
+    N, C, H, W = batch.shape
+    if len(descs_host) != N or len(mean) != C or len(std) != C:
+        raise ValueError(f"batch is {tuple(batch.shape)} for {len(descs_host)} images and {len(mean)} / {len(std)} constants")
+    m_host, s_host = (ct.c_float * C)(*[float(v) for v in mean]), (ct.c_float * C)(*[float(v) for v in std])
+    args = (descs_host, ptr(descs), N, C, m_host, s_host, _LOGITS_DT[batch.dtype], ptr(batch), H, W)
+    nbytes = 4.0 * C * sum(d.h * d.w for d in descs_host) + float(batch.element_size() * batch.numel())
+    return Rec(L.load().edtr_det_transform, args, (descs_host, descs, m_host, s_host, batch) + tuple(keep), name, 0.0, nbytes)
+
+
 
 def make_cast16(*, dtype, src: torch.Tensor, rows: int, C: int, dst: torch.Tensor, name="cast16") -> Rec:
     args = (dt_code(dtype), ptr(src), rows, C, src.stride(0), ptr(dst), dst.stride(0))

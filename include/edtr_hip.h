@@ -1309,6 +1309,43 @@ int edtr_roi_align(int dtype, const void* const* features_host, const int32_t* l
                    int C, const float* rois, const int32_t* batch_index, int K, int P, int S, int k_min, int k_max,
                    float canonical_scale, float canonical_level, float* out, edtr_stream_t stream);
 
+/* ---- Detector input: normalise, resize and pad a ragged list of images in one launch (additive to ABI 10) -------------------------
+ * GeneralizedRCNNTransform.forward in eval mode (model/faster_rcnn.py:2266-2435) from the point where every extent is known: the
+ * caller works out each image's resized extent (oh, ow) and the padded extent (H, W) of the batch on the host, from shapes alone
+ * (edtr_amd/detinput.py `resized_extent`, `batch_extent`).  One edtr_det_image per image, N of them in a DEVICE array that the kernel
+ * reads and the same N in a HOST array that the entry point checks before anything is launched.  Layout (24 bytes, 8-byte aligned):
+ *    0 src   fp32 planar [channels][h][w] on the device, contiguous, 4-byte aligned
+ *    8 h  12 w  the source extent   16 oh  20 ow  the resized extent                                               all int32
+ * batch [N][channels][H][W] in fp32 / fp16 / bf16 (out_dtype = EDTR_LOGITS_F32 / _F16 / _BF16).  For image i, channel c and
+ * (y, x) in [0, oh) x [0, ow):
+ *   taps     the four source elements of F.interpolate(size = (oh, ow), mode = "bilinear", align_corners = False): the source
+ *            coordinate fp32(h) / fp32(oh) * (y + 0.5) - 0.5 clamped at 0, each step rounded (what scale_factor = with
+ *            recompute_scale_factor = True reduces to), its floor cut at h - 1 and the lambda cut to [0, 1]; x alike
+ *   value    every tap normalised as (v - mean_c) / std_c, an fp32 subtraction and an IEEE division as edtr_cls_normalize does; then
+ *            the blend, columns first: top = (1 - tx) v00 + tx v01, bottom alike, out = (1 - ty) top + ty bottom, seven rounded fp32
+ *            operations, no product contracted with a sum; a 16-bit batch takes the fp32 result rounded once (to nearest even)
+ * and every other element of slot i is +0.0, written by the same launch: no memset, no requirement on what batch held, exactly one
+ * writer per word, no atomics.  The bits are those of edtr_cls_normalize -> edtr_degrade_resize(bilinear) -> a zeroed batch -> a copy,
+ * without the two intermediates.  mean_host / std_host: `channels` floats each, on the HOST.
+ * A workgroup owns an EDTR_DET_TILE_H x EDTR_DET_TILE_W tile of a slot; a lane owns four columns, whose taps it works out once for
+ * the rows and channels of the tile.  Rows move as 16 bytes per lane (8 for a 16-bit batch) where W % 4 == 0 and batch is aligned
+ * to them, element by element otherwise.  Offsets into the batch are 64-bit.
+ * Errors (nothing is launched): a NULL array, batch, mean_host, std_host or src EDTR_E_NULL; N outside 1 .. 65535, channels outside
+ * 1 .. EDTR_DET_MAX_CHANNELS, any extent (h, w, oh, ow, H, W) below 1 or above EDTR_DET_MAX_EXTENT, oh > H, ow > W, a std of 0 or a
+ * NaN constant EDTR_E_SHAPE; an unknown out_dtype EDTR_E_DTYPE; a src or batch not aligned to its element, or descs not to 8 bytes,
+ * EDTR_E_ALIGN.
+ * replaces: normalize, _resize_image_and_masks' F.interpolate and batch_images, model/faster_rcnn.py:2340-2349, 2519-2526, 2417-2435. */
+#define EDTR_DET_MAX_CHANNELS 4
+#define EDTR_DET_MAX_EXTENT 32768
+#define EDTR_DET_TILE_W 256
+#define EDTR_DET_TILE_H 16
+typedef struct edtr_det_image {
+    const float* src;
+    int32_t h; int32_t w; int32_t oh; int32_t ow;
+} edtr_det_image;
+int edtr_det_transform(const edtr_det_image* descs_host, const edtr_det_image* descs, int N, int channels, const float* mean_host,
+                       const float* std_host, int out_dtype, void* batch, int H, int W, edtr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * hipGraph capture of a launch sequence issued on `stream` (one denoise step, or a whole batch).
  * ---------------------------------------------------------------------------------------- */
