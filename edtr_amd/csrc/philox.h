@@ -1,5 +1,5 @@
 // The seeded normal stream of edtr_hip.h "Reproducible noise", shared by the kernels that draw from it (rng.hip, degrade.hip,
-// degrade2.hip): Philox4x32-10 on the counter (e >> 2, draw, purpose, image id) and the Box-Muller step that turns its four words
+// degrade2.hip, targets.hip): Philox4x32-10 on the counter (e >> 2, draw, purpose, image id) and the Box-Muller step that turns its four words
 // into the normals of four consecutive elements; and how an entry point turns (seed, image_ids, image_id_base, draw) into the
 // arguments of a launch.  One definition, so that every consumer gives the same bits, and the same answers, for the same stream.
 #pragma once
@@ -39,6 +39,11 @@ __device__ __forceinline__ f32x4 philox_normal4(uint32_t k0, uint32_t k1, uint32
     box_muller(w.z, w.w, z2, z3);
     return f32x4{z0, z1, z2, z3};
 }
+
+// The raw words of the stream (rng.uniform_words_reference): element e of image `id` receives word e & 3 of the call on the counter
+// (e >> 2, draw, purpose, id); word_of picks it without indexing the vector.  edtr_targets_sample ranks boxes by these words under
+// EDTR_NOISE_SAMPLE_RPN / EDTR_NOISE_SAMPLE_ROI, a lane owning the four boxes of one call.
+__device__ __forceinline__ uint32_t word_of(u32x4 w, int j) { return j == 0 ? w.x : (j == 1 ? w.y : (j == 2 ? w.z : w.w)); }
 
 // ---- a stream's launch arguments.  A struct with k0, k1, ids, id_base names the stream; rng.hip's has its own layout. ------------
 

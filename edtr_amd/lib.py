@@ -23,6 +23,8 @@ COCO_ACC_TILE, COCO_ACC_MAX_ROWS = 1024, 1 << 22        # EDTR_COCO_ACC_*: the s
 CLS_MAX_CLASSES, CLS_MAX_KEEP, CLS_MAX_TOPK, CLS_FD_CHUNK, CLS_FD_MAX_ELEMS = 65536, 8, 4, 4096, 1 << 28       # EDTR_CLS_*: caps of edtr_cls_*
 RPN_MAX_LEVELS, RPN_MAX_PRE_NMS, ROI_MAX_TAPS = 8, 4096, 64          # EDTR_RPN_* / EDTR_ROI_*: caps of edtr_rpn_* and edtr_roi_align
 DET_MAX_CHANNELS, DET_MAX_EXTENT, DET_TILE_W, DET_TILE_H = 4, 32768, 256, 16       # EDTR_DET_*: caps and tile of edtr_det_transform
+TARGETS_MAX_GT, TARGETS_MAX_BATCH, TARGETS_TILE = 1024, 4096, 1024      # EDTR_TARGETS_*: caps and tile of edtr_targets_*
+TARGETS_RPN, TARGETS_ROI = 0, 1         # EDTR_TARGETS_RPN / _ROI: the label form of edtr_targets_match and edtr_targets_sample
 
 DECLARED_SYMBOLS = [
     "edtr_abi_version", "edtr_error_string", "edtr_device_info", "edtr_igemm", "edtr_flash_attn64", "edtr_flash_attn64_plan",
@@ -44,6 +46,7 @@ DECLARED_SYMBOLS = [
     "edtr_cls_rank", "edtr_cls_fdist", "edtr_cls_commit", "edtr_cls_normalize", "edtr_cls_window",
     "edtr_rpn_anchors", "edtr_rpn_select", "edtr_rpn_candidates", "edtr_roi_align",
     "edtr_det_transform",
+    "edtr_targets_match", "edtr_targets_encode", "edtr_targets_sample", "edtr_targets_gather",
 ]
 
 
@@ -345,6 +348,11 @@ def load() -> C.CDLL:
     lib.edtr_roi_align.argtypes = [i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(f32), i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, vp]
     # the detector's input transform (edtr_hip.h "Detector input"): descs_host is a ctypes array of DetImage, mean / std ctypes float arrays
     lib.edtr_det_transform.argtypes = [C.POINTER(DetImage), vp, i32, i32, C.POINTER(f32), C.POINTER(f32), i32, vp, i32, i32, vp]
+    # detector training targets (edtr_hip.h "Detector training targets"): table_host is a ctypes int32 array, weights_host four ctypes floats
+    lib.edtr_targets_match.argtypes = [vp, i32, vp, vp, C.POINTER(i32), vp, i32, f32, f32, i32, i32, C.POINTER(f32), vp, vp, vp, i64, vp, vp, vp, vp]
+    lib.edtr_targets_encode.argtypes = [vp, vp, i64, C.POINTER(f32), vp, vp]
+    lib.edtr_targets_sample.argtypes = [vp, i32, C.POINTER(i32), vp, i32, i32, i32, u64, vp, i64, i64, i32, vp, vp, vp, vp, vp, vp]
+    lib.edtr_targets_gather.argtypes = [vp, vp, vp, vp, C.POINTER(i32), vp, i32, vp, i32, C.POINTER(f32), vp, vp, vp, vp, vp]
     if lib.edtr_abi_version() != 10:
         raise RuntimeError("libedtr_hip.so ABI version mismatch")
     _lib = lib

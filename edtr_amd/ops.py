@@ -1227,6 +1227,67 @@ def make_det_transform(*, descs_host, descs, mean: Sequence[float], std: Sequenc
     return Rec(L.load().edtr_det_transform, args, (descs_host, descs, m_host, s_host, batch) + tuple(keep), name, 0.0, nbytes)
 
 
+# -- detector training targets (edtr_hip.h "Detector training targets"; the callers and the host restatements are edtr_amd/targets.py) --
+def _targets_table(table_host):
+    """the ctypes int32 [N + 1][2] table of box and ground-truth starts from a list of rows"""
+    flat = [int(v) for row in table_host for v in row]
+    return (ct.c_int32 * len(flat))(*flat), len(flat) // 2 - 1
+
+
+def targets_partial_words(table_host) -> int:
+    """words of `make_targets_match`'s ``partial``: N x tiles of the longest image x the largest ground-truth count (at least 1)"""
+    rows = [tuple(int(v) for v in r) for r in table_host]
+    pmax = max([b[0] - a[0] for a, b in zip(rows, rows[1:])] + [1])
+    gmax = max([b[1] - a[1] for a, b in zip(rows, rows[1:])] + [1])
+    return (len(rows) - 1) * ((pmax + L.TARGETS_TILE - 1) // L.TARGETS_TILE) * gmax
+
+
+def make_targets_match(*, boxes, shared: bool, gt_boxes, gt_labels, table_host, table, high: float, low: float, allow_low_quality: bool, form: int,
+                       weights, best_val, best_idx, partial, matched, labels, regression=None, name="targets.match") -> Rec:
+    """Matcher over box_iou per image of a ragged batch (two launches): int32 ``matched`` and ``labels`` (fp32 for `lib.TARGETS_RPN`,
+    int64 for `lib.TARGETS_ROI`) [sum P]; with ``regression`` fp32 [sum P, 4] (RPN form) the encoding of every box against its
+    ground truth under ``weights``.  ``table_host``: rows (box_start, gt_start), N + 1 of them; ``table`` its int32 copy on the device;
+    ``best_val`` / ``best_idx`` [sum P] and ``partial`` (`targets_partial_words` uint32 words, an int32 tensor) are the scan's workspace."""
+    tab, N = _targets_table(table_host)
+    w_host = (ct.c_float * 4)(*[float(v) for v in weights])
+    args = (ptr(boxes), int(bool(shared)), ptr(gt_boxes), ptr(gt_labels), tab, ptr(table), N, float(high), float(low), int(bool(allow_low_quality)),
+            int(form), w_host, ptr(best_val), ptr(best_idx), ptr(partial), int(partial.numel()), ptr(matched), ptr(labels), ptr(regression))
+    keep = (tab, w_host, boxes, gt_boxes, gt_labels, table, best_val, best_idx, partial, matched, labels, regression)
+    G = max(int(gt_boxes.shape[0]) // max(N, 1), 1) if gt_boxes is not None else 1
+    return Rec(L.load().edtr_targets_match, args, keep, name, 30.0 * matched.numel() * G, 64.0 * matched.numel())
+
+
+def make_targets_encode(*, reference_boxes, proposals, weights, out, name="targets.encode") -> Rec:
+    """fp32 ``out`` [K, 4] = encode_boxes(``reference_boxes``, ``proposals``, ``weights``), all fp32 [K, 4] on the device"""
+    w_host = (ct.c_float * 4)(*[float(v) for v in weights])
+    args = (ptr(reference_boxes), ptr(proposals), int(out.shape[0]), w_host, ptr(out))
+    return Rec(L.load().edtr_targets_encode, args, (w_host, reference_boxes, proposals, out), name, 0.0, 48.0 * out.shape[0])
+
+
+def make_targets_sample(*, labels, form: int, table_host, table, batch: int, max_pos: int, source, draw: int, purpose: int, mask_pos, mask_neg,
+                        sampled, counts, keys=None, name="targets.sample") -> Rec:
+    """The balanced sample of every image on ``source``'s stream: uint8 ``mask_pos`` / ``mask_neg`` [sum P], int32 ``sampled`` [N, batch]
+    (ascending, then -1) and ``counts`` [N, 2] = num_pos, num_neg.  ``keys``: None, or int32 / uint32 words [sum P] on the device that take the
+    stream's place (``source`` may then be None)"""
+    tab, N = _targets_table(table_host)
+    seed, ids_p, base, ids = (0, None, 0, None) if source is None and keys is not None else _noise_args(source, N, labels.device, name)
+    args = (ptr(labels), int(form), tab, ptr(table), N, int(batch), int(max_pos), seed, ids_p, base, int(draw), int(purpose), ptr(keys), ptr(mask_pos),
+            ptr(mask_neg), ptr(sampled), ptr(counts))
+    keep = (tab, ids, labels, keys, table, mask_pos, mask_neg, sampled, counts)
+    return Rec(L.load().edtr_targets_sample, args, keep, name, 0.0, 5.0 * labels.element_size() * labels.numel())
+
+
+def make_targets_gather(*, boxes, gt_boxes, matched, labels, table_host, table, sampled, weights, out_boxes, out_labels, out_matched, out_targets,
+                        name="targets.gather") -> Rec:
+    """The sampled boxes of every image with their labels, clamped matches and regression targets: ``out_boxes`` / ``out_targets`` fp32
+    [N, batch, 4], ``out_labels`` / ``out_matched`` int64 [N, batch]"""
+    tab, N = _targets_table(table_host)
+    w_host = (ct.c_float * 4)(*[float(v) for v in weights])
+    args = (ptr(boxes), ptr(gt_boxes), ptr(matched), ptr(labels), tab, ptr(table), N, ptr(sampled), int(sampled.shape[1]), w_host, ptr(out_boxes),
+            ptr(out_labels), ptr(out_matched), ptr(out_targets))
+    keep = (tab, w_host, boxes, gt_boxes, matched, labels, table, sampled, out_boxes, out_labels, out_matched, out_targets)
+    return Rec(L.load().edtr_targets_gather, args, keep, name, 0.0, 80.0 * sampled.numel())
+
 
 def make_cast16(*, dtype, src: torch.Tensor, rows: int, C: int, dst: torch.Tensor, name="cast16") -> Rec:
     args = (dt_code(dtype), ptr(src), rows, C, src.stride(0), ptr(dst), dst.stride(0))

@@ -28,6 +28,10 @@ DEGRADE_PURPOSES = (PURPOSE_DEGRADE, PURPOSE_DEGRADE_GRAY)
 # colour / grey noise of edtr_degrade_poisson_noise: the raw words of the same counters (`uniform_words_reference`), never normals
 PURPOSE_DEGRADE_POISSON, PURPOSE_DEGRADE_POISSON_GRAY = 6, 7
 POISSON_PURPOSES = (PURPOSE_DEGRADE_POISSON, PURPOSE_DEGRADE_POISSON_GRAY)
+# the keys of `targets.sample` in place of torch.randperm (draw = the training step), for the RPN's anchors and the box head's proposals:
+# raw words again; only `uniform_words_reference` evaluates them
+PURPOSE_SAMPLE_RPN, PURPOSE_SAMPLE_ROI = 8, 9
+SAMPLE_PURPOSES = (PURPOSE_SAMPLE_RPN, PURPOSE_SAMPLE_ROI)
 Z_MAX = float(np.sqrt(48.0 * np.log(2.0)))      # u1 >= 2^-24: no value of the stream is larger in magnitude
 
 _M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
@@ -78,8 +82,8 @@ def normal_reference(seed: int, image_ids, purpose: int, draw, per_image: int) -
 def uniform_words_reference(seed: int, image_ids, purpose: int, draw, per_image: int) -> np.ndarray:
     """uint32 [B][per_image]: the raw Philox words of the stream, element e of an image receiving word e & 3 of the call on the counter
     (e >> 2, draw, purpose, image id) — what edtr_degrade_poisson_noise inverts its tables with.  Every purpose of the header."""
-    if purpose not in PURPOSES + DEGRADE_PURPOSES + POISSON_PURPOSES:
-        raise ValueError(f"purpose must be one of {PURPOSES + DEGRADE_PURPOSES + POISSON_PURPOSES}, got {purpose}")
+    if purpose not in PURPOSES + DEGRADE_PURPOSES + POISSON_PURPOSES + SAMPLE_PURPOSES:
+        raise ValueError(f"purpose must be one of {PURPOSES + DEGRADE_PURPOSES + POISSON_PURPOSES + SAMPLE_PURPOSES}, got {purpose}")
     return _words(seed, image_ids, purpose, draw, per_image).reshape(-1, per_image)
 
 

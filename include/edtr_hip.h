@@ -1346,6 +1346,75 @@ typedef struct edtr_det_image {
 int edtr_det_transform(const edtr_det_image* descs_host, const edtr_det_image* descs, int N, int channels, const float* mean_host,
                        const float* std_host, int out_dtype, void* batch, int H, int W, edtr_stream_t stream);
 
+/* ---- Detector training targets: match, encode, sample (additive to ABI 10) ------------------------------------------------------------
+ * The non-learned half of the reference's Faster R-CNN in train mode (main/det/train_edtr.py:205-240): Matcher over box_iou,
+ * BoxCoder.encode and BalancedPositiveNegativeSampler, as RegionProposalNetwork.assign_targets_to_anchors and
+ * RoIHeads.select_training_samples run them (model/faster_rcnn.py:2030-2066, 1087-1185; model/util.py:594-679, 746-920).  No gradient
+ * flows through any of it.  edtr_amd/targets.py restates every launch in numpy and writes the rules out; the launches equal the
+ * restatements bit for bit except where logf enters (the dw and dh of an encoding).
+ * The batch is ragged: image n owns boxes [box_start_n, box_start_{n+1}) and ground truths [gt_start_n, gt_start_{n+1}) of the flat
+ * arrays.  table_host: int32 [N + 1][2] = box_start, gt_start on the HOST (checked before anything is launched), table: its copy on
+ * the device (read by the kernels); both start at 0.  Boxes are fp32 xyxy, 16-byte aligned.
+ * Common errors (nothing is launched): a NULL pointer EDTR_E_NULL; N <= 0, a table that does not start at 0, an image without a box
+ * or with a negative count EDTR_E_SHAPE; N > 65535, an image of 2^24 boxes or more, or of more than EDTR_TARGETS_MAX_GT ground truths
+ * EDTR_E_UNSUPPORTED; an unknown form or flag EDTR_E_DTYPE; boxes not aligned to 16 bytes, the others to their element EDTR_E_ALIGN. */
+#define EDTR_TARGETS_MAX_GT 1024        /* ground truths of one image: they are kept in LDS */
+#define EDTR_TARGETS_MAX_BATCH 4096     /* batch_size_per_image of the sampler */
+#define EDTR_TARGETS_TILE 1024          /* boxes of one workgroup of the match passes */
+#define EDTR_TARGETS_RPN 0              /* labels fp32: 1 matched, 0 below the low threshold, -1 between the thresholds */
+#define EDTR_TARGETS_ROI 1              /* labels int64: gt_labels[matched], 0 below the low threshold, -1 between the thresholds */
+#define EDTR_NOISE_SAMPLE_RPN 8         /* the sampler's keys for the RPN's anchors (draw = the training step): raw words, never normals */
+#define EDTR_NOISE_SAMPLE_ROI 9         /* the sampler's keys for the box head's proposals (draw = the training step) */
+/* Matcher(high, low, allow_low_quality) over box_iou(gt, boxes) per image, with no [G][P] matrix in memory.
+ *   iou      area = (x2 - x1) (y2 - y1); w, h = max(min(rb) - max(lt), 0) (a NaN stays); inter = w h; iou = inter / ((area_g + area_p)
+ *            - inter): each step one rounded fp32 operation, IEEE division
+ *   best     per box the first maximal ground truth, a NaN counting as the maximum (torch's max(dim=0))
+ *   matched  -1 where best < low, -2 where low <= best < high (a NaN compares false both times), else the index
+ *   restore  with allow_low_quality: highest[g] = max over the image's boxes of iou[g][p] (a NaN propagates); every box whose iou with
+ *            some g equals highest[g] gets its own best index back (set_low_quality_matches_, including that a ground truth which
+ *            overlaps nothing restores every box whose iou with it is 0)
+ * Two launches: a scan (a workgroup per EDTR_TARGETS_TILE boxes of an image, the image's ground truths in LDS) writes best_val,
+ * best_idx [sum P] and partial [N][tiles][gmax] (uint32 order-preserving keys of each tile's greatest iou per ground truth; tiles =
+ * ceil(max P / EDTR_TARGETS_TILE), gmax = max(max G, 1); partial_words >= N tiles gmax, EDTR_E_SHAPE otherwise); the assign pass folds
+ * the keys in LDS and recomputes the ious it needs with the same code, the same bits.  No device-wide atomic.
+ * shared = 1: boxes is one [P][4] set that every image uses (the RPN's anchors; every image's count must be P).  matched: int32
+ * [sum P].  labels [sum P] by form (EDTR_TARGETS_RPN / _ROI; gt_labels: int64 [sum G], needed for _ROI).  regression (RPN form,
+ * optional): fp32 [sum P][4], the encoding below of gt[max(matched, 0)] against every box with weights_host (four HOST floats).  An
+ * image without ground truth: matched 0, label 0, encoded against the zero box (the reference's background branch).
+ * low > high or a NaN threshold EDTR_E_SHAPE.
+ * replaces: box_iou, Matcher.__call__, set_low_quality_matches_, assign_targets_to_anchors, assign_targets_to_proposals. */
+int edtr_targets_match(const float* boxes, int shared, const float* gt_boxes, const int64_t* gt_labels, const int32_t* table_host,
+                       const int32_t* table, int N, float high, float low, int allow_low_quality, int form, const float* weights_host,
+                       float* best_val, int32_t* best_idx, uint32_t* partial, int64_t partial_words, int32_t* matched, void* labels,
+                       float* regression, edtr_stream_t stream);
+/* out [K][4] = encode_boxes(reference_boxes [K][4], proposals [K][4], weights) in the reference's operation order, each step rounded:
+ * ew = px2 - px1, ecx = px1 + 0.5 ew, gw, gcx alike; dx = (wx (gcx - ecx)) / ew, dw = ww logf(gw / ew); y, h alike.
+ * K <= 0 or a NaN weight EDTR_E_SHAPE; K > 2^30 EDTR_E_UNSUPPORTED.  replaces: BoxCoder.encode_single, model/util.py:594-679. */
+int edtr_targets_encode(const float* reference_boxes, const float* proposals, int64_t K, const float* weights_host, float* out,
+                        edtr_stream_t stream);
+/* BalancedPositiveNegativeSampler with torch.randperm replaced by the seeded stream of "Reproducible noise".  Per image: positives are
+ * labels >= 1, negatives labels == 0 (labels [sum P]: fp32 for EDTR_TARGETS_RPN, int64 for EDTR_TARGETS_ROI); num_pos = min(#positive,
+ * max_pos), num_neg = min(#negative, batch - num_pos) (max_pos = int(batch positive_fraction), the caller's).  The key of box i is word
+ * i & 3 of Philox on the counter (i >> 2, draw, purpose, image id), purpose EDTR_NOISE_SAMPLE_RPN or _ROI (EDTR_E_DTYPE otherwise); key,
+ * ids and draw as for every stream consumer; keys (optional, uint32 [sum P] on the device) takes the stream's place: tests hand
+ * equal keys in, which the stream practically never gives.  Sampled: the num_pos positives with the smallest keys, equal keys to the smaller index;
+ * the negatives alike.  mask_pos, mask_neg: uint8 [sum P]; sampled: int32 [N][batch], the sampled image-local indices in ascending
+ * order, then -1; counts: int32 [N][2] = num_pos, num_neg.  One 1024-lane workgroup per image: a radix select on the 32-bit key
+ * (histograms by integer adds in LDS), then ordered ballots in index order.  No host sync.
+ * batch <= 0, max_pos outside [0, batch], draw outside [0, 2^32) EDTR_E_SHAPE; batch > EDTR_TARGETS_MAX_BATCH EDTR_E_UNSUPPORTED.
+ * replaces: BalancedPositiveNegativeSampler.__call__ with its two torch.randperm per image, model/util.py:860-920. */
+int edtr_targets_sample(const void* labels, int form, const int32_t* table_host, const int32_t* table, int N, int batch, int max_pos,
+                        uint64_t seed, const int64_t* image_ids, int64_t image_id_base, int64_t draw, int purpose, const uint32_t* keys,
+                        uint8_t* mask_pos, uint8_t* mask_neg, int32_t* sampled, int32_t* counts, edtr_stream_t stream);
+/* The last step of select_training_samples in one launch.  For slot (n, j) with i = sampled[n][j] >= 0: out_boxes = boxes[i] of image n,
+ * out_labels = labels[i], out_matched = max(matched[i], 0), out_targets = the encoding of that ground truth (the zero box for an image
+ * without any) against the box with weights_host.  A slot with i < 0: zeros, label -1.  out_boxes, out_targets: fp32 [N][batch][4];
+ * out_labels, out_matched: int64 [N][batch].
+ * replaces: the gathers by sampled_inds and BoxCoder.encode, model/faster_rcnn.py:1171-1185. */
+int edtr_targets_gather(const float* boxes, const float* gt_boxes, const int32_t* matched, const int64_t* labels, const int32_t* table_host,
+                        const int32_t* table, int N, const int32_t* sampled, int batch, const float* weights_host, float* out_boxes,
+                        int64_t* out_labels, int64_t* out_matched, float* out_targets, edtr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * hipGraph capture of a launch sequence issued on `stream` (one denoise step, or a whole batch).
  * ---------------------------------------------------------------------------------------- */
