@@ -217,12 +217,9 @@ __device__ __forceinline__ int gn_ld_of(const edtr_igemm_params& p) { return p.g
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// tile 17 of edtr_igemm lives in its own translation unit (halo512.hip)
-bool edtr_halo512_ok(const edtr_igemm_params& p);
+// tiles 17, 21 and 20 of edtr_igemm live in their own translation unit (halo512.hip); what they accept: igemm_plan.h
 int edtr_launch_halo512(const edtr_igemm_params& p, hipStream_t stream);
-bool edtr_halo512p_ok(const edtr_igemm_params& p);           // tile 21
 int edtr_launch_halo512p(const edtr_igemm_params& p, hipStream_t stream);
-bool edtr_halo160_ok(const edtr_igemm_params& p);            // tile 20
 int edtr_launch_halo160(const edtr_igemm_params& p, hipStream_t stream);
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is PER DEVICE: one flag per (launch site, device), not one per process (ADVICE r04:

@@ -27,6 +27,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
+#include "igemm_plan.h"
 
 // Diagnostic build only (tools/exp/halo512_stamps.py compiles with -DEDTR_STAMPS): thread 0 of every workgroup stores s_memtime at
 // phase boundaries into p.workspace (unused by this tile otherwise).  The product library contains no stamp code.
@@ -67,7 +68,7 @@ __device__ __forceinline__ void dma(uint32_t voff, const u32x4& srd, uint32_t so
 
 template <int V> using IC = std::integral_constant<int, V>;
 
-constexpr int CK = 32;                          // channels per chunk = K of one 16x16x32 MFMA
+using igemm_plan::CK;                           // channels per chunk = K of one 16x16x32 MFMA
 constexpr int WTAP = 128 * CK * 2;              // 8 KiB: one tap's [128][32] weight slice
 namespace h1 {                                  // tile 17
 constexpr int PW = 34, PROWS = 18, PPIX = PW * PROWS, PROWB = PW * 64;
@@ -1368,35 +1369,13 @@ int launch_halo512p(const edtr_igemm_params& p, hipStream_t stream) {
 
 }  // namespace
 
-// tile 21 = tile 17's shapes with a 16-bit output, no residual, no time-embedding row, an even number of 32-channel chunks
-bool edtr_halo512p_ok(const edtr_igemm_params& p) {
-    return edtr_halo512_ok(p) && !p.out_f32 && !p.out16 && !p.residual && !p.rowvec && p.N <= 512 && ((p.C1 / CK) & 1) == 0 &&
-           (int64_t)p.M * p.ldc * 2 < 0xF0000000LL;      // (the output is written by buffer-addressed stores)
-}
-
 int edtr_launch_halo512p(const edtr_igemm_params& p, hipStream_t stream) {
     return p.dtype == EDTR_BF16 ? launch_halo512p<BF16>(p, stream) : launch_halo512p<F16>(p, stream);
 }
 
-// shape / option requirements of tile 17 (the caller has validated the generic edtr_igemm rules and buffer addressability)
-bool edtr_halo512_ok(const edtr_igemm_params& p) {
-    return p.OH > 0 && p.taps == 9 && p.stride == 1 && p.pad_t == 1 && p.pad_l == 1 && p.C2 == 0 && (p.C1 % CK) == 0 && !p.upsample2x &&
-           p.OH == p.IH && p.OW == p.IW && (p.OH & 15) == 0 && (p.OW & 31) == 0 && p.Z == 1 && p.splitk <= 1 && p.act == EDTR_ACT_NONE &&
-           !p.bias_m && (p.N & 127) == 0 && (p.n_valid == 0 || p.n_valid == p.N) && !p.vt_out && !p.row_stats && !p.ln_stats && !p.a_wrap &&
-           p.M == (p.M / (p.OH * p.OW)) * p.OH * p.OW && (!p.rowvec || p.rows_per_image == p.OH * p.OW) &&
-           (!p.residual || p.residual_f32 || (int64_t)p.M * p.ldr * 2 < 0xF0000000LL);      // (a 16-bit residual is fetched by buffer-addressed DMA)
-}
-
+// (what tiles 17, 20 and 21 accept: edtr_halo512_ok, edtr_halo160_ok, edtr_halo512p_ok in igemm_plan.h, next to the rules that call them)
 int edtr_launch_halo512(const edtr_igemm_params& p, hipStream_t stream) {
     return p.dtype == EDTR_BF16 ? launch_halo512<BF16>(p, stream) : launch_halo512<F16>(p, stream);
-}
-
-// tile 20: 16 x 16-pixel units x 160 channels (no a_gn: the emitters fuse a GroupNorm input only into N <= 128 convolutions)
-bool edtr_halo160_ok(const edtr_igemm_params& p) {
-    return p.OH > 0 && p.taps == 9 && p.stride == 1 && p.pad_t == 1 && p.pad_l == 1 && p.C2 == 0 && (p.C1 % CK) == 0 && !p.upsample2x &&
-           p.OH == p.IH && p.OW == p.IW && (p.OH & 15) == 0 && (p.OW & 15) == 0 && p.Z == 1 && p.splitk <= 1 && p.act == EDTR_ACT_NONE &&
-           !p.bias_m && p.N % 160 == 0 && (p.n_valid == 0 || p.n_valid == p.N) && !p.vt_out && !p.row_stats && !p.ln_stats && !p.a_wrap && !p.a_gn &&
-           p.M == (p.M / (p.OH * p.OW)) * p.OH * p.OW && (!p.rowvec || p.rows_per_image == p.OH * p.OW);
 }
 
 int edtr_launch_halo160(const edtr_igemm_params& p, hipStream_t stream) {
@@ -1404,6 +1383,9 @@ int edtr_launch_halo160(const edtr_igemm_params& p, hipStream_t stream) {
 }
 
 #ifdef EDTR_STAMPS
+using igemm_plan::edtr_halo160_ok;
+using igemm_plan::edtr_halo512_ok;
+using igemm_plan::edtr_halo512p_ok;
 extern "C" int edtr_halo512_stamped(const edtr_igemm_params* p, void* stream) {      // stand-alone diagnostic build: no edtr_igemm in front
     if (p->tile == 20) return edtr_halo160_ok(*p) ? edtr_launch_halo160(*p, static_cast<hipStream_t>(stream)) : EDTR_E_UNSUPPORTED;
     if (p->tile == 21) return edtr_halo512p_ok(*p) ? edtr_launch_halo512p(*p, static_cast<hipStream_t>(stream)) : EDTR_E_UNSUPPORTED;

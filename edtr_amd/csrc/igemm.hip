@@ -12,6 +12,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
+#include "igemm_plan.h"
 
 // Diagnostic build only (tools/exp/igemm_stamps.py compiles with -DEDTR_STAMPS): thread 0 of every workgroup stores
 // s_memtime at a few phase boundaries into p.workspace (otherwise unused when splitk <= 1).  The product library
@@ -2437,91 +2438,35 @@ int launch_halo(const edtr_igemm_params& p, hipStream_t stream) {
     return EDTR_OK;
 }
 
-// the halo tile's shape requirements (the caller checks buffer addressability)
-// four whole 8 x 8 images per workgroup (GEO 2 of the halo kernel)
-static bool igemm_halo_img8(const edtr_igemm_params& p) {
-    return !p.upsample2x && p.OH == 8 && p.OW == 8 && p.IH == 8 && p.IW == 8 && (p.M & 255) == 0;
-}
-
-static bool igemm_halo_ok(const edtr_igemm_params& p, bool spatial) {
-    const int up = p.upsample2x ? 2 : 1;
-    if (p.upsample2x == 2 && ((p.IH & 15) || (p.IW & 15) || p.w_phase_stride < (int64_t)p.N * p.ldw || p.ldw < 4 * p.C1)) return false;   // sub-pixel form: 16 x 16 source blocks
-    return spatial && p.taps == 9 && p.stride == 1 && p.pad_t == 1 && p.pad_l == 1 && p.C2 == 0 && (p.C1 & 63) == 0 &&
-           p.OH == p.IH * up && p.OW == p.IW * up && (((p.OH & 15) == 0 && (p.OW & 15) == 0) || igemm_halo_img8(p)) && p.Z == 1 &&
-           p.splitk <= p.C1 / 64 && p.act != EDTR_ACT_GEGLU && p.M == (p.M / (p.OH * p.OW)) * p.OH * p.OW;
-}
-
-static bool igemm_fast_addressable(const edtr_igemm_params& p, bool spatial) {
-    const int64_t a_rows = spatial ? (int64_t)(p.M / (p.OH * p.OW)) * p.IH * p.IW : p.M;
-    const int64_t a_bytes = (a_rows + (spatial ? 3 * (int64_t)p.IW + 3 : 0)) * p.ld1 * 2 + (int64_t)p.K * 2;
-    const int64_t w_bytes = (int64_t)p.N * p.ldw * 2 + (int64_t)p.K * 2;
-    return a_bytes < 0xF0000000LL && w_bytes < 0xF0000000LL;
-}
-
-// A/B switches for measurements on one device (edtr_hip.h: debug_flags)
-static int dbg_flags() {
-    static int dbg = -1;
-    if (dbg < 0) {
-        const char* e8 = getenv("EDTR_IGEMM_GENERAL_EPILOGUE");
-        const char* e10 = getenv("EDTR_IGEMM_N160_TWO_PASS");
-        const char* e12 = getenv("EDTR_IGEMM_GEGLU_SERIAL");
-        dbg = ((e8 && e8[0] == '1') ? 1 : 0) | ((e10 && e10[0] == '1') ? 2 : 0) | ((e12 && e12[0] == '1') ? 4 : 0);
-    }
-    return dbg;
-}
-
-// dry: edtr_igemm_plan — every check of the chosen kernel, no launch; the answer is the tile number
+// An IgemmPlan (igemm_plan.h: every check and every choice) as a launch; nothing is checked here.
 template <typename T>
-int dispatch(const edtr_igemm_params& p, int tile, bool spatial, hipStream_t s, bool dry) {
-    if (tile == 20) {      // halo tile, 16 x 16 pixels x 160 channels (halo512.hip)
-        if (!spatial || !edtr_halo160_ok(p) || !igemm_fast_addressable(p, spatial)) return EDTR_E_UNSUPPORTED;
-        if (dry) return tile;
-        return edtr_launch_halo160(p, s);
-    }
-    if (tile == 21) {      // tile 17 as a persistent kernel with deferred stores (halo512.hip)
-        if (!spatial || !edtr_halo512p_ok(p) || !igemm_fast_addressable(p, spatial)) return EDTR_E_UNSUPPORTED;
-        if (dry) return tile;
-        return edtr_launch_halo512p(p, s);
-    }
-    if (tile == 17) {      // halo tile, 512-pixel units (halo512.hip)
-        if (!spatial || !edtr_halo512_ok(p) || !igemm_fast_addressable(p, spatial)) return EDTR_E_UNSUPPORTED;
-        if (dry) return tile;
-        return edtr_launch_halo512(p, s);
-    }
-    if (tile == 16) {      // halo tile for 3x3 / stride 1 convolutions
-        if (!igemm_halo_ok(p, spatial) || !igemm_fast_addressable(p, spatial)) return EDTR_E_UNSUPPORTED;
-        if (dry) return tile;
-        if (igemm_halo_img8(p)) return launch_halo<T, 2>(p, s);
-        if (p.upsample2x == 2) return launch_halo<T, 3>(p, s);
-        if (p.a3) return launch_halo<T, 4>(p, s);
-        return p.upsample2x ? launch_halo<T, 1>(p, s) : launch_halo<T, 0>(p, s);
-    }
-    if (tile >= 3 && tile <= 14) {
-        // buffer-addressed fast path: 32-bit byte offsets must cover the A and W operands (per z slice)
-        const bool fast = (!p.upsample2x || (p.stride == 1 && (tile == 3 || tile >= 6))) && igemm_fast_addressable(p, spatial);
-        if (tile == 14) {  // 256 x 32 tile for skinny-N convolutions (N <= 32: the decoder's 3-channel output conv wastes 94 % of a
-                           // 128-wide tile); an instantiation of the 16x16x32 template, experiment, same status
-            if (!fast || p.act == EDTR_ACT_GEGLU || p.gn_partial) return EDTR_E_UNSUPPORTED;
-            if (dry) return tile;
-            return spatial ? launch_n160<T, true, 8, 1>(p, s) : launch_n160<T, false, 8, 1>(p, s);
+int launch_plan(const igemm_plan::IgemmPlan& pl, hipStream_t s) {
+    const edtr_igemm_params& p = pl.p;
+    const bool spatial = pl.spatial;
+    switch (pl.rc) {
+    case 1: return spatial ? launch<T, 2, 2, true>(p, s) : launch<T, 2, 2, false>(p, s);
+    case 2: return spatial ? launch<T, 1, 1, true>(p, s) : launch<T, 1, 1, false>(p, s);
+    case 3:     // buffer-addressed fast path where 32-bit byte offsets cover the A and W operands (per z slice)
+        if (!spatial) return pl.fast ? launch_dma<T, false, true>(p, s) : launch_dma<T, false, false>(p, s);
+        return pl.fast ? launch_dma<T, true, true>(p, s) : launch_dma<T, true, false>(p, s);
+    case 6: return spatial ? launch_256<T, true>(p, s) : launch_256<T, false>(p, s);
+    case 8: return spatial ? launch_n160<T, true, 4, 5>(p, s) : launch_n160<T, false, 4, 5>(p, s);
+    case 14:    // 256 x 32 tile for skinny-N convolutions (N <= 32: the decoder's 3-channel output conv wastes 94 % of a 128-wide tile);
+                // an instantiation of the 16x16x32 template
+        return spatial ? launch_n160<T, true, 8, 1>(p, s) : launch_n160<T, false, 8, 1>(p, s);
+    case 16:    // halo tile for 3x3 / stride 1 convolutions, five geometries
+        switch (pl.halo_geo) {
+        case 1: return launch_halo<T, 1>(p, s);
+        case 2: return launch_halo<T, 2>(p, s);
+        case 3: return launch_halo<T, 3>(p, s);
+        case 4: return launch_halo<T, 4>(p, s);
+        default: return launch_halo<T, 0>(p, s);
         }
-        if (tile == 8) {
-            if (!fast || p.act == EDTR_ACT_GEGLU) return EDTR_E_UNSUPPORTED;
-            if (dry) return tile;
-            return spatial ? launch_n160<T, true, 4, 5>(p, s) : launch_n160<T, false, 4, 5>(p, s);
-        }
-        if (tile == 6) {
-            if (!fast || p.splitk > 1 || p.act == EDTR_ACT_GEGLU) return EDTR_E_UNSUPPORTED;
-            if (dry) return tile;
-            return spatial ? launch_256<T, true>(p, s) : launch_256<T, false>(p, s);
-        }
-        if (dry) return tile;
-        if (!spatial) return fast ? launch_dma<T, false, true>(p, s) : launch_dma<T, false, false>(p, s);
-        return fast ? launch_dma<T, true, true>(p, s) : launch_dma<T, true, false>(p, s);
+    case 17: return edtr_launch_halo512(p, s);      // halo tiles of halo512.hip: 512-pixel units,
+    case 20: return edtr_launch_halo160(p, s);      // 16 x 16 pixels x 160 channels,
+    case 21: return edtr_launch_halo512p(p, s);     // tile 17 as a persistent kernel with deferred stores
+    default: return pl.rc;                          // the plan's error
     }
-    if (dry) return tile;
-    if (tile == 1) return spatial ? launch<T, 2, 2, true>(p, s) : launch<T, 2, 2, false>(p, s);
-    return spatial ? launch<T, 1, 1, true>(p, s) : launch<T, 1, 1, false>(p, s);
 }
 
 }  // namespace
@@ -2619,271 +2564,14 @@ extern "C" int edtr_gn_table(const float* partial, int tiles_per_image, const do
     return EDTR_OK;
 }
 
-static int igemm_run(const edtr_igemm_params* pp, edtr_stream_t stream, bool dry) {
-    if (!pp) return EDTR_E_NULL;
-    edtr_igemm_params p = *pp;
-    if (!p.a1 || !p.w || !p.out) return EDTR_E_NULL;
-    if (p.dtype != EDTR_BF16 && p.dtype != EDTR_F16) return EDTR_E_DTYPE;
-    if (p.taps != 1 && p.taps != 9) return EDTR_E_UNSUPPORTED;
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.Z <= 0) return EDTR_E_SHAPE;
-    if (p.zdiv <= 0) p.zdiv = 1;
-    if (p.C2 > 0 && !p.a2) return EDTR_E_NULL;
-    if (p.C2 < 0 || p.C1 <= 0) return EDTR_E_SHAPE;
-    if (!p.a3 || p.C3 == 0) { p.a3 = nullptr; p.C3 = 0; p.ld3 = 0; }     // no K tail
-    if (p.C3 < 0) return EDTR_E_SHAPE;
-    if (p.K != p.taps * (p.C1 + p.C2) + p.C3) return EDTR_E_SHAPE;
-    const bool spatial = p.OH > 0;
-    if (p.a3) {     // K tail: the halo tiles' plain 3x3 / stride 1 / pad 1 geometry only (the tile is checked once it is chosen)
-        if (p.taps != 9 || !spatial || p.stride != 1 || p.pad_t != 1 || p.pad_l != 1 || p.upsample2x || p.C2 != 0 || (p.C3 & 63) ||
-            (p.C1 & 63) || p.a_wrap != 0 || p.Z != 1 || p.act == EDTR_ACT_GEGLU)
-            return EDTR_E_UNSUPPORTED;
-        if (p.ld3 < p.C3 || p.ldw < p.K) return EDTR_E_SHAPE;
-        if ((p.ld3 & 7) || !aligned16(p.a3)) return EDTR_E_ALIGN;
-        if (((int64_t)p.M * p.ld3 + p.C3) * 2 >= 0xF0000000LL) return EDTR_E_UNSUPPORTED;    // 32-bit buffer offsets
-    }
-    const int ksel = p.K - p.C3;      // the tile rules below see the 9-tap product: a tail does not move a convolution to another tile
-    if (p.taps == 9 && !spatial) return EDTR_E_SHAPE;
-    if (spatial) {
-        if (p.OW <= 0 || p.IH <= 0 || p.IW <= 0 || p.stride <= 0) return EDTR_E_SHAPE;
-        if (p.M % (p.OH * p.OW) != 0) return EDTR_E_SHAPE;
-    }
-    if (p.upsample2x < 0 || p.upsample2x > 2) return EDTR_E_SHAPE;
-    if (p.act < EDTR_ACT_NONE || p.act > EDTR_ACT_LRELU) return EDTR_E_DTYPE;
-    if (p.act == EDTR_ACT_LRELU && !(p.act_slope >= 0.0f && p.act_slope <= 1.0f)) return EDTR_E_SHAPE;
-    if (p.rowvec && p.rows_per_image <= 0) return EDTR_E_SHAPE;
-    // 16-byte rule
-    if ((p.K & 7) || (p.N & 7) || (p.C1 & 7) || (p.C2 & 7) || (p.ld1 & 7) || (p.C2 && (p.ld2 & 7)) || (p.ldw & 7))
-        return EDTR_E_ALIGN;
-    const int n_out = p.act == EDTR_ACT_GEGLU ? p.N / 2 : p.N;
-    if (p.act == EDTR_ACT_GEGLU && (p.N & 63)) return EDTR_E_ALIGN;
-    if ((n_out & 7) || (p.ldc & (p.out_f32 ? 3 : 7)) || (p.residual && (p.ldr & (p.residual_f32 ? 3 : 7)))) return EDTR_E_ALIGN;
-    if (!aligned16(p.a1) || !aligned16(p.w) || !aligned16(p.out) || (p.a2 && !aligned16(p.a2)) ||
-        (p.residual && !aligned16(p.residual)))
-        return EDTR_E_ALIGN;
-    if ((p.a_zs_outer & 7) || (p.a_zs_inner & 7) || (p.w_zs_outer & 7) || (p.w_zs_inner & 7) ||
-        (p.o_zs_outer & 3) || (p.o_zs_inner & 3))
-        return EDTR_E_ALIGN;
-    // the epilogue reads bias / time-embedding rows as 16-byte vectors
-    if ((p.bias_n && !aligned16(p.bias_n)) || (p.rowvec && (!aligned16(p.rowvec) || (p.rowvec_ld & 3)))) return EDTR_E_ALIGN;
-    if (p.n_valid < 0 || p.n_valid > p.N) return EDTR_E_SHAPE;
-    if (p.residual && p.Z != 1) return EDTR_E_UNSUPPORTED;  // residual / rowvec are not z-batched
-    if (p.rowvec && p.Z != 1) return EDTR_E_UNSUPPORTED;
-    if (p.splitk < 0) return EDTR_E_SHAPE;
-    if (p.splitk <= 1) p.splitk = 1;
-    if (p.splitk > 1) {
-        if (p.Z != 1 || p.act == EDTR_ACT_GEGLU) return EDTR_E_UNSUPPORTED;
-        if (!p.workspace) return EDTR_E_NULL;
-        if (p.workspace_bytes < (int64_t)p.splitk * p.M * p.N * 4 || !aligned16(p.workspace)) return EDTR_E_SHAPE;
-        if (p.splitk > (p.K + 63) / 64) return EDTR_E_SHAPE;
-    }
-
-    if (p.vt_out) {
-        if (p.Z != 1 || p.splitk > 1 || p.act == EDTR_ACT_GEGLU || p.residual || p.rowvec || p.gn_partial || p.out_f32 || spatial)
-            return EDTR_E_UNSUPPORTED;
-        if (p.rows_per_image <= 0 || (p.rows_per_image & 7) || (p.M & 7) || p.vt_col0 <= 0 || p.vt_col0 >= p.N) return EDTR_E_SHAPE;
-        if ((p.vt_ld & 7) || p.vt_ld < p.rows_per_image || !aligned16(p.vt_out)) return EDTR_E_ALIGN;
-    }
-
-    if (p.row_stats) {
-        if (p.Z != 1 || p.splitk > 1 || p.act == EDTR_ACT_GEGLU || p.vt_out) return EDTR_E_UNSUPPORTED;
-        if (p.N & 31) return EDTR_E_SHAPE;
-        if (!aligned16(p.row_stats)) return EDTR_E_ALIGN;
-    }
-    if (p.ln_stats) {
-        if (p.Z != 1 || p.splitk > 1 || p.taps != 1 || spatial || p.C2) return EDTR_E_UNSUPPORTED;
-        if (!p.ln_c1 || !p.ln_c2) return EDTR_E_NULL;
-        // ln_C = the number of REAL columns the statistics run over (SwinIR keeps 180 channels in rows of 192 whose pad columns are
-        // exactly zero: they add nothing to the slots); the slots cover the K = ln_slots * 32 stored columns
-        if (p.ln_slots <= 0 || p.ln_slots * 32 != p.K || p.ln_C <= 0 || p.ln_C > p.K) return EDTR_E_SHAPE;
-        if (!aligned16(p.ln_stats) || !aligned16(p.ln_c1) || !aligned16(p.ln_c2)) return EDTR_E_ALIGN;
-    }
-
-    // the LDS-DMA main loops need every 64-wide K-tile inside one tap of one source
-    const bool dma_ok = p.C2 == 0 && (p.C1 & 63) == 0;
-    int tile = p.tile;
-    if (tile == 0) {   // default: the LDS-DMA kernels wherever they apply
-        const int64_t big = (int64_t)((p.M + 127) / 128) * ((p.N + 127) / 128) * p.Z;
-        tile = dma_ok ? 3 : (big >= 200 ? 1 : 2);
-        // 256x256 ping-pong kernel: large-K convolutions whose 256-column tiles are mostly full and fill >= half the CUs
-        // (measured on MI355X: 1.17-1.32 PFLOP/s vs 0.98-1.05 for the 128x128 loop on the VAE convolutions)
-        const int nbn256 = (p.N + 255) / 256;
-        const int64_t nb256 = (int64_t)((p.M + 255) / 256) * nbn256 * p.Z;
-        // A/B switch for measurements on ONE device (devices differ by several percent): bit i of EDTR_IGEMM_NO_AUTO
-        // disables the automatic choice of tile i (6, 8, 9); explicit p.tile requests are unaffected.
-        static int no_auto = -1;
-        if (no_auto < 0) {
-            const char* e = getenv("EDTR_IGEMM_NO_AUTO");
-            no_auto = e ? atoi(e) : 0;
-        }
-        const bool pp_ok = dma_ok && p.splitk <= 1 && p.act != EDTR_ACT_GEGLU && (!p.upsample2x || p.stride == 1) &&
-                           igemm_fast_addressable(p, spatial);
-        // 128x160 tile: the SD UNet widths 320 / 640 / 1280 are multiples of 160 (no padded columns; N = 320 at M = 32768 is
-        // one resident round).  Measured faster than the 128-wide grid whenever >= 200 tiles exist, except the
-        // short-K GEMMs whose N the 128-wide grid also divides (two-pass epilogue).
-        const int64_t nb160 = (int64_t)((p.M + 127) / 128) * (p.N / 160) * p.Z;
-        if (pp_ok && !(no_auto & (1 << 8)) && p.N % 160 == 0 && nb160 >= 200 && (p.N % 128 != 0 || ksel >= 640))
-            tile = 8;
-        else if (pp_ok && !(no_auto & (1 << 6)) && ksel >= 1024 && nb256 >= 120 && p.N * 5 >= nbn256 * 256 * 4)
-            tile = 6;
-        // Halo tile: 3x3 / stride 1 convolutions on 16-pixel-aligned images.  Measured on the MI355X against the tile chosen above
-        // (profiles/r02/halo_tile_experiments.log): 1.16-1.27x over the 128x128 loop on the N = 128 convolutions of the VAE's 512x512
-        // level, 1.03-1.13x over the 256x256 ping-pong on its 256 / 128 / 64-pixel levels, 1.39x over the 128x160 tile at 640
-        // channels; NOT where 128-column tiles pad N (N = 320: the 160-column tile wins) or with fewer than 48 units
-        // (16x16-pixel patches x 128-column tiles; measured: 1.3-1.4x over the 128x160 tile at 80 units, 1.04-1.29x at 64, equal at 32).  EDTR_IGEMM_HALO=0 switches it off.
-        static int halo = -1;
-        if (halo < 0) {
-            const char* e4 = getenv("EDTR_IGEMM_HALO");
-            halo = (e4 && e4[0] == '0') ? 0 : 1;
-        }
-        if (halo && dma_ok && (p.N & 127) == 0 && igemm_halo_ok(p, spatial) && igemm_fast_addressable(p, spatial) &&
-            (int64_t)(p.M >> 8) * (p.N >> 7) * p.splitk >= 48)      // (p.splitk was normalised to >= 1 above)
-            tile = 16;
-        // ... and where they DO pad N (N = 320 = 2.5 tiles) as long as the padded grid is at most ONE round of workgroups: the
-        // 64x64-latent convolutions at batch <= 4 (192 units), where the 128x160 tile's 256 workgroups crawl alone on their CUs.
-        // Measured (profiles/r03/halo_n320.log, one device): 37.0 / 63.1 / 88.9 us against 51.8 / 92.6 / 133.8 (K = 2880 / 5760 /
-        // 8640, batch 4: 1.40 - 1.50x), 33.1 against 48.7 at batch 2; at batch 8 (384 units = 1.5 rounds) the 128x160 tile wins by 8 %.
-        static int ragged = -1;
-        if (ragged < 0) {
-            const char* e6 = getenv("EDTR_IGEMM_HALO_RAGGED");
-            ragged = (e6 && e6[0] == '0') ? 0 : 1;
-        }
-        if (halo && ragged && dma_ok && (p.N & 127) != 0 && p.N > 128 && p.splitk <= 1 && igemm_halo_ok(p, spatial) &&
-            igemm_fast_addressable(p, spatial)) {
-            const int64_t units = (int64_t)(p.M >> 8) * ((p.N + 127) >> 7);
-            if (units >= 48 && units <= 256) tile = 16;
-        }
-        // 256x32 tile for skinny-N convolutions (the VAE decoder's 3-channel output conv: 94 % of a 128-wide tile is padding);
-        // validated against tile 3 on the MI355X (profiles/r02/ab_tiles_3_vs_14*.log).  EDTR_IGEMM_SKINNY=0 switches it off.
-        static int skinny = -1;
-        if (skinny < 0) {
-            const char* e3 = getenv("EDTR_IGEMM_SKINNY");
-            skinny = (e3 && e3[0] == '0') ? 0 : 1;
-        }
-        if (skinny && tile == 3 && p.N <= 32 && p.M >= 65536 && p.splitk <= 1 && !p.gn_partial && p.act != EDTR_ACT_GEGLU &&
-            (!p.upsample2x || p.stride == 1) && igemm_fast_addressable(p, spatial))
-            tile = 14;
-    }
-    // Halo tile with 512-pixel units (tile 17, halo512.hip): the plain 3x3 / stride-1 convolutions whose image is a multiple of
-    // 32 x 16 pixels, N a multiple of 128, no split-K / activation — wherever the 256-pixel halo tile was chosen and there are at
-    // least two rounds of 512-pixel units.  EDTR_IGEMM_HALO512=0 switches the automatic choice off (A/B on one device).
-    static int halo512 = -1;
-    if (halo512 < 0) {
-        const char* e5 = getenv("EDTR_IGEMM_HALO512");
-        halo512 = e5 ? atoi(e5) : 1;
-    }
-    const bool h512_ok = spatial && (p.C1 & 31) == 0 && edtr_halo512_ok(p) && igemm_fast_addressable(p, spatial);
-    // (whole-round rules below count the CUs of the device the launch goes to; the HIP-free edtr_igemm_plan has no device and answers
-    //  for the 256 CUs of an MI355X — ADVICE r05)
-    const int cus = dry ? 256 : edtr_cu_count();
-    if (p.tile == 0 && tile == 16 && halo512 > 0 && h512_ok && (int64_t)(p.M >> 9) * (p.N >> 7) >= (int64_t)cus * halo512) tile = 17;
-    static int halo512p = -1;
-    if (halo512p < 0) {
-        const char* e13 = getenv("EDTR_IGEMM_HALO512P");
-        halo512p = e13 ? atoi(e13) : 0;
-    }
-    if (p.tile == 0 && tile == 17 && halo512p > 0 && edtr_halo512p_ok(p) && (int64_t)(p.M >> 9) * (p.N >> 7) >= (int64_t)cus * halo512p) tile = 21;
-    // Halo tile of 160 columns (tile 20): N % 160 == 0 convolutions whose 16 x 16-pixel x 160-channel units fill whole rounds of the
-    // chip (the 64 x 64-latent ResBlock convolutions at batch 8: 256 units = one per CU), where the 128 x 160 implicit-GEMM tile would run.
-    // EDTR_IGEMM_HALO160=0 switches the automatic choice off (A/B on one device).
-    static int halo160 = -1;
-    if (halo160 < 0) {
-        const char* e10 = getenv("EDTR_IGEMM_HALO160");
-        halo160 = (e10 && e10[0] == '0') ? 0 : 1;
-    }
-    if (p.tile == 0 && tile == 8 && halo160 && spatial && edtr_halo160_ok(p) && igemm_fast_addressable(p, spatial)) {
-        const int64_t units = (int64_t)(p.M >> 8) * (p.N / 160), tail = units % cus, most = (int64_t)cus * 3 / 4;
-        if (units >= most && (tail == 0 || tail >= most)) tile = 20;       // whole rounds of one unit per CU (the last one >= 3/4 full)
-    }
-    if (p.a_gn) {           // GroupNorm (+ SiLU) of the input fused into the halo tiles' patch staging: 16 x 16 / 32 x 16-patch geometries only
-        if (p.tile == 21 || (p.tile == 0 && tile == 21)) {
-            if (!h512_ok || !edtr_halo512p_ok(p)) return EDTR_E_UNSUPPORTED;
-            tile = 21;
-        } else if (p.tile == 17 || (p.tile == 0 && tile == 17)) {
-            if (!h512_ok) return EDTR_E_UNSUPPORTED;
-            tile = 17;
-        } else {
-            if ((p.dtype != EDTR_BF16 && p.dtype != EDTR_F16) || !spatial || p.upsample2x || !dma_ok || !igemm_halo_ok(p, spatial) ||
-                igemm_halo_img8(p) || !igemm_fast_addressable(p, spatial) || (p.tile != 0 && p.tile != 16))
-                return EDTR_E_UNSUPPORTED;
-            tile = 16;
-        }
-        if (!aligned16(p.a_gn)) return EDTR_E_ALIGN;
-    }
-    if (p.out16) {
-        if (!p.out_f32 || p.Z != 1 || p.act == EDTR_ACT_GEGLU || p.vt_out) return EDTR_E_UNSUPPORTED;
-        if ((p.ld16 & 7) || !aligned16(p.out16)) return EDTR_E_ALIGN;
-    }
-    if (p.a_wrap != 0) {          // weights-exact two-part product: A[m][k mod a_wrap] against [Wh | Wl]; plain GEMMs on tiles 1 / 2 / 3 / 8
-        if (p.a_wrap < 0 || p.K != 2 * p.a_wrap || (p.a_wrap & 63) || spatial || p.taps != 1 || p.C2 || p.Z != 1 || p.ln_stats) return EDTR_E_UNSUPPORTED;
-        if (p.tile != 0 && !(p.tile == 1 || p.tile == 2 || p.tile == 3 || p.tile == 8)) return EDTR_E_UNSUPPORTED;
-        if (!(tile == 1 || tile == 2 || tile == 3 || tile == 8)) tile = 3;       // (an automatic 256x256 / ping-pong choice)
-    }
-    if (p.upsample2x == 2) {      // sub-pixel form of the upsample convolution: the halo kernel only (phase-major pre-summed weights)
-        if (p.tile != 0 && p.tile != 16) return EDTR_E_UNSUPPORTED;
-        if (!dma_ok || !igemm_halo_ok(p, spatial) || !igemm_fast_addressable(p, spatial)) return EDTR_E_UNSUPPORTED;
-        tile = 16;
-    }
-    if (p.vt_out) {     // the transposed V store needs whole column tiles of V: tiles 1 / 3 (128 columns) or 8 (160)
-        if (p.tile == 0 && !((tile == 8 && p.vt_col0 % 160 == 0) || ((tile == 1 || tile == 3) && p.vt_col0 % 128 == 0)))
-            tile = (dma_ok && p.N % 160 == 0 && p.vt_col0 % 160 == 0 && igemm_fast_addressable(p, spatial)) ? 8
-                   : (p.vt_col0 % 128 == 0 ? (dma_ok ? 3 : 1) : -1);
-        const int bn = tile == 8 ? 160 : 128;
-        if (!(tile == 1 || tile == 3 || tile == 8) || p.vt_col0 % bn != 0) return EDTR_E_UNSUPPORTED;
-    }
-    if (p.ln_stats && !(tile == 1 || tile == 3)) {
-        if (p.tile != 0) return EDTR_E_UNSUPPORTED;       // the folded LayerNorm's epilogue exists in the 128 x 128 tiles only
-        tile = dma_ok ? 3 : 1;
-        if (p.vt_out && p.vt_col0 % 128 != 0) return EDTR_E_UNSUPPORTED;
-    }
-    if (p.row_stats && !(tile == 1 || tile == 2 || tile == 3 || (tile == 8 && !(dbg_flags() & 2)))) {   // ... the row statistics: + the 64x64 tile 2 and the 128x160 tile
-        if (p.tile != 0) return EDTR_E_UNSUPPORTED;
-        tile = dma_ok ? 3 : 1;
-    }
-    if ((p.row_stats || p.vt_out) && (tile == 16 || tile == 17 || tile == 20 || tile == 21)) return EDTR_E_UNSUPPORTED;
-    if (p.act == EDTR_ACT_GEGLU && tile == 2) tile = 1;  // value/gate pairing needs two 32-column MFMA tiles per wave
-    if (tile >= 3 && !dma_ok && !((tile == 17 || tile == 20 || tile == 21) && p.C2 == 0 && (p.C1 & 31) == 0)) return EDTR_E_UNSUPPORTED;      // (tiles 17 / 20 walk 32-channel chunks)
-    if (p.a3) {             // K tail: tile 16 in its plain 16 x 16-patch and 8 x 8-image forms (no a_gn there), tiles 17 and 20
-        if (!((tile == 16 && !p.a_gn) || tile == 17 || tile == 20)) return EDTR_E_UNSUPPORTED;
-    }
-    if (p.gn_partial) {
-        const int sr = p.gn_slot_rows > 0 ? p.gn_slot_rows : 128;
-        if (p.gn_ld < 0 || (p.gn_ld > 0 && p.gn_ld < p.N)) return EDTR_E_SHAPE;
-        if (p.Z != 1 || p.act == EDTR_ACT_GEGLU) return EDTR_E_UNSUPPORTED;
-        if (p.splitk > 1) {          // the split-K reducer writes the statistics: slots of 128 rows, or of 64 (the 8 x 8 images)
-            if ((sr != 64 && sr != 128) || p.M % sr || (p.N & 31)) return EDTR_E_UNSUPPORTED;
-        } else if (tile == 2 || sr != 128 || (p.M & 127)) {
-            return EDTR_E_UNSUPPORTED;   // fused GroupNorm statistics need whole 128-row tiles of the 128x128 kernels
-        }
-    }
-    // live tiles: 1, 2 (register-staged), 3 (LDS-DMA 128x128), 6 (256x256 ping-pong), 8 (128x160), 14 (256x32), 16 (halo), 17 (halo, 512-pixel units).
-    // 4, 5, 7, 9 - 13, 15, 18 (and a round-2 "17") were experiments, measured (profiles/r01 - r03) and removed (15 = the 8-wave ping-pong 128x128 tile
-    // for small grids and 18 = the persistent halo tile were faster in isolation and neutral on the whole path: round 4 took them out)
-    if (!(tile == 1 || tile == 2 || tile == 3 || tile == 6 || tile == 8 || tile == 14 || tile == 16 || tile == 17 || tile == 20 || tile == 21)) return EDTR_E_DTYPE;
-    // lockstep breaker of the two-workgroups-per-CU kernels (stagger_second_slot): only when the grid has more than one round
-    // (>= 768 workgroups: below that the second slot's blocks are the tail anyway) and the tile is short enough for the epilogue
-    // to matter.  EDTR_IGEMM_STAGGER = percent of the estimated half life (default 100; 0 = off).
-    p.debug_flags = dbg_flags();
-    p.stagger = 0;
-    if ((tile == 3 || tile == 8) && p.splitk <= 1) {
-        static int pct = -1;
-        if (pct < 0) {
-            const char* e7 = getenv("EDTR_IGEMM_STAGGER");
-            pct = e7 ? atoi(e7) : 0;       // measured: no gain in isolation (the two workgroups of a CU are not slowed by their lockstep), off
-        }
-        const int bm = 128, bn = tile == 8 ? 160 : 128;
-        const int64_t wgs = (int64_t)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) * p.Z;
-        const int nkt = (p.K + 63) / 64;
-        if (pct > 0 && wgs >= 768 && nkt <= 48) {
-            const int life = 4000 + nkt * 1350 + (p.act == EDTR_ACT_GEGLU ? 11000 : 9000);      // cycles, from the in-kernel stamps
-            p.stagger = (int)((int64_t)life * pct / 200);
-        }
-    }
+extern "C" int edtr_igemm(const edtr_igemm_params* pp, edtr_stream_t stream) {
+    // (whole-round rules count the CUs of the device the launch goes to)
+    const igemm_plan::IgemmPlan pl = igemm_plan::plan(pp, edtr_cu_count());
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return p.dtype == EDTR_BF16 ? dispatch<BF16>(p, tile, spatial, s, dry) : dispatch<F16>(p, tile, spatial, s, dry);
+    return pl.p.dtype == EDTR_BF16 ? launch_plan<BF16>(pl, s) : launch_plan<F16>(pl, s);
 }
 
-extern "C" int edtr_igemm(const edtr_igemm_params* pp, edtr_stream_t stream) { return igemm_run(pp, stream, false); }
-
 // Which kernel would edtr_igemm run for these parameters?  Every validation and every shape rule of the launch, no launch (no HIP
-// call: usable without a GPU): > 0 = the tile number (edtr_igemm_params.tile), < 0 = the error edtr_igemm would return.
-extern "C" int edtr_igemm_plan(const edtr_igemm_params* pp) { return igemm_run(pp, nullptr, true); }
+// call: usable without a GPU): > 0 = the tile number (edtr_igemm_params.tile), < 0 = the error edtr_igemm would return.  It has no
+// device and answers for the 256 CUs of an MI355X.
+extern "C" int edtr_igemm_plan(const edtr_igemm_params* pp) { return igemm_plan::plan(pp, 256).rc; }

@@ -579,7 +579,7 @@ def make_gn_table(*, partial, tiles_per_image, sums, B, C, HW, gamma, beta, eps,
 
 
 def igemm_fast_addressable(rows_in: int, ld: int, IW: int, K: int, N: int, ldw: int) -> bool:
-    """Mirror of igemm.hip: igemm_fast_addressable — the buffer-addressed kernels (every LDS-DMA tile, the halo tiles) reach their
+    """Mirror of csrc/igemm_plan.h: igemm_fast_addressable — the buffer-addressed kernels (every LDS-DMA tile, the halo tiles) reach their
     operands through 32-bit byte offsets; edtr_igemm answers EDTR_E_UNSUPPORTED for an explicit halo request beyond that, so the
     predicates below must not promise the halo tile there (the untiled 1024 x 1024 decode at batch 8 has a 4.29-GB
     operand).  tests/test_host_logic.py checks the predicates against edtr_igemm_plan."""
