@@ -14,7 +14,9 @@ C ABI (edtr_amd.ops -> libedtr_hip.so) and compared with a plain torch CPU compu
 Most igemm outputs (GEMM, split-K, GEGLU / concat, GELU / LeakyReLU, tile orders, conv3x3, the halo tiles through _halo_case)
 also sit in NaN-filled buffers with guard rows and columns (guarded / check_guards): a store past a ragged tail fails.  The
 attention cases at the launch geometry of a batch-8 run (test_flash_attn64_launch_geometry and its neighbours) guard every operand
-and the output that way (HostileAttn) and assert edtr_flash_attn64_plan's answer before they launch."""
+and the output that way (HostileAttn) and assert edtr_flash_attn64_plan's answer before they launch.  igemm's z-batched launches
+(Z > 1 on every tile, zdiv > 1), its wide operands (the 64-bit-address form of tile 3), tile 14 against fp64 and split-K on tiles 8 /
+14 or with empty trailing splits live in tests/test_gpu_igemm_cells.py (case table: tests/igemm_cells.py), under the same two gates."""
 import math
 
 import pytest
