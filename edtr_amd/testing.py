@@ -2,9 +2,10 @@
 Nothing here touches the CPU oracle (oracle/ is imported by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline only)."""
 from __future__ import annotations
 
+import bisect
 import contextlib
 import math
-from typing import Dict, Iterable
+from typing import Dict, Iterable, Set, Tuple
 
 import torch
 
@@ -63,6 +64,70 @@ def injected_noise(noises: Iterable[torch.Tensor]):
         yield
     finally:
         torch.randn_like = orig
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Buffer discipline of a launch program (tests/test_lanes_cpu.py) and the captured forms of the engines (tests/test_gpu_graphs.py)
+# ---------------------------------------------------------------------------------------------------------------------
+def tensor_range(t: torch.Tensor) -> Tuple[int, int]:
+    """(first byte, end byte) of ``t``: from data_ptr() to its last element inclusive, sum((size - 1) * stride) + 1 elements — so
+    two interleaved column slices of one buffer overlap (deliberately conservative)."""
+    span = sum((n - 1) * s for n, s in zip(t.shape, t.stride())) + 1
+    return t.data_ptr(), t.data_ptr() + span * t.element_size()
+
+
+def rec_ranges(rec) -> Set[Tuple[int, int]]:
+    """The (first byte, end byte) ranges of every non-empty tensor reachable from ``rec.keep`` (tuples and lists nest:
+    ops.make_swin_layer keeps ``(attn.keep, mlp.keep)``; parameter structs, scalars and None are passed over)."""
+    out: Set[Tuple[int, int]] = set()
+    todo = [rec.keep]
+    while todo:
+        v = todo.pop()
+        if isinstance(v, torch.Tensor):
+            if v.numel():
+                out.add(tensor_range(v))
+        elif isinstance(v, (tuple, list)):
+            todo.extend(v)
+    return out
+
+
+def ranges_overlap(A, B) -> Set[Tuple[int, int]]:
+    """The members of ``A`` that intersect any member of ``B`` (half-open byte ranges).  B sorted by first byte with a running
+    maximum of the end bytes: a range of A is hit iff one of the B ranges that begin before its end reaches past its start."""
+    b = sorted(B)
+    starts = [s for s, _ in b]
+    reach, hi = [], 0
+    for _, e in b:
+        hi = max(hi, e)
+        reach.append(hi)
+    out = set()
+    for s, e in A:
+        n = bisect.bisect_left(starts, e)          # the B ranges with first byte < e
+        if n and reach[n - 1] > s:
+            out.add((s, e))
+    return out
+
+
+def capture_engines(cldm: ControlLDM, parallel_lanes: bool = True) -> None:
+    """What bench.py's capture_all() does: every cached engine program that is not a hipGraph yet becomes one (the denoise step
+    with its two lanes as two graph branches unless ``parallel_lanes`` is False; the context programs stay launch lists)."""
+    for e in cldm._cldm_engines.values():
+        if e.step_prog.graph is None:
+            e.step_prog.capture(parallel_lanes=parallel_lanes)
+    for e in cldm._vae_engines.values():
+        if e.prog.graph is None:
+            e.prog.capture()
+
+
+def release_graphs(cldm: ControlLDM) -> None:
+    """Back to eager replay: drop the hipGraph of every cached engine (the engines, their buffers and programs stay)."""
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()                   # a replay of one of these graphs may still be queued
+    for e in cldm._cldm_engines.values():
+        e.step_prog.release_graph()
+        e.ctx_prog.release_graph()
+    for e in cldm._vae_engines.values():
+        e.prog.release_graph()
 
 
 def rel_err(a, b) -> float:

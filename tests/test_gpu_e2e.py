@@ -5,7 +5,12 @@ the REFERENCE produced on CPU fp32 (tests/golden/tiny_pipeline*.npz) with identi
 Stated tolerances, relative L2 error vs the fp32 reference (16-bit activations, fp32 accumulation; four denoise
 steps through 2 x 25 residual blocks and 23 transformer blocks each):
     fp16 storage: eps per step 4e-3, final latent 4e-3, decoded image 6e-3
-    bf16 storage: eps per step 3e-2, final latent 3e-2, decoded image 4e-2"""
+    bf16 storage: eps per step 3e-2, final latent 3e-2, decoded image 4e-2
+
+Every CLDM / VAE test here replays the engines' launch lists eagerly, in list order, on one stream, in slot 0.  The forms the
+benchmark times — the programs as hipGraphs, the denoise step's two lanes as parallel graph branches, two engine slots in
+flight — are held bit for bit against this eager replay in tests/test_gpu_graphs.py; the buffer rules that make them safe
+(what the lanes and the slots may share) are checked on the host in tests/test_lanes_cpu.py."""
 import os
 
 import numpy as np
