@@ -21,6 +21,12 @@
  *     offsets are multiples of 8 elements.
  *   - return value: 0 = success; negative = EDTR_E* argument error (nothing was launched);
  *     positive = hipError_t from the launch.  Never throws, never exits.
+ *
+ * The Python binding is READ from this file at import (edtr_amd/header.py: structs, constants, prototypes), so the file keeps
+ * to a narrow dialect and the reader refuses anything else: block comments only; `#define EDTR_NAME <integers, parentheses, <<>`;
+ * enums with explicit values; `typedef struct edtr_x { ... } edtr_x;` of int / int32_t / int64_t / uint64_t / float and pointer
+ * fields (no arrays, no nested structs); prototypes of such scalars, edtr_stream_t and pointers (no callbacks).  A struct array
+ * that is passed twice is named `x_host` (the host reads it), then `x` (its device copy).
  */
 #ifndef EDTR_HIP_H
 #define EDTR_HIP_H

@@ -23,11 +23,11 @@ def _default_switches():
 
 
 def test_ids_match_the_header():
-    from edtr_amd import ops
-    text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "edtr_hip.h")).read()
+    from edtr_amd import lib, ops
     for name, value in (("GENERIC", GENERIC), ("SPLIT_QK", SPLIT_QK), ("SPLIT_QKPV", SPLIT_QKPV), ("SMALLK", SMALLK), ("V3", V3)):
-        assert f"EDTR_ATTN_{name} = {value}" in text
+        assert getattr(lib, f"ATTN_{name}") == value            # enum edtr_attn_kernel, as the binding reads it from the header
         assert getattr(ops, f"ATTN_{name}") == value
+    assert (lib.E_NULL, lib.E_SHAPE, lib.E_ALIGN, lib.E_DTYPE, lib.E_UNSUPPORTED) == (E_NULL, E_SHAPE, E_ALIGN, E_DTYPE, E_UNSUPPORTED)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

@@ -142,14 +142,13 @@ def test_reference_argument_errors():
 def test_entry_point_is_declared_listed_and_bound():
     from edtr_amd import build, lib
     text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "edtr_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(edtr_[a-z0-9_]+)\s*\(", text))
-    assert "edtr_seg_confusion_coarse" in declared and "edtr_seg_confusion_coarse" in lib.DECLARED_SYMBOLS
+    assert "edtr_seg_confusion_coarse" in lib.DECLARED_SYMBOLS
     assert re.search(r"int edtr_seg_confusion_coarse\(int logits_dtype, const void\* coarse, int B, int n, int ih, int iw,\s*const uint8_t\* target, "
                      r"int H, int W,\s*const int32_t\* sizes_host, const int32_t\* sizes, int64_t\* mat, uint8_t\* pred, int max_blocks,\s*"
                      r"edtr_stream_t stream\);", text)
     build.build_library()
     handle = lib.load()
-    assert handle.edtr_abi_version() == 10 and hasattr(handle, "edtr_seg_confusion_coarse")
+    assert handle.edtr_abi_version() == lib.ABI_VERSION == 10 and hasattr(handle, "edtr_seg_confusion_coarse")
 
 
 def test_entry_point_rejects_bad_arguments_in_the_order_of_edtr_seg_confusion():

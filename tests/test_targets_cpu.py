@@ -260,19 +260,14 @@ SYMBOLS = ("edtr_targets_match", "edtr_targets_encode", "edtr_targets_sample", "
 
 def test_the_new_symbols_are_declared_bound_exported_and_the_abi_is_still_10():
     from edtr_amd import build, lib
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "edtr_hip.h")).read(), flags=re.S)
-    declared = re.findall(r"\b(edtr_[a-z0-9_]+)\s*\(", text)
-    assert all(s in declared and s in lib.DECLARED_SYMBOLS for s in SYMBOLS)
-    assert re.search(r"#define EDTR_ABI_VERSION 10\b", text)
+    assert all(s in lib.DECLARED_SYMBOLS for s in SYMBOLS)
+    assert lib.ABI_VERSION == 10
     assert "targets.hip" in build.GLUE_SOURCES and "targets.hip" not in build.SOURCES
     deps = [os.path.basename(d) for d in build.object_deps("targets.hip")]
     assert "glue.h" in deps and "philox.h" in deps
-    raw = open(os.path.join(ROOT, "include", "edtr_hip.h")).read()
-    caps = tuple(int(re.search(rf"#define EDTR_TARGETS_{n} (\d+)\b", raw).group(1)) for n in ("MAX_GT", "MAX_BATCH", "TILE", "RPN", "ROI"))
-    assert caps == (lib.TARGETS_MAX_GT, lib.TARGETS_MAX_BATCH, lib.TARGETS_TILE, lib.TARGETS_RPN, lib.TARGETS_ROI)
+    caps = (lib.TARGETS_MAX_GT, lib.TARGETS_MAX_BATCH, lib.TARGETS_TILE, lib.TARGETS_RPN, lib.TARGETS_ROI)
     assert caps == (targets.MAX_GT, targets.MAX_BATCH, targets.TILE, targets.FORM_RPN, targets.FORM_ROI)
-    purposes = tuple(int(re.search(rf"#define EDTR_NOISE_SAMPLE_{n} (\d+)\b", raw).group(1)) for n in ("RPN", "ROI"))
-    assert purposes == rng.SAMPLE_PURPOSES
+    assert (lib.NOISE_SAMPLE_RPN, lib.NOISE_SAMPLE_ROI) == rng.SAMPLE_PURPOSES
     build.build_library()
     handle = lib.load()
     assert handle.edtr_abi_version() == 10 and all(hasattr(handle, s) for s in SYMBOLS)

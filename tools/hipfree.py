@@ -19,7 +19,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
-from edtr_amd import lib as L  # noqa: E402  (struct definitions only; L.load() would import torch and is not used here)
+from edtr_amd import lib as L  # noqa: E402  (structs, constants and bind(); L.load() would import torch and is not used here)
 
 DRY = os.environ.get("HIPFREE_DRY") == "1"
 vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -36,15 +36,7 @@ hip.hipEventCreate.argtypes = [C.POINTER(vp)]
 hip.hipEventRecord.argtypes = [vp, vp]
 hip.hipEventSynchronize.argtypes = [vp]
 hip.hipEventElapsedTime.argtypes = [C.POINTER(f32), vp, vp]
-edtr.edtr_error_string.restype = C.c_char_p
-edtr.edtr_igemm.argtypes = [C.POINTER(L.IgemmParams), vp]
-edtr.edtr_flash_attn64.argtypes = [C.POINTER(L.AttnParams), vp]
-edtr.edtr_window_attn.argtypes = [C.POINTER(L.WindowAttnParams), vp]
-edtr.edtr_gn_stats.argtypes = [C.POINTER(L.GnParams), vp]
-edtr.edtr_gn_apply.argtypes = [C.POINTER(L.GnParams), vp]
-edtr.edtr_layernorm.argtypes = [i32, vp, i64, i32, i32, i32, vp, vp, f32, vp, i32, vp]
-edtr.edtr_pixel_unshuffle.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, f32, vp, i32, i32, vp]
-edtr.edtr_zero_bytes.argtypes = [vp, i64, vp]
+L.bind(edtr, [n for n in L.DECLARED_SYMBOLS if hasattr(edtr, n)])      # prototypes from include/edtr_hip.h; a variant build may hold a subset
 
 
 def chk(code: int, what: str = "") -> None:
