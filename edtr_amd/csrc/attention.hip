@@ -16,6 +16,7 @@
 // raised when it grows by more than 2^8 (deferred rescale: O and l are rescaled on <1 % of the tiles).
 #include <stdlib.h>
 #include "common.h"
+#include "wave_prims.h"
 
 namespace {
 
@@ -23,28 +24,6 @@ constexpr int kThreads = 256;
 constexpr int KV = 64;            // keys per tile
 constexpr int TILE_BYTES = 64 * 64 * 2;
 constexpr float kDeferLog2 = 8.0f;   // P <= 2^8 before a rescale is forced (exact in bf16/fp16: only the exponent grows)
-
-constexpr uint32_t kOob = 0xFFFFFF00u;
-
-__device__ __forceinline__ int swap23(int i) { return (i & ~12) | ((i & 4) << 1) | ((i & 8) >> 1); }
-
-__device__ __forceinline__ u32x4 srd_of(const void* base) {
-    const uint64_t b = reinterpret_cast<uint64_t>(base);
-    u32x4 srd;
-    srd.x = __builtin_amdgcn_readfirstlane((uint32_t)b);
-    srd.y = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32) & 0xffffu);
-    srd.z = 0xFFFFFF00u;
-    srd.w = 0x00020000u;
-    return srd;
-}
-
-__device__ __forceinline__ void dma16(uint32_t voff, const u32x4& srd, uint32_t soff, uint32_t lds_addr) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(srd), "s"(lds_addr), "s"(soff)
-                 : "memory");
-}
 
 // ---- coalesced store of a wave's O tile [32 queries][64 channels] (round 4) ------------------------------------------------
 // The accumulator layout of O^T = V^T P^T gives lane (query l31, half lh) the channels db*32 + 8g + 4*lh + (0..3): written straight
@@ -69,7 +48,7 @@ __device__ __forceinline__ void store_o_tile(char* slab, const ACC& o0, const AC
         v.y = pack2<T>(o1[4 * g + 2] * inv, o1[4 * g + 3] * inv);
         *reinterpret_cast<uint2*>(slab + l31 * OPITCH + (32 + 8 * g + 4 * lh) * 2) = v;
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // same wave: the LDS queue keeps the order, the compiler must too
+    wait_lds();        // same wave: the LDS queue keeps the order, the compiler must too
     const int r8 = lane >> 3, ch = lane & 7;
 #pragma unroll
     for (int ps = 0; ps < 4; ++ps) {
@@ -77,7 +56,7 @@ __device__ __forceinline__ void store_o_tile(char* slab, const ACC& o0, const AC
         const U4 v = *reinterpret_cast<const U4*>(slab + row * OPITCH + ch * 16);
         if (q0 + row < Nq) stg16(out_rows + (int64_t)row * o_ld + ch * 8, v);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // the slab may be rewritten by this wave's next tile
+    wait_lds();        // the slab may be rewritten by this wave's next tile
 }
 
 template <typename T>
@@ -117,8 +96,8 @@ __global__ void __launch_bounds__(kThreads, 2) flash_attn64_kernel(const edtr_at
     }
 
     // ---- tile staging by LDS-DMA: one instruction = 8 tile rows of 128 bytes; a wave owns rows wave*16 + 8j + (lane>>3)
-    const u32x4 srd_k = srd_of(kp), srd_v = srd_of(vp);
-    const uint32_t smem_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)((const __attribute__((address_space(3))) char*)smem));
+    const u32x4 srd_k = make_srd(kp), srd_v = make_srd(vp);
+    const uint32_t smem_base = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
     const int rsub = lane >> 3, slot = lane & 7;
     uint32_t koff[2], voff[2];     // constant per-lane byte offsets (tile 0); a tile step only moves the scalar offset
     int vkey[2], krow[2];
@@ -138,8 +117,8 @@ __global__ void __launch_bounds__(kThreads, 2) flash_attn64_kernel(const edtr_at
         const uint32_t soff_k = (uint32_t)kv0 * (uint32_t)p.k_ld * 2u, soff_v = (uint32_t)kv0 * 2u;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            dma16(kv0 + krow[j] < p.Nk ? koff[j] : kOob, srd_k, soff_k, sk + j * 1024);
-            dma16(kv0 + vkey[j] < p.Nk ? voff[j] : kOob, srd_v, soff_v, sv + j * 1024);
+            dma16_buf_keep_m0(kv0 + krow[j] < p.Nk ? koff[j] : kOobOffset, srd_k, soff_k, sk + j * 1024);
+            dma16_buf_keep_m0(kv0 + vkey[j] < p.Nk ? voff[j] : kOobOffset, srd_v, soff_v, sv + j * 1024);
         }
     };
 
@@ -158,9 +137,9 @@ __global__ void __launch_bounds__(kThreads, 2) flash_attn64_kernel(const edtr_at
         const int cur = t & 1;
         if (t + 1 < nt) {
             issue_tile(t + 1, cur ^ 1);
-            asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // this wave's 4 DMAs of tile t have landed
+            wait_vm<4>();   // this wave's 4 DMAs of tile t have landed
         } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
         }
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
@@ -241,9 +220,7 @@ __global__ void __launch_bounds__(kThreads, 2) flash_attn64_kernel(const edtr_at
                     const U4 vf = *reinterpret_cast<const U4*>(sv + tile_off(db * 32 + l31, kb * 4 + 2 * st + lh));
                     o[db] = T::mfma(vf, pf[kb][st], o[db]);
                 }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();      // buffer `cur` is refilled by the next iteration's DMA
-        asm volatile("" ::: "memory");
+        block_sync();                      // buffer `cur` is refilled by the next iteration's DMA
     }
 
     // ---- normalise and store: lane (q, half) holds d = db*32 + 8g + 4*half + (0..3) in regs 4g..4g+3; the tile goes through a
@@ -291,10 +268,10 @@ __global__ void __launch_bounds__(kThreads, 1) flash_attn64_split_kernel(const e
             ql[ks] = ldg16(qpl + (int64_t)q_row * p.q_ld + ks * 16 + lh * 8);
         }
     }
-    const u32x4 srd_kh = srd_of(static_cast<const uint16_t*>(p.k) + ko), srd_kl = srd_of(static_cast<const uint16_t*>(p.k_lo) + ko);
-    const u32x4 srd_vh = srd_of(static_cast<const uint16_t*>(p.vt) + vo);
-    const u32x4 srd_vl = srd_of(static_cast<const uint16_t*>(PV ? p.vt_lo : p.vt) + vo);
-    const uint32_t smem_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)((const __attribute__((address_space(3))) char*)smem));
+    const u32x4 srd_kh = make_srd(static_cast<const uint16_t*>(p.k) + ko), srd_kl = make_srd(static_cast<const uint16_t*>(p.k_lo) + ko);
+    const u32x4 srd_vh = make_srd(static_cast<const uint16_t*>(p.vt) + vo);
+    const u32x4 srd_vl = make_srd(static_cast<const uint16_t*>(PV ? p.vt_lo : p.vt) + vo);
+    const uint32_t smem_base = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
     const int rsub = lane >> 3, slot = lane & 7;
     uint32_t koff[2], voff[2];
     int vkey[2], krow[2];
@@ -313,11 +290,11 @@ __global__ void __launch_bounds__(kThreads, 1) flash_attn64_split_kernel(const e
         const uint32_t soff_k = (uint32_t)kv0 * (uint32_t)p.k_ld * 2u, soff_v = (uint32_t)kv0 * 2u;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const uint32_t ko_ = kv0 + krow[j] < p.Nk ? koff[j] : kOob, vo_ = kv0 + vkey[j] < p.Nk ? voff[j] : kOob;
-            dma16(ko_, srd_kh, soff_k, s0 + j * 1024);
-            dma16(ko_, srd_kl, soff_k, s0 + TILE_BYTES + j * 1024);
-            dma16(vo_, srd_vh, soff_v, s0 + 2 * TILE_BYTES + j * 1024);
-            if constexpr (PV) dma16(vo_, srd_vl, soff_v, s0 + 3 * TILE_BYTES + j * 1024);
+            const uint32_t ko_ = kv0 + krow[j] < p.Nk ? koff[j] : kOobOffset, vo_ = kv0 + vkey[j] < p.Nk ? voff[j] : kOobOffset;
+            dma16_buf_keep_m0(ko_, srd_kh, soff_k, s0 + j * 1024);
+            dma16_buf_keep_m0(ko_, srd_kl, soff_k, s0 + TILE_BYTES + j * 1024);
+            dma16_buf_keep_m0(vo_, srd_vh, soff_v, s0 + 2 * TILE_BYTES + j * 1024);
+            if constexpr (PV) dma16_buf_keep_m0(vo_, srd_vl, soff_v, s0 + 3 * TILE_BYTES + j * 1024);
         }
     };
 
@@ -335,10 +312,10 @@ __global__ void __launch_bounds__(kThreads, 1) flash_attn64_split_kernel(const e
         const int cur = t & 1;
         if (t + 1 < nt) {
             issue_tile(t + 1, cur ^ 1);
-            if constexpr (PV) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            if constexpr (PV) wait_vm<8>();
+            else wait_vm<6>();
         } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
         }
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
@@ -431,9 +408,7 @@ __global__ void __launch_bounds__(kThreads, 1) flash_attn64_split_kernel(const e
                     }
                     o[db] = T::mfma(vfh, pfh[kb][st], o[db]);
                 }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        block_sync();
     }
 
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
@@ -500,8 +475,8 @@ __global__ void __launch_bounds__(kThreads, 2) flash_attn64_smallk_kernel(const 
     // ---- K / V^T of this (image, head): both key tiles at once (keys >= Nk fail the range check and land as zeros)
     const int nt = (p.Nk + KV - 1) / KV;                                  // 1 or 2
     {
-        const u32x4 srd_k = srd_of(kp), srd_v = srd_of(vp);
-        const uint32_t smem_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)((const __attribute__((address_space(3))) char*)smem));
+        const u32x4 srd_k = make_srd(kp), srd_v = make_srd(vp);
+        const uint32_t smem_base = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
         const int rsub = lane >> 3, slot = lane & 7;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
@@ -513,8 +488,8 @@ __global__ void __launch_bounds__(kThreads, 2) flash_attn64_smallk_kernel(const 
                     const int row = wave * 16 + 8 * j + rsub, chunk = slot ^ ((row >> 1) & 7);
                     const uint32_t koff = (uint32_t)(((int64_t)(kv0 + row) * p.k_ld + chunk * 8) * 2);
                     const uint32_t voff = (uint32_t)(((int64_t)row * p.vt_ld + kv0 + chunk * 8) * 2);
-                    dma16(kv0 + row < p.Nk ? koff : kOob, srd_k, 0u, sk + j * 1024);
-                    dma16(kv0 + chunk * 8 < p.Nk ? voff : kOob, srd_v, 0u, sv + j * 1024);
+                    dma16_buf_keep_m0(kv0 + row < p.Nk ? koff : kOobOffset, srd_k, 0u, sk + j * 1024);
+                    dma16_buf_keep_m0(kv0 + chunk * 8 < p.Nk ? voff : kOobOffset, srd_v, 0u, sv + j * 1024);
                 }
             }
         }
@@ -536,15 +511,15 @@ __global__ void __launch_bounds__(kThreads, 2) flash_attn64_smallk_kernel(const 
     auto to_fragments = [&](const U4 (&qr)[4], U4 (&qf)[4]) {
 #pragma unroll
         for (int ps = 0; ps < 4; ++ps) *reinterpret_cast<U4*>(slab + (ps * 8 + r8) * OPITCH + ch8 * 16) = qr[ps];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lds();
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const U4*>(slab + l31 * OPITCH + (2 * ks + lh) * 16);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lds();
     };
     U4 qf[4], qn[4];
     int blk = blk0 + wave;
     load_q(blk, qn);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 
@@ -690,8 +665,8 @@ __global__ void __launch_bounds__(kThreads, 1) flash_attn64_v3_kernel(const edtr
         if (q_rowA < p.Nq) qA[ks] = ldg16(qp + (int64_t)q_rowA * p.q_ld + ks * 16 + lh * 8);
         if (q_rowB < p.Nq) qB[ks] = ldg16(qp + (int64_t)q_rowB * p.q_ld + ks * 16 + lh * 8);
     }
-    const u32x4 srd_k = srd_of(kp), srd_v = srd_of(vp);
-    const uint32_t smem_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)((const __attribute__((address_space(3))) char*)smem));
+    const u32x4 srd_k = make_srd(kp), srd_v = make_srd(vp);
+    const uint32_t smem_base = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
     const uint32_t ldsb = smem_base + (uint32_t)wave * (16 * 128);
     const uint32_t stepk = (uint32_t)KV * (uint32_t)p.k_ld * 2u;
     const int nt = p.Nk / KV;

@@ -22,33 +22,9 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
+#include "wave_prims.h"
 
 namespace {
-
-constexpr uint32_t kOob = 0xFFFFFF00u;
-
-__device__ __forceinline__ u32x4 srd_of(const void* base) {
-    const uint64_t b = reinterpret_cast<uint64_t>(base);
-    u32x4 srd;
-    srd.x = __builtin_amdgcn_readfirstlane((uint32_t)b);
-    srd.y = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32) & 0xffffu);
-    srd.z = 0xFFFFFF00u;
-    srd.w = 0x00020000u;
-    return srd;
-}
-
-__device__ __forceinline__ void dma(uint32_t voff, const u32x4& srd, uint32_t soff, uint32_t lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds"
-                 :
-                 : "v"(voff), "s"(srd), "s"(lds_addr), "s"(soff)
-                 : "memory");
-}
-
-// 2-bit XOR key of a 64-byte LDS row by row index mod 8 (halo512.hip: conflict-free ds_read_b128 of 16 consecutive 64-byte rows)
-__device__ __forceinline__ int key8(int x) {
-    constexpr uint32_t kKey = 3u | (3u << 2) | (0u << 4) | (1u << 6) | (0u << 8) | (1u << 10) | (3u << 12) | (2u << 14);
-    return (int)((kKey >> (2 * (x & 7))) & 3u);
-}
 
 constexpr int BQ = 128, TK = 32, D = 512;
 constexpr int KTILE = TK * D * 2, VTILE = D * TK * 2;      // 32 KiB each
@@ -72,7 +48,7 @@ __global__ void __launch_bounds__(512, 1) flash_attn512_kernel(const edtr_attn_p
     const uint32_t smem_base = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
     const uint16_t* kp = static_cast<const uint16_t*>(p.k) + (int64_t)b * p.k_bs;
     const uint16_t* vp = static_cast<const uint16_t*>(p.vt) + (int64_t)b * p.vt_bs;
-    const u32x4 srd_k = srd_of(kp), srd_v = srd_of(vp);
+    const u32x4 srd_k = make_srd(kp), srd_v = make_srd(vp);
 
     // ---- staging geometry.  K piece = one LDS row L = wave + 8 j (1 KiB = one key, 64 chunks of 16 B): L = 16 kb + r holds key
     // 8 (r >> 2) + 4 kb + (r & 3) of the tile; LDS chunk i holds the key's chunk i ^ (L & 15).  V^T piece = 16 LDS rows of 64 B:
@@ -96,8 +72,8 @@ __global__ void __launch_bounds__(512, 1) flash_attn512_kernel(const edtr_attn_p
     auto stage_piece = [&](int t, int buf, int j8) {
         const uint32_t sk = (uint32_t)(t * TK) * (uint32_t)p.k_ld * 2u, sv = (uint32_t)(t * TK * 2);
         const int j = j8 & 3;
-        if (j8 < 4) dma(voff_k[j & 1], srd_k, sk + (uint32_t)((j >> 1) * 4 * p.k_ld * 2), smem_base + K_BASE + buf * KTILE + (wave + 8 * (j & 1) + 16 * (j >> 1)) * 1024);
-        else dma(voff_v, srd_v, sv + (uint32_t)(128 * j) * (uint32_t)p.vt_ld * 2u, smem_base + V_BASE + buf * VTILE + (wave + 8 * j) * 1024);
+        if (j8 < 4) dma16_buf(voff_k[j & 1], srd_k, sk + (uint32_t)((j >> 1) * 4 * p.k_ld * 2), smem_base + K_BASE + buf * KTILE + (wave + 8 * (j & 1) + 16 * (j >> 1)) * 1024);
+        else dma16_buf(voff_v, srd_v, sv + (uint32_t)(128 * j) * (uint32_t)p.vt_ld * 2u, smem_base + V_BASE + buf * VTILE + (wave + 8 * j) * 1024);
     };
     auto stage = [&](int t, int buf) {
 #pragma unroll
@@ -133,7 +109,7 @@ __global__ void __launch_bounds__(512, 1) flash_attn512_kernel(const edtr_attn_p
 
     auto tile = [&](int t, auto BUFc) {
         constexpr int BUF = decltype(BUFc)::value;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
         __builtin_amdgcn_s_barrier();                       // tile t landed for every wave; every wave is past tile t - 1
         const bool more = t + 1 < NT;                       // tile t + 1's eight pieces are requested one per MFMA group of the S phase below: up
                                                             // front they cost ~500 cycles of DMA issue with no MFMA of any wave beside them
@@ -169,7 +145,7 @@ __global__ void __launch_bounds__(512, 1) flash_attn512_kernel(const edtr_attn_p
         m_run = m_new;
         *reinterpret_cast<U4*>(smem + p_wr) = pack8<T>(sv);
         if (lq == 0) *reinterpret_cast<float*>(smem + A_BASE + (16 * wave + l15) * 4) = alpha;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lds();
         __builtin_amdgcn_s_barrier();                       // P and the rescale factors of all 128 queries are visible
         // ---- O^T (this wave's 64 channels x 128 queries) += V^T P^T
         bool any = false;
@@ -212,7 +188,7 @@ __global__ void __launch_bounds__(512, 1) flash_attn512_kernel(const edtr_attn_p
     l_run += __shfl_xor(l_run, 32, 64);
     __builtin_amdgcn_s_barrier();                           // every wave is past its last read of the rescale factors
     if (lqe == 0) *reinterpret_cast<float*>(smem + A_BASE + (16 * wave + l15e) * 4) = 1.0f / l_run;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lds();
     __builtin_amdgcn_s_barrier();
 #pragma unroll
     for (int qb = 0; qb < 8; ++qb) {

@@ -168,49 +168,6 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
-// Byte offset of 16-byte chunk `c` of row `r` in a [rows][64 x 16-bit] LDS tile (128-byte rows).
-// XOR swizzle so that the 16 lanes of every ds_read_b128 lane group (rows r..r+15 pattern of the
-// MFMA operand read, chunk fixed) hit 16 distinct 16-byte bank slots of the 256-byte bank row.
-__device__ __forceinline__ int tile_off(int r, int c) { return r * 128 + ((c ^ ((r >> 1) & 7)) << 4); }
-
-// One global_load_lds_dwordx4: lane i's 16 bytes land at LDS byte address lds_addr + 16*i (lds_addr wave-uniform, in
-// M0).  Inline asm on purpose: hipcc neither counts it in its own vmcnt bookkeeping nor serialises later ds_reads
-// behind it with a vmcnt(0), so the prefetch can stay in flight across the barrier; completion is waited for by
-// the hand-placed counted s_waitcnt in the main loop.
-__device__ __forceinline__ void dma16(const void* gsrc, uint32_t lds_addr) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(lds_addr)
-                 : "memory");
-}
-
-__device__ __forceinline__ uint32_t lds_addr_of(const char* p) {
-    return (uint32_t)(uintptr_t)((const __attribute__((address_space(3))) char*)p);
-}
-
-// Buffer-addressed LDS-DMA: address = SRD base + voff (per lane) + soff (wave uniform); lanes whose voff fails the
-// descriptor's range check write zeros.
-constexpr uint32_t kOobOffset = 0xFFFFFF00u;     // >= num_records - 15 -> always out of range
-constexpr uint32_t kNumRecords = 0xFFFFFF00u;
-
-__device__ __forceinline__ u32x4 make_srd(const void* base) {
-    const uint64_t b = reinterpret_cast<uint64_t>(base);
-    u32x4 srd;
-    srd.x = __builtin_amdgcn_readfirstlane((uint32_t)b);
-    srd.y = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32) & 0xffffu);   // stride 0 (raw buffer)
-    srd.z = kNumRecords;
-    srd.w = 0x00020000u;
-    return srd;
-}
-
-__device__ __forceinline__ void dma16_buf(uint32_t voff, const u32x4& srd, uint32_t soff, uint32_t lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds"
-                 :
-                 : "v"(voff), "s"(srd), "s"(lds_addr), "s"(soff)
-                 : "memory");   // M0 is free here: hipcc keeps no value in it across statements on gfx950
-}
-
 // slot stride (in channels) of edtr_igemm's fused GroupNorm partials: N, or the caller's wider buffer (gn_ld: the two halves of a
 // concatenation share one buffer of slots)
 __device__ __forceinline__ int gn_ld_of(const edtr_igemm_params& p) { return p.gn_ld > 0 ? p.gn_ld : p.N; }

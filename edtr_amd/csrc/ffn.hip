@@ -16,7 +16,7 @@
 // Eight waves: wave (t, h) owns tokens 32 t .. 32 t + 31; in the first product it computes hidden half h of the chunk (32 gated
 // units = a 32-row value tile and its gate tile: one lane holds a value and its gate), in the second product output half h (160
 // columns = five 32 x 32 accumulators).  The two waves of a token tile swap their G fragments through 2 KiB of LDS per chunk.
-// LDS holds only weights: 15 granules of 8 KiB (64 rows x 64 k, the XOR-swizzled tile of common.h) per 64-unit chunk — ten of
+// LDS holds only weights: 15 granules of 8 KiB (64 rows x 64 k, the XOR-swizzled tile of wave_prims.h) per 64-unit chunk — ten of
 // W1 (k-tile kt, half h) and five of W2 (64 output rows each) — every granule type has a FIXED slot, refilled by LDS-DMA for the
 // next chunk as soon as the step that read it is over (one dma per wave and granule: the counted vmcnt waits are uniform).
 //
@@ -28,6 +28,7 @@
 // A step waits for the pieces it reads by counting what was issued AFTER them (loads complete in order):  kt = 0: vmcnt(8);
 // kt = 1 .. 4: vmcnt(12);  B: vmcnt(9);  in the last chunk, where nothing is refilled: 8, 11, 9, 7, 5, 0.
 #include "common.h"
+#include "wave_prims.h"
 
 namespace {
 
@@ -49,29 +50,6 @@ constexpr int CST = 2 * 2 * 256;
 constexpr int FLDS = CST_OFF + CST;        // 156672 bytes
 constexpr int OPITCH = 656;                // output tile row pitch in bytes (640 + 16: the 8-byte column writes of 32 rows spread over the banks)
 static_assert(FLDS <= 160 * 1024 && FBM * OPITCH <= RING, "LDS budget");
-
-// one buffer_load_dword ... lds: lane i's 4 bytes land at lds_addr + 4 i (buffer-addressed like dma16_buf: one 32-bit offset per lane,
-// the chunk moves the scalar offset — no 64-bit pointer to carry through the loop)
-__device__ __forceinline__ void dma4_buf(uint32_t voff, const u32x4& srd, uint32_t soff, uint32_t lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dword %0, %1, %3 offen lds"
-                 :
-                 : "v"(voff), "s"(srd), "s"(lds_addr), "s"(soff)
-                 : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-#ifdef FFN_DRAIN        // diagnostic build (tools/exp/ffn_debug.py): every counted wait drains the queue
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-#endif
-}
-__device__ __forceinline__ void block_sync() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 // gelu from x / 2 over eight values as four PACKED fp32 pairs (v_pk_fma_f32 / v_pk_mul_f32: two values per instruction and lane): the
 // GEGLU of a chunk is ~250 vector instructions per wave between two runs of MFMAs, with both waves of a SIMD in it at the same time —

@@ -27,6 +27,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
+#include "wave_prims.h"
 #include "igemm_plan.h"
 
 // Diagnostic build only (tools/exp/halo512_stamps.py compiles with -DEDTR_STAMPS): thread 0 of every workgroup stores s_memtime at
@@ -46,26 +47,6 @@
 
 namespace {
 
-constexpr uint32_t kOob = 0xFFFFFF00u;     // >= num_records - 15: the buffer range check turns the lane's 16 bytes into zeros
-
-__device__ __forceinline__ u32x4 srd_of(const void* base) {
-    const uint64_t b = reinterpret_cast<uint64_t>(base);
-    u32x4 srd;
-    srd.x = __builtin_amdgcn_readfirstlane((uint32_t)b);
-    srd.y = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32) & 0xffffu);   // stride 0 (raw buffer)
-    srd.z = 0xFFFFFF00u;
-    srd.w = 0x00020000u;
-    return srd;
-}
-
-// buffer-addressed LDS-DMA: lane i's 16 bytes (SRD base + voff + soff) land at LDS byte lds_addr + 16 i
-__device__ __forceinline__ void dma(uint32_t voff, const u32x4& srd, uint32_t soff, uint32_t lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds"
-                 :
-                 : "v"(voff), "s"(srd), "s"(lds_addr), "s"(soff)
-                 : "memory");
-}
-
 template <int V> using IC = std::integral_constant<int, V>;
 
 using igemm_plan::CK;                           // channels per chunk = K of one 16x16x32 MFMA
@@ -78,30 +59,6 @@ constexpr int W_BASE = 2 * PATCHB;
 constexpr int TBL = W_BASE + 3 * WTAP;          // two 1-KiB slots for the (scale, shift) rows of a chunk (a_gn)
 constexpr int RED = 128 * 1024;                 // epilogue: [0, 128 KiB) = the unit's 16-bit residual (16 KiB per wave), then the GroupNorm partial sums
 constexpr int LDS_BYTES = RED + 4096;
-}
-
-// 2-bit XOR key of a 64-byte LDS row (a patch pixel or a weight row), by row index mod 8: {3, 3, 0, 1, 0, 1, 3, 2}
-__device__ __forceinline__ int key8(int x) {
-    constexpr uint32_t kKey = 3u | (3u << 2) | (0u << 4) | (1u << 6) | (0u << 8) | (1u << 10) | (3u << 12) | (2u << 14);
-    return (int)((kKey >> (2 * (x & 7))) & 3u);
-}
-
-// sum over the 16 lanes of a DPP row (lanes that share lane >> 4), result in every lane: four v_add_f32 with DPP operands
-// (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror) instead of four ds_bpermute round trips
-__device__ __forceinline__ float row16_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
-    return v;
-}
-
-template <int N> __device__ __forceinline__ void wait_vm() {
-    if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else static_assert(N >= 1 && N <= 4, "wait_vm");
 }
 
 // ---- epilogue of the halo kernels of this file, straight from the accumulators (no LDS staging).  NW = waves per workgroup
@@ -183,13 +140,13 @@ __device__ __forceinline__ void direct_epilogue(const edtr_igemm_params& p, f32x
         char* const rl = smem + wave * 16384;
         if constexpr (RES) {
             pin8(cb[0]); pin8(cb[1]);                   // (the bias loads are consumed BEFORE the DMAs: a compiler-placed wait on them would drain the DMAs too)
-            const u32x4 srd_r = srd_of(p.residual);
+            const u32x4 srd_r = make_srd(p.residual);
 #pragma unroll
             for (int mb = 0; mb < 8; ++mb) {
                 const int64_t mu = mu0 + blk_off(mb);
                 const uint32_t so = (uint32_t)((mu * p.ldr + nu) * 2);
-                dma(lo_r1 * 2, srd_r, so, smem_base + wave * 16384 + (2 * mb) * 1024);
-                dma(lo_r2 * 2, srd_r, so, smem_base + wave * 16384 + (2 * mb + 1) * 1024);
+                dma16_buf(lo_r1 * 2, srd_r, so, smem_base + wave * 16384 + (2 * mb) * 1024);
+                dma16_buf(lo_r2 * 2, srd_r, so, smem_base + wave * 16384 + (2 * mb + 1) * 1024);
             }
         }
         const int rd0 = (lo8 ? 0 : 1024) + (lane_e & ~8) * 16, rd1 = (lo8 ? 0 : 1024) + (lane_e | 8) * 16;
@@ -205,7 +162,7 @@ __device__ __forceinline__ void direct_epilogue(const edtr_igemm_params& p, f32x
                     f[hp][i + 4] = __builtin_fmaf(acc[mb][2 * hp + 1][i], alpha, cb[hp][i + 4]);
                 }
             if constexpr (RES) {
-                asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
+                wait_vm<14>();
                 const U4 q0 = *reinterpret_cast<const U4*>(rl + mb * 2048 + rd0), q1 = *reinterpret_cast<const U4*>(rl + mb * 2048 + rd1);
                 float rf[8];
                 unpack8<T>(q0, rf);
@@ -397,8 +354,8 @@ __global__ void __launch_bounds__(512, 1) igemm_halo512_kernel(const edtr_igemm_
 
     const uint16_t* a1 = static_cast<const uint16_t*>(p.a1);
     const uint32_t smem_base = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
-    const u32x4 srd_a = srd_of(a1);
-    const u32x4 srd_w = srd_of(p.w);
+    const u32x4 srd_a = make_srd(a1);
+    const u32x4 srd_w = make_srd(p.w);
     const int Cin = p.C1, nchunk = Cin / CK;
 
     // ---- staging geometry
@@ -414,8 +371,8 @@ __global__ void __launch_bounds__(512, 1) igemm_halo512_kernel(const edtr_igemm_
         voff_w = (uint32_t)(((int64_t)n * p.ldw + c * 8) * 2);
     }
     auto stage_w = [&](int chunk, int tap, int buf) {
-        const uint32_t vo = chunk < nchunk ? voff_w : kOob;
-        dma(vo, srd_w, (uint32_t)((tap * Cin + chunk * CK) * 2), smem_base + W_BASE + buf * WTAP + wave * 1024);
+        const uint32_t vo = chunk < nchunk ? voff_w : kOobOffset;
+        dma16_buf(vo, srd_w, (uint32_t)((tap * Cin + chunk * CK) * 2), smem_base + W_BASE + buf * WTAP + wave * 1024);
     };
     // the weight slices of taps 0 and 1 start their flight before the patch addresses are worked out
     stage_w(0, 0, 0);
@@ -429,18 +386,18 @@ __global__ void __launch_bounds__(512, 1) igemm_halo512_kernel(const edtr_igemm_
         const int iy = sy0 + py, ix = sx0 + px;
         const bool ok = pp < PPIX && iy >= 0 && iy < p.IH && ix >= 0 && ix < p.IW;
         const int c = slot ^ key8(px);
-        voff_p[j] = ok ? (uint32_t)(((((int64_t)img * p.IH + iy) * p.IW + ix) * p.ld1 + c * 8) * 2) : kOob;
+        voff_p[j] = ok ? (uint32_t)(((((int64_t)img * p.IH + iy) * p.IW + ix) * p.ld1 + c * 8) * 2) : kOobOffset;
         if (ok) gn_bits |= (uint32_t)(8 | c) << (4 * j);
     }
     auto stage_p = [&](int chunk, int j, int par) {
-        const uint32_t vo = chunk < nchunk ? voff_p[j] : kOob;
-        dma(vo, srd_a, (uint32_t)(chunk * CK * 2), smem_base + par * PATCHB + (wave + 8 * j) * 1024);
+        const uint32_t vo = chunk < nchunk ? voff_p[j] : kOobOffset;
+        dma16_buf(vo, srd_a, (uint32_t)(chunk * CK * 2), smem_base + par * PATCHB + (wave + 8 * j) * 1024);
     };
     const bool gnf = p.a_gn != nullptr;
-    const u32x4 srd_t = srd_of(gnf ? p.a_gn + (int64_t)img * Cin * 2 : reinterpret_cast<const float*>(a1));
+    const u32x4 srd_t = make_srd(gnf ? p.a_gn + (int64_t)img * Cin * 2 : reinterpret_cast<const float*>(a1));
     auto stage_t = [&](int chunk, int par) {                 // (scale, shift) of the chunk's 32 channels: 256 bytes, lanes 0..15
-        const uint32_t vo = (chunk < nchunk && lane < 16) ? (uint32_t)(lane * 16) : kOob;
-        dma(vo, srd_t, (uint32_t)(chunk * CK * 8), smem_base + TBL + par * 1024);
+        const uint32_t vo = (chunk < nchunk && lane < 16) ? (uint32_t)(lane * 16) : kOobOffset;
+        dma16_buf(vo, srd_t, (uint32_t)(chunk * CK * 8), smem_base + TBL + par * 1024);
     };
     auto gn_piece = [&](int j, int par) {
         const uint32_t bits = gn_bits >> (4 * j);
@@ -499,11 +456,11 @@ __global__ void __launch_bounds__(512, 1) igemm_halo512_kernel(const edtr_igemm_
     if (gnf) stage_t(0, 0);
 #pragma unroll
     for (int j = 0; j < NPP; ++j) stage_p(0, j, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     if (gnf) {               // the first chunk's patch: every wave normalises its own pieces (its own table copy has landed too)
 #pragma unroll
         for (int j = 0; j < NPP; ++j) gn_piece(j, 0);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lds();
     }
     __builtin_amdgcn_s_barrier();
     if (g == 1) __builtin_amdgcn_s_barrier();           // waves 4-7 run half a phase behind their SIMD partners
@@ -539,7 +496,7 @@ __global__ void __launch_bounds__(512, 1) igemm_halo512_kernel(const edtr_igemm_
                 else wait_vm<INFLIGHT>();
             }
             __builtin_amdgcn_s_barrier();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wait_lds();
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -566,7 +523,7 @@ __global__ void __launch_bounds__(512, 1) igemm_halo512_kernel(const edtr_igemm_
     };
     for (int c = 0; c < nchunk - 1; ++c) chunk_body(c, std::false_type{});
     chunk_body(nchunk - 1, std::true_type{});
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     if (g == 0) __builtin_amdgcn_s_barrier();           // re-align the two wave groups
     // ---- K tail (edtr_hip.h: a3): C3 more columns read at the output pixel itself, i.e. the centre tap of C3 / 32 more chunks.
     // Not part of the counted schedule above: a plain double-buffered loop with full waits (chunk t + 1 flies while chunk t is
@@ -574,7 +531,7 @@ __global__ void __launch_bounds__(512, 1) igemm_halo512_kernel(const edtr_igemm_
     // normalises the 9-tap operand only.
     if (p.a3 != nullptr) {
         const int ntail = p.C3 / CK;
-        const u32x4 srd_3 = srd_of(p.a3);
+        const u32x4 srd_3 = make_srd(p.a3);
         __syncthreads();                                // every wave's look-ahead DMAs (zeros) have landed, nobody reads the buffers
         int lane_t = lane;                              // (opaque: keeps the tail's addresses out of the main loop's register file)
         asm volatile("" : "+v"(lane_t));
@@ -584,17 +541,17 @@ __global__ void __launch_bounds__(512, 1) igemm_halo512_kernel(const edtr_igemm_
             const int py = pp / PW, px = pp - py * PW;
             const int iy = sy0 + py, ix = sx0 + px;
             const bool ok = pp < PPIX && iy >= 0 && iy < p.IH && ix >= 0 && ix < p.IW;
-            voff_p[j] = ok ? (uint32_t)(((((int64_t)img * p.IH + iy) * p.IW + ix) * p.ld3 + (slot ^ key8(px)) * 8) * 2) : kOob;
+            voff_p[j] = ok ? (uint32_t)(((((int64_t)img * p.IH + iy) * p.IW + ix) * p.ld3 + (slot ^ key8(px)) * 8) * 2) : kOobOffset;
         }
         auto stage_tail = [&](int t, int par) {
 #pragma unroll
-            for (int j = 0; j < NPP; ++j) dma(voff_p[j], srd_3, (uint32_t)(t * CK * 2), smem_base + par * PATCHB + (wave + 8 * j) * 1024);
-            dma(voff_w, srd_w, (uint32_t)((9 * Cin + t * CK) * 2), smem_base + W_BASE + par * WTAP + wave * 1024);
+            for (int j = 0; j < NPP; ++j) dma16_buf(voff_p[j], srd_3, (uint32_t)(t * CK * 2), smem_base + par * PATCHB + (wave + 8 * j) * 1024);
+            dma16_buf(voff_w, srd_w, (uint32_t)((9 * Cin + t * CK) * 2), smem_base + W_BASE + par * WTAP + wave * 1024);
         };
         stage_tail(0, 0);
         for (int t = 0; t < ntail; ++t) {
             const int par = t & 1;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
             __syncthreads();                            // chunk t has landed for every wave; the other buffers are free
             if (t + 1 < ntail) stage_tail(t + 1, par ^ 1);
             const char* pa = smem + par * PATCHB;
@@ -638,22 +595,6 @@ constexpr int BIASL = RED + 4096;               // the launch's bias row (fp32, 
 constexpr int LDS_BYTES_P = BIASL + 2048;
 }
 
-template <int N> __device__ __forceinline__ void wait_vm_n() {
-    static_assert(N >= 1 && N <= 12, "wait_vm_n");
-    if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if constexpr (N == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-    else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    else if constexpr (N == 11) asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-}
-
 template <typename T>
 __global__ void __launch_bounds__(512, 1) igemm_halo512p_kernel(const edtr_igemm_params p) {
     using namespace h1p;
@@ -674,11 +615,11 @@ __global__ void __launch_bounds__(512, 1) igemm_halo512p_kernel(const edtr_igemm
 
     const uint16_t* a1 = static_cast<const uint16_t*>(p.a1);
     const uint32_t smem_base = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
-    const u32x4 srd_a = srd_of(a1);
-    const u32x4 srd_w = srd_of(p.w);
+    const u32x4 srd_a = make_srd(a1);
+    const u32x4 srd_w = make_srd(p.w);
     const int Cin = p.C1, nchunk = Cin / CK;
     const bool gnf = p.a_gn != nullptr;
-    const u32x4 srd_t = srd_of(gnf ? p.a_gn : reinterpret_cast<const float*>(a1));
+    const u32x4 srd_t = make_srd(gnf ? p.a_gn : reinterpret_cast<const float*>(a1));
     const bool gn_acc = p.gn_partial != nullptr;
 
     // unit geometry (wave-uniform): cur = the unit whose taps run, nxt = the unit whose first operands the last chunk stages
@@ -707,7 +648,7 @@ __global__ void __launch_bounds__(512, 1) igemm_halo512p_kernel(const edtr_igemm
         voff_w = (uint32_t)(((int64_t)n * p.ldw + c * 8) * 2);
     }
     auto stage_w = [&](int n0, int chunk, int tap, int buf, bool valid) {
-        dma(valid ? voff_w : kOob, srd_w, (uint32_t)(((int64_t)n0 * p.ldw + tap * Cin + chunk * CK) * 2), smem_base + W_BASE + buf * WTAP + wave * 1024);
+        dma16_buf(valid ? voff_w : kOobOffset, srd_w, (uint32_t)(((int64_t)n0 * p.ldw + tap * Cin + chunk * CK) * 2), smem_base + W_BASE + buf * WTAP + wave * 1024);
     };
     uint32_t voff_p[NPP];
     uint32_t gn_bits = 0;
@@ -722,16 +663,16 @@ __global__ void __launch_bounds__(512, 1) igemm_halo512p_kernel(const edtr_igemm
             const int iy = u.sy0 + py, ix = u.sx0 + px;
             const bool ok = valid && pp < PPIX && iy >= 0 && iy < p.IH && ix >= 0 && ix < p.IW;
             const int c = slot ^ key8(px);
-            voff_p[j] = ok ? (uint32_t)(((((int64_t)u.img * p.IH + iy) * p.IW + ix) * p.ld1 + c * 8) * 2) : kOob;
+            voff_p[j] = ok ? (uint32_t)(((((int64_t)u.img * p.IH + iy) * p.IW + ix) * p.ld1 + c * 8) * 2) : kOobOffset;
             if (ok) gn_bits |= (uint32_t)(8 | c) << (4 * j);
         }
     };
     auto stage_p = [&](int chunk, int j, int par) {
-        dma(voff_p[j], srd_a, (uint32_t)(chunk * CK * 2), smem_base + par * PATCHB + (wave + 8 * j) * 1024);
+        dma16_buf(voff_p[j], srd_a, (uint32_t)(chunk * CK * 2), smem_base + par * PATCHB + (wave + 8 * j) * 1024);
     };
     auto stage_t = [&](int img, int chunk, int par, bool valid) {
-        const uint32_t vo = (valid && lane < 16) ? (uint32_t)(lane * 16) : kOob;
-        dma(vo, srd_t, (uint32_t)((img * Cin * 2 + chunk * CK * 2) * 4), smem_base + TBL + par * 1024);
+        const uint32_t vo = (valid && lane < 16) ? (uint32_t)(lane * 16) : kOobOffset;
+        dma16_buf(vo, srd_t, (uint32_t)((img * Cin * 2 + chunk * CK * 2) * 4), smem_base + TBL + par * 1024);
     };
     auto gn_piece = [&](int j, int par) {
         const uint32_t bits = gn_bits >> (4 * j);
@@ -798,12 +739,12 @@ __global__ void __launch_bounds__(512, 1) igemm_halo512p_kernel(const edtr_igemm
         if (p.bias_n) b = *reinterpret_cast<const f32x4*>(p.bias_n + 4 * tid);
         *reinterpret_cast<f32x4*>(smem + BIASL + 16 * tid) = b;
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     if (gnf) {
 #pragma unroll
         for (int j = 0; j < NPP; ++j) gn_piece(j, 0);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lds();
     __builtin_amdgcn_s_barrier();
     if (g == 1) __builtin_amdgcn_s_barrier();           // waves 4-7 run half a phase behind their SIMD partners
     asm volatile("" ::: "memory");
@@ -811,15 +752,15 @@ __global__ void __launch_bounds__(512, 1) igemm_halo512p_kernel(const edtr_igemm
 
     // The stores are buffer-addressed: lane offset + a wave-uniform scalar offset, and an out-of-range lane offset DROPS the lane — the first
     // unit of a workgroup has no predecessor, but its first chunk must issue the same 16 instructions (the counted waits count them).
-    const u32x4 srd_o = srd_of(p.out);
-    uint32_t so1 = kOob, so2 = kOob;
+    const u32x4 srd_o = make_srd(p.out);
+    uint32_t so1 = kOobOffset, so2 = kOobOffset;
     auto store_piece = [&](const Unit& u, int k) {            // store instruction k of the wave: pixel block k >> 1, lanes' pixels pa (+ 8)
         const int mb = k >> 1;
         const int64_t mu = (int64_t)u.m0 + (4 * q + (mb & 3)) * p.OW + 16 * (mb >> 2);
         const uint32_t soff = (uint32_t)((mu * p.ldc + u.n0 + wc * 64) * 2);
         const u32x4 v = u32x4{pk[mb][k & 1].x, pk[mb][k & 1].y, pk[mb][k & 1].z, pk[mb][k & 1].w};
 #ifdef H5P_NOSTORE     // (diagnostic builds only: what do the stores cost the loop?)
-        asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen" : : "v"(v), "v"(kOob), "s"(srd_o), "s"(soff) : "memory");
+        asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen" : : "v"(v), "v"(kOobOffset), "s"(srd_o), "s"(soff) : "memory");
 #else
         asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen" : : "v"(v), "v"((k & 1) ? so2 : so1), "s"(srd_o), "s"(soff) : "memory");
 #endif
@@ -891,7 +832,7 @@ __global__ void __launch_bounds__(512, 1) igemm_halo512p_kernel(const edtr_igemm
                     for (int j = 0; j < 8; ++j) { dst[2 * j] = gs[hp][j]; dst[2 * j + 1] = gq[hp][j]; }
                 }
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wait_lds();
         }
     };
     auto gn_publish = [&](const Unit& u) {                    // per-channel sums of the unit's 512 pixels -> its four 128-row slots (the first takes them)
@@ -957,11 +898,11 @@ __global__ void __launch_bounds__(512, 1) igemm_halo512p_kernel(const edtr_igemm
                 // (+ in phase 1 the STB stores issued between the units: younger than everything phase 2 reads)
                 constexpr int INFLIGHT = 1 + (PH >= PP0 && PH < PP0 + NPP ? 1 : 0) + (PH - 1 >= PP0 && PH - 1 < PP0 + NPP ? 1 : 0) + (STH ? 1 : 0) + (STP ? 1 : 0) +
                                          (ST && PH == 1 ? STB : 0);
-                if (PH == 1 && gnf) wait_vm_n<INFLIGHT + 1>();
-                else wait_vm_n<INFLIGHT>();
+                if (PH == 1 && gnf) wait_vm<INFLIGHT + 1>();
+                else wait_vm<INFLIGHT>();
             }
             __builtin_amdgcn_s_barrier();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wait_lds();
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -1073,8 +1014,8 @@ __global__ void __launch_bounds__(512, 1) igemm_halo160_kernel(const edtr_igemm_
 
     const uint16_t* a1 = static_cast<const uint16_t*>(p.a1);
     const uint32_t smem_base = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
-    const u32x4 srd_a = srd_of(a1);
-    const u32x4 srd_w = srd_of(p.w);
+    const u32x4 srd_a = make_srd(a1);
+    const u32x4 srd_w = make_srd(p.w);
     const int Cin = p.C1, nchunk = Cin / CK;
 
     // ten weight pieces per tap (LDS rows 16 piece ..): wave w requests piece w, waves 0 and 1 also pieces 8 and 9 — NOT two requests
@@ -1088,11 +1029,11 @@ __global__ void __launch_bounds__(512, 1) igemm_halo160_kernel(const edtr_igemm_
         const int R = (wave + 8 * jj) * 16 + (lane >> 2), slot = lane & 3;
         const int r = R & 15, nb = R >> 4;
         const int n = n0 + 40 * (r >> 2) + 4 * nb + (r & 3);
-        voff_w[jj] = R < 160 ? (uint32_t)(((int64_t)n * p.ldw + (slot ^ key8(R)) * 8) * 2) : kOob;
+        voff_w[jj] = R < 160 ? (uint32_t)(((int64_t)n * p.ldw + (slot ^ key8(R)) * 8) * 2) : kOobOffset;
     }
     auto stage_w = [&](int chunk, int tap, int buf) {
-        dma(chunk < nchunk ? voff_w[0] : kOob, srd_w, (uint32_t)((tap * Cin + chunk * CK) * 2), smem_base + W_BASE + buf * WSL + wave * 1024);
-        if (nwp == 2) dma(chunk < nchunk ? voff_w[1] : kOob, srd_w, (uint32_t)((tap * Cin + chunk * CK) * 2), smem_base + W_BASE + buf * WSL + (wave + 8) * 1024);
+        dma16_buf(chunk < nchunk ? voff_w[0] : kOobOffset, srd_w, (uint32_t)((tap * Cin + chunk * CK) * 2), smem_base + W_BASE + buf * WSL + wave * 1024);
+        if (nwp == 2) dma16_buf(chunk < nchunk ? voff_w[1] : kOobOffset, srd_w, (uint32_t)((tap * Cin + chunk * CK) * 2), smem_base + W_BASE + buf * WSL + (wave + 8) * 1024);
     };
     stage_w(0, 0, 0);
     stage_w(0, 1, 1);
@@ -1104,11 +1045,11 @@ __global__ void __launch_bounds__(512, 1) igemm_halo160_kernel(const edtr_igemm_
         const int py = pp / PW, px = pp - py * PW;
         const int iy = sy0 + py, ix = sx0 + px;
         const bool ok = pp < PPIX && iy >= 0 && iy < p.IH && ix >= 0 && ix < p.IW;
-        voff_p[j] = ok ? (uint32_t)(((((int64_t)img * p.IH + iy) * p.IW + ix) * p.ld1 + (slot ^ key8(px)) * 8) * 2) : kOob;
+        voff_p[j] = ok ? (uint32_t)(((((int64_t)img * p.IH + iy) * p.IW + ix) * p.ld1 + (slot ^ key8(px)) * 8) * 2) : kOobOffset;
     }
     auto stage_p = [&](int chunk, int j, int par) {
         const int piece = wave + 8 * j;
-        dma(chunk < nchunk ? voff_p[j] : kOob, srd_a, (uint32_t)(chunk * CK * 2), smem_base + (piece < 21 ? P_BASE + par * PATCHB + piece * 1024 : DUMP));
+        dma16_buf(chunk < nchunk ? voff_p[j] : kOobOffset, srd_a, (uint32_t)(chunk * CK * 2), smem_base + (piece < 21 ? P_BASE + par * PATCHB + piece * 1024 : DUMP));
     };
 
     // fragment reads: pixel block mb = patch row 2 wave + mb (+ ky), pixels l15 (+ kx); weight block nb = slice rows 16 nb + l15
@@ -1128,7 +1069,7 @@ __global__ void __launch_bounds__(512, 1) igemm_halo160_kernel(const edtr_igemm_
 
 #pragma unroll
     for (int j = 0; j < NPP; ++j) stage_p(0, j, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     if (g == 1) __builtin_amdgcn_s_barrier();           // waves 4-7 run half a phase behind their SIMD partners
     asm volatile("" ::: "memory");
@@ -1152,7 +1093,7 @@ __global__ void __launch_bounds__(512, 1) igemm_halo160_kernel(const edtr_igemm_
             __builtin_amdgcn_s_barrier();
             stage_w(c3, TAP3, (rb + TAP + 3) & 3);
             if constexpr (TAP >= 1 && TAP <= NPP) stage_p(c + 1, TAP - 1, par ^ 1);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wait_lds();
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -1172,13 +1113,13 @@ __global__ void __launch_bounds__(512, 1) igemm_halo160_kernel(const edtr_igemm_
         if (c0 + 2 < nchunk) chunk_body(c0 + 2, IC<2>{});
         if (c0 + 3 < nchunk) chunk_body(c0 + 3, IC<3>{});
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     if (g == 0) __builtin_amdgcn_s_barrier();           // re-align the two wave groups
     // ---- K tail (edtr_hip.h: a3; as in tile 17): the centre tap of C3 / 32 more chunks read from a3, double-buffered over the two
     // patch buffers and ring slots 0 / 1, full waits
     if (p.a3 != nullptr) {
         const int ntail = p.C3 / CK;
-        const u32x4 srd_3 = srd_of(p.a3);
+        const u32x4 srd_3 = make_srd(p.a3);
         __syncthreads();                                // every wave's look-ahead DMAs (zeros) have landed, nobody reads the buffers
         int lane_t = lane;                              // (opaque: keeps the tail's addresses out of the main loop's register file)
         asm volatile("" : "+v"(lane_t));
@@ -1188,21 +1129,21 @@ __global__ void __launch_bounds__(512, 1) igemm_halo160_kernel(const edtr_igemm_
             const int py = pp / PW, px = pp - py * PW;
             const int iy = sy0 + py, ix = sx0 + px;
             const bool ok = pp < PPIX && iy >= 0 && iy < p.IH && ix >= 0 && ix < p.IW;
-            voff_p[j] = ok ? (uint32_t)(((((int64_t)img * p.IH + iy) * p.IW + ix) * p.ld3 + (slot ^ key8(px)) * 8) * 2) : kOob;
+            voff_p[j] = ok ? (uint32_t)(((((int64_t)img * p.IH + iy) * p.IW + ix) * p.ld3 + (slot ^ key8(px)) * 8) * 2) : kOobOffset;
         }
         auto stage_tail = [&](int t, int par) {
 #pragma unroll
             for (int j = 0; j < NPP; ++j) {
                 const int piece = wave + 8 * j;
-                dma(voff_p[j], srd_3, (uint32_t)(t * CK * 2), smem_base + (piece < 21 ? P_BASE + par * PATCHB + piece * 1024 : DUMP));
+                dma16_buf(voff_p[j], srd_3, (uint32_t)(t * CK * 2), smem_base + (piece < 21 ? P_BASE + par * PATCHB + piece * 1024 : DUMP));
             }
-            dma(voff_w[0], srd_w, (uint32_t)((9 * Cin + t * CK) * 2), smem_base + W_BASE + par * WSL + wave * 1024);
-            if (nwp == 2) dma(voff_w[1], srd_w, (uint32_t)((9 * Cin + t * CK) * 2), smem_base + W_BASE + par * WSL + (wave + 8) * 1024);
+            dma16_buf(voff_w[0], srd_w, (uint32_t)((9 * Cin + t * CK) * 2), smem_base + W_BASE + par * WSL + wave * 1024);
+            if (nwp == 2) dma16_buf(voff_w[1], srd_w, (uint32_t)((9 * Cin + t * CK) * 2), smem_base + W_BASE + par * WSL + (wave + 8) * 1024);
         };
         stage_tail(0, 0);
         for (int t = 0; t < ntail; ++t) {
             const int par = t & 1;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
             __syncthreads();                            // chunk t has landed for every wave; the other buffers are free
             if (t + 1 < ntail) stage_tail(t + 1, par ^ 1);
             U4 bfr[10], afr[2];

@@ -6,12 +6,13 @@
 // conv halo / concat / upsample, so the staging is register-based, not LDS-DMA), LDS is double
 // buffered with ONE barrier per K-tile: the loads of tile t+2 are issued right after the registers
 // holding tile t+1 have been written to LDS, so their latency hides under the MFMAs of tile t+1.
-// LDS tiles are [rows][64 x 16-bit] with the XOR swizzle of common.h (conflict-free ds_read_b128).
+// LDS tiles are [rows][64 x 16-bit] with the XOR swizzle of wave_prims.h (conflict-free ds_read_b128).
 // The epilogue stages the fp32 accumulators through LDS so that bias / time-embedding row vector /
 // residual / activation are applied on 8-wide row vectors and stored with 16-byte writes.
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
+#include "wave_prims.h"
 #include "igemm_plan.h"
 
 // Diagnostic build only (tools/exp/igemm_stamps.py compiles with -DEDTR_STAMPS): thread 0 of every workgroup stores
@@ -1274,9 +1275,9 @@ __global__ void __launch_bounds__(kThreads, 2) igemm_dma_kernel(const edtr_igemm
 #ifdef EDTR_STAMPS
             stamp_acc[0] += __builtin_amdgcn_s_memtime() - ts0;
 #endif
-            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // this wave's 8 DMAs of tile kt have landed
+            wait_vm<8>();   // this wave's 8 DMAs of tile kt have landed
         } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
         }
 #ifdef EDTR_STAMPS
         const uint64_t ts1 = __builtin_amdgcn_s_memtime();
@@ -1306,7 +1307,7 @@ __global__ void __launch_bounds__(kThreads, 2) igemm_dma_kernel(const edtr_igemm
 #pragma unroll
                 for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = T::mfma(af[mi], bf[ni], acc[mi][ni]);
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lds();
 #ifdef EDTR_STAMPS
         stamp_acc[3] += __builtin_amdgcn_s_memtime() - ts2;     // ds_read + MFMA issue section
 #endif
@@ -1521,7 +1522,7 @@ __global__ void __launch_bounds__(512, 1) igemm_256_kernel(const edtr_igemm_para
     using H2 = std::integral_constant<int, 2>;
     using H3 = std::integral_constant<int, 3>;
 
-    // ---- fragment read geometry (conflict-free ds_read_b128 of the swizzled image, see common.h tile_off)
+    // ---- fragment read geometry (conflict-free ds_read_b128 of the swizzled image, see wave_prims.h tile_off)
     const int a_rd = tile_off(wr * 64 + l15, lq);      // + blk * 2048, ^ 64 for the second k-step
     const int b_rd = tile_off(wc * 32 + l15, lq);
 
@@ -1564,9 +1565,9 @@ __global__ void __launch_bounds__(512, 1) igemm_256_kernel(const edtr_igemm_para
     };
     // second half of every phase: wait for the half-tiles that must have landed, rendezvous, multiply, rendezvous
     auto compute = [&](auto AHc, auto BHc) {
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        wait_vm<6>();
         __builtin_amdgcn_s_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lds();
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
         mma(AHc, BHc);
@@ -1582,7 +1583,7 @@ __global__ void __launch_bounds__(512, 1) igemm_256_kernel(const edtr_igemm_para
     stage_half(sE, 0, H0{}); stage_half(sE, 0, H1{}); stage_half(sE, 0, H2{}); stage_half(sE, 0, H3{});
     stage_half(sO, 1, H2{}); stage_half(sO, 1, H0{});
     advance2(sE);
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    wait_vm<4>();
     __builtin_amdgcn_s_barrier();
     if (wr == 1) __builtin_amdgcn_s_barrier();          // waves 4-7 run half a phase behind their SIMD partners
     asm volatile("" ::: "memory");
@@ -1600,7 +1601,7 @@ __global__ void __launch_bounds__(512, 1) igemm_256_kernel(const edtr_igemm_para
         read_a(1, 1);                  stage_half(sO, 1, H2{}); compute(H1{}, H1{});                 // phase 7
                                        stage_half(sO, 1, H0{}); compute(H1{}, H0{});                 // phase 8
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     if (wr == 0) __builtin_amdgcn_s_barrier();          // re-align the two wave groups
     __syncthreads();
 
@@ -1846,13 +1847,9 @@ __global__ void __launch_bounds__(kThreads, 2) igemm_n160_kernel(const edtr_igem
         const int cur = kt & 1;
         if (kt + 1 < nkt) {
             issue_tile(kt0 + kt + 1, cur ^ 1);
-            // this wave's MB + NB DMAs of tile kt have landed
-            static_assert(MB + NB == 9 || MB + NB == 8 || MB + NB == 6, "add the literal wait count for this geometry");
-            if constexpr (MB + NB == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-            else if constexpr (MB + NB == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            wait_vm<MB + NB>();         // this wave's MB + NB DMAs of tile kt have landed
         } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
         }
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
@@ -1871,9 +1868,7 @@ __global__ void __launch_bounds__(kThreads, 2) igemm_n160_kernel(const edtr_igem
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb) acc[mb][nb] = T::mfma16(af[mb], bf[nb], acc[mb][nb]);
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        block_sync();
     }
     if (nkt == 0) __syncthreads();
     EDTR_STAMP(3);
@@ -2208,12 +2203,12 @@ __global__ void __launch_bounds__(512, 1) igemm_halo_kernel(const edtr_igemm_par
     }
 #pragma unroll
     for (int j = 0; j < NPP; ++j) stage_p(cbeg, j, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     if constexpr (GEO == 0) {
         if (gnf) {           // the first chunk's patch: every wave normalises its own pieces (its own table copy has landed too)
 #pragma unroll
             for (int j = 0; j < NPP; ++j) gn_piece(j, 0);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wait_lds();
         }
     }
     __builtin_amdgcn_s_barrier();
@@ -2253,13 +2248,11 @@ __global__ void __launch_bounds__(512, 1) igemm_halo_kernel(const edtr_igemm_par
                 // issued in this and the previous phase: 1 weight piece each, + 1 patch piece each in phases PP0 .. PP0 + NPP - 1
                 // (+ the table piece of phase 0 when the GroupNorm is fused)
                 constexpr int INFLIGHT = 2 + (PH >= PP0 && PH < PP0 + NPP ? 1 : 0) + (PH - 1 >= PP0 && PH - 1 < PP0 + NPP ? 1 : 0);
-                if (GEO == 0 && PH == 1 && gnf) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");       // (GEO 0: INFLIGHT is 2 at phase 1)
-                else if constexpr (INFLIGHT == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                else if constexpr (INFLIGHT == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+                if (GEO == 0 && PH == 1 && gnf) wait_vm<3>();       // (GEO 0: INFLIGHT is 2 at phase 1)
+                else wait_vm<INFLIGHT>();
             }
             __builtin_amdgcn_s_barrier();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wait_lds();
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -2283,7 +2276,7 @@ __global__ void __launch_bounds__(512, 1) igemm_halo_kernel(const edtr_igemm_par
             rb = rbuf[1];                                // 4 % 3 == 1
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     if (g == 0) __builtin_amdgcn_s_barrier();           // re-align the two wave groups
     __syncthreads();
     // ---- K tail (a3: the 1x1 skip convolution of a width-changing ResBlock as C3 more columns of this product, centre tap only).
@@ -2330,7 +2323,7 @@ __global__ void __launch_bounds__(512, 1) igemm_halo_kernel(const edtr_igemm_par
             stage_tail(tbeg, 0);
             for (int t = tbeg; t < tend; ++t) {
                 const int par = (t - tbeg) & 1;
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                wait_vm<0>();
                 __syncthreads();                   // chunk t has landed for every wave; nobody reads the other buffers any more
                 if (t + 1 < tend) stage_tail(t + 1, par ^ 1);
                 const char* pa = smem + par * PATCHB;

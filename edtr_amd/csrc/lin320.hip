@@ -18,6 +18,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
+#include "wave_prims.h"
 
 namespace {
 
@@ -33,14 +34,6 @@ constexpr int L_STG = 2 * LCHB;                // staging tiles: 4 waves x LSTGB
 constexpr int L_CV = L_STG + 4 * LSTGB;        // the additive row (fp32, N <= 1024)
 constexpr int L_LDS = L_CV + 4096;             // 80 KiB: two workgroups per CU
 static_assert(LSTGB >= 32 * LPITCH && 2 * L_LDS <= 160 * 1024, "LDS budget");
-
-template <int N> __device__ __forceinline__ void lwait() {
-    static_assert(N == 0 || N == 4 || N == 5 || N == 9, "lwait");
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-}
 
 template <typename T, bool LN, bool RES, bool GN>
 __global__ void __launch_bounds__(256, 2) lin320_kernel(const edtr_lin320_params p) {
@@ -78,7 +71,7 @@ __global__ void __launch_bounds__(256, 2) lin320_kernel(const edtr_lin320_params
         // The workgroup's 128 rows lie in one image: its table row (2.5 KiB) crosses LDS (the staging tiles are idle until the first group).
         const int img = (blockIdx.x * LBM) / p.rows_per_image;
         if (tid < LK / 2) *reinterpret_cast<f32x4*>(smem + L_STG + 16 * tid) = *reinterpret_cast<const f32x4*>(p.gn_table + (int64_t)img * LK * 2 + 4 * tid);
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        wait_vm_lds();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         int tbo = L_STG + 64 * lh;
@@ -141,7 +134,7 @@ __global__ void __launch_bounds__(256, 2) lin320_kernel(const edtr_lin320_params
     const uint16_t* resp = RES ? static_cast<const uint16_t*>(p.residual) + (int64_t)(m0 + erow) * p.ldr + ecol : nullptr;
     uint16_t* const outp = static_cast<uint16_t*>(p.out) + (int64_t)(m0 + erow) * p.ldo + ecol;
 
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // own fragments of chunk 0, own part of the additive row
+    wait_vm_lds();      // own fragments of chunk 0, own part of the additive row
 #pragma unroll 1
     for (int g = 0; g < (nchunk >> 1); ++g) {
         U4 rv[4];
@@ -151,9 +144,9 @@ __global__ void __launch_bounds__(256, 2) lin320_kernel(const edtr_lin320_params
             const int c = 2 * g + hh;
             // this wave's fragments of chunk c have landed; younger than them: the residual loads of this group (odd chunks), the four
             // stores of the previous group's epilogue (even chunks; none in front of chunk 0, which the prologue waited for outright)
-            if (hh == 0) lwait<4>();
-            else if (RES) lwait<4>();
-            else lwait<0>();
+            if (hh == 0) wait_vm<4>();
+            else if (RES) wait_vm<4>();
+            else wait_vm<0>();
             __builtin_amdgcn_s_barrier();                      // ... everyone's; chunk c - 1 is multiplied: its buffer is free
             asm volatile("" ::: "memory");                     // (a raw barrier: __syncthreads() would drain the residual loads and the DMAs)
             if (c + 1 < nchunk) issue_w(c + 1);

@@ -13,14 +13,13 @@
 // V is token-major in memory but the V^T operand needs 8 consecutive keys of one channel per lane: each wave transposes its
 // 64 x 32 V block through a private 4.5 KiB LDS slab (ds_write_b16 columns, ds_read_b128 rows).
 #include "common.h"
+#include "wave_prims.h"
 #include <type_traits>
 
 namespace {
 
 constexpr int WS = 8, NTOK = 64, HP = 32;          // window edge, tokens per window, padded head width
 constexpr int VT_PITCH = 72;                        // 16-bit elements per V^T row in LDS (64 keys + 8 pad: 144-byte rows)
-
-__device__ __forceinline__ int swap23(int i) { return (i & ~12) | ((i & 4) << 1) | ((i & 8) >> 1); }
 
 template <typename T>
 __global__ void __launch_bounds__(256) window_attn_kernel(const edtr_window_attn_params p, int total_tasks) {
@@ -153,7 +152,7 @@ __global__ void __launch_bounds__(256) window_attn_kernel(const edtr_window_attn
     }
 
     // ---- O^T[d][q] = V^T[d][key] P^T[key][q]
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // this wave's V^T writes have landed (LDS ops of one wave are in order)
+    wait_lds();     // this wave's V^T writes have landed (LDS ops of one wave are in order)
     __builtin_amdgcn_wave_barrier();
     f32x16 o[2];
 #pragma unroll
@@ -299,8 +298,8 @@ __device__ __forceinline__ void swin_mlp_body(const edtr_swin_mlp_params& p, cha
 #pragma unroll 1
     for (int t = 0; t < PERIODS; ++t) {
         // unit(t) (and, at t = 0, the token tile) has landed: everything this wave issued except unit(t + 1)'s three
-        if (t + 1 < PERIODS) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (t + 1 < PERIODS) wait_vm<3>();
+        else wait_vm<0>();
         __syncthreads();
         if (t + 2 < PERIODS) stage_unit(t + 2);                 // into the buffer period t - 2 read
         if (t == 0) {
@@ -637,7 +636,7 @@ __device__ __forceinline__ void swin_attn_body(const edtr_swin_attn_params& p, i
 
 #pragma unroll 1
     for (int n = 0; n < 4 * 3; ++n) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's share of unit n (and, at n = 0, of the token tile) has landed
+        wait_vm<0>();       // this wave's share of unit n (and, at n = 0, of the token tile) has landed
         __syncthreads();                                        // ... everyone's, and the other buffer is free
         if (n + 1 < 12) stage_unit(n + 1);
         if (n == 0) {
@@ -878,7 +877,7 @@ __global__ void __launch_bounds__(SA_THREADS) swin_layer_kernel(const edtr_swin_
 // leave as 16-byte stores (or, for the network's last convolution, as fp32 NCHW planes).  Wave w owns patch rows 2 w, 2 w + 1
 // (32 pixels) x 64 channels: per tap and 16-channel k-step one patch fragment feeds two MFMAs.
 // Patch image: pixel (py, px) at (18 py + px) * 128 B, 16-byte chunk c in slot c ^ ((px >> 1) & 7): the 16 pixels of a
-// ds_read_b128 lane group are 16 different columns (mod 16) for every tap — conflict-free; weights as tile_off (common.h).
+// ds_read_b128 lane group are 16 different columns (mod 16) for every tap — conflict-free; weights as tile_off (wave_prims.h).
 constexpr int C64_THREADS = 512;
 constexpr int C64_W_BYTES = 9 * 64 * 128;                    // 73728
 constexpr int C64_PATCH_INSTRS = 41;                         // 18 * 18 * 128 B = 40.5 KiB: 41 DMA instructions, the last one half used
@@ -946,9 +945,9 @@ __global__ void __launch_bounds__(C64_THREADS) conv64_kernel(const edtr_conv64_p
     for (; patch < patches; patch += gridDim.x, ++it) {
         // the fetch of this patch (and, the first time, the weights) has landed; the previous patch's stores may still be in flight
         // (counted: the fetch was issued BEFORE that patch's 4 — fp32 planes: n_valid >= 1 — store instructions)
-        if (it == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (p.out_nchw_f32) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        if (it == 0) wait_vm<0>();
+        else if (p.out_nchw_f32) wait_vm<1>();
+        else wait_vm<4>();
         __syncthreads();
         const int next = patch + gridDim.x;
         if (next < patches) fetch(next, (it + 1) & 1);
@@ -1076,7 +1075,7 @@ __global__ void __launch_bounds__(CO_THREADS) conv128_out_kernel(const edtr_conv
                 dma16(src, lds0 + CO_W_BYTES + (wave + 8 * q) * 1024);
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // (also the previous patch's stores, issued before these fetches)
+        wait_vm<0>();       // (also the previous patch's stores, issued before these fetches)
         if (p.gn_table) {
             // GroupNorm apply + SiLU of this lane's own 16 bytes of every piece, in place (edtr_gn_apply's arithmetic and rounding)
             const float* tbl = reinterpret_cast<const float*>(smem + CO_TBL);

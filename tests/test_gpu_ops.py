@@ -979,7 +979,7 @@ def test_layernorm_folded_into_the_consumer_gemm(dtype, M, C, N, kind):
     full = alpha * (ln @ w.t()) + bias
     kw = dict(dtype=dtype, a1=x.to(d), w=packed.to(d), M=M, N=N, C1=C, ld1=C, ldw=C, alpha=alpha, bias_n=bq.to(d), ln_stats=stats.to(d), ln_C=C,
               ln_c1=c1.to(d), ln_c2=c2.to(d))
-    # element bound on what the kernel computes from what it reads (igemm.hip:298-303 mean / rstd from the stats slots, :324 the
+    # element bound on what the kernel computes from what it reads (igemm.hip:299-304 mean / rstd from the stats slots, :325 the
     # epilogue): fp64 rstd (a acc - mean a c1) + a c2 + bias over the PACKED 16-bit gamma W, per column a (alpha; vt_alpha = 1 for V).
     # The fp32 epilogue cancels acc against mean c1 and the fp32 variance E[x^2] - mean^2 carries ~C 2^-24 E[x^2] / var: absref
     # takes |x| |P|^T + |mean| |c1| and |acc - mean c1| rstd^2 E[x^2] (k = C)
@@ -1358,7 +1358,7 @@ def test_conv128_out_one_launch(dtype, B, H, W, gn):
     r64, a64 = conv_ref(xin, w.to(dtype).float(), None, padding=1)
     bd = bias[:3, None, None].double()
     extra = None
-    if gn:      # swin.hip:1080-1110: GroupNorm apply + SiLU from the table, packed to 16 bits in place before the product: mirrored
+    if gn:      # swin.hip:1079-1109: GroupNorm apply + SiLU from the table, packed to 16 bits in place before the product: mirrored
         tb = table.cpu()
         xg, flip = gn_apply16(x.float().reshape(B, HW, 128), tb[:, None, :, 0], tb[:, None, :, 1], dtype)
         xg, flip = (t.reshape(B, H, W, 128).permute(0, 3, 1, 2) for t in (xg, flip))
@@ -1415,8 +1415,8 @@ def test_swin_attention_half_one_launch(dtype, B, H, W, shift):
     assert torch.isfinite(got).all()
     assert rel(got[:, :C], ref) < TOL[dtype]
     # per-block check against a reference that mirrors the kernel's roundings: the 16-bit weights it reads (gamma and the q scale in
-    # wg, beta and the qkv bias in c2b, the padded proj), LayerNorm folded into the raw rows (swin.hip:644-659), q / k / v packed to
-    # 16 bits (swin.hip:666-706), O packed to 16 bits before proj (swin.hip:760-774).  The 16-bit P (swin.hip:755) is not mirrored:
+    # wg, beta and the qkv bias in c2b, the padded proj), LayerNorm folded into the raw rows (swin.hip:643-658), q / k / v packed to
+    # 16 bits (swin.hip:665-705), O packed to 16 bits before proj (swin.hip:759-773).  The 16-bit P (swin.hip:754) is not mirrored:
     # its rounding, like the flips of the other roundings, is what the tolerance carries.
     xd = x.double()
     mu = xd[:, :C].mean(1, keepdim=True)
@@ -1520,7 +1520,7 @@ def test_swin_mlp_one_launch(dtype, rows):
     assert torch.isfinite(got).all()
     assert rel(got[:, :C], ref) < TOL[dtype]
     # element bound on a reference that mirrors the kernel: LayerNorm folded into the first product over the RAW rows (swin.hip:
-    # 307-325, one-pass statistics: pre = rstd (acc - mean c1) + c2b), GELU, the hidden units packed to 16 bits (swin.hip:391), the
+    # 306-324, one-pass statistics: pre = rstd (acc - mean c1) + c2b), GELU, the hidden units packed to 16 bits (swin.hip:390), the
     # second product over the 16-bit W2, + b2 + x, one rounding.  Hidden values whose fp32 error bound reaches a 16-bit rounding
     # boundary may land one spacing away (rounded_operand), propagated through |W2|.
     W1, W2 = w1g.to(dtype).double(), w2p.to(dtype).double()
@@ -1686,7 +1686,7 @@ def test_halo_conv_tile17_with_groupnorm_of_its_input(dtype, B, H, W, cin, cout,
     assert rel(outs[True].float(), ref) < TOL[dtype]
     assert rel(outs[True].float(), outs[False].float()) < 0.1 * TOL[dtype]
     # element bound on the mirrored composition: the patch staging applies the table + SiLU in fp32 and packs the result to 16 bits
-    # (igemm.hip:2145-2171 for tile 16, halo512.hip:452-475 for tile 17) — edtr_gn_apply's rounding; the padding stays zero
+    # (igemm.hip:2140-2166 for tile 16, halo512.hip:409-432 for tile 17) — edtr_gn_apply's rounding; the padding stays zero
     tb = table.cpu()
     xg, flip = gn_apply16(x.float().reshape(B, HW, cin), tb[:, None, :, 0], tb[:, None, :, 1], dtype)
     xg, flip = (t.reshape(B, H, W, cin).permute(0, 3, 1, 2) for t in (xg, flip))
@@ -1878,7 +1878,7 @@ def test_halo_conv_with_groupnorm_of_its_input(dtype, B, H, W, cin, cout, splitk
     assert torch.isfinite(outs[True].float()).all()
     assert rel(outs[True].float(), ref) < TOL[dtype]
     # element bound on the mirrored composition: the patch staging applies the table + SiLU in fp32 and packs the result to 16 bits
-    # (igemm.hip:2145-2171 for tile 16, halo512.hip:452-475 for tile 17) — edtr_gn_apply's rounding; the padding stays zero
+    # (igemm.hip:2140-2166 for tile 16, halo512.hip:409-432 for tile 17) — edtr_gn_apply's rounding; the padding stays zero
     tb = table.cpu()
     xg, flip = gn_apply16(x.float().reshape(B, HW, cin), tb[:, None, :, 0], tb[:, None, :, 1], dtype)
     xg, flip = (t.reshape(B, H, W, cin).permute(0, 3, 1, 2) for t in (xg, flip))
@@ -2264,9 +2264,9 @@ def _ffn_operands(ops, dtype, seed=0):
 
 def _ffn_elem(got, x16, o, dtype):
     """Element bound of edtr_ffn on a reference that mirrors its two intermediate roundings: the normalised rows packed to 16 bits
-    (ffn.hip:195-209, two-pass statistics) and G = value * gelu(gate) packed to 16 bits as the B operand of the second product
+    (ffn.hip:173-187, two-pass statistics) and G = value * gelu(gate) packed to 16 bits as the B operand of the second product
     (ffn.hip:13); the first product over the packed gamma W1 (+ W1 beta + b1 in fp32), the second over the 16-bit W2, + b2 + x in
-    fp32 and one rounding (ffn.hip:357).  Where the kernel's fp32 value of an intermediate may cross a 16-bit rounding boundary
+    fp32 and one rounding (ffn.hip:335).  Where the kernel's fp32 value of an intermediate may cross a 16-bit rounding boundary
     (rounded_operand) the one-spacing difference is propagated through the weights that follow."""
     D = x16.shape[1]
     W1, W2 = o["w1p"].double(), o["w2"].to(dtype).double()
@@ -2416,7 +2416,7 @@ def test_lin320_vs_fp32_reference(dtype, M, N, ln, res, pad):
     if ln:
         # lin320.hip rounds the normalised rows to 16 bits before the product (what the LayerNorm launch hands its GEMM): mirrored
         # here; where the kernel's fp32 statistics move a rounding boundary the operand differs by one ulp: 2 u alpha |xn| |W|^T
-        # (lin320.hip:125-133: two-pass statistics, (x - mean) rstd packed to 16 bits before the product)
+        # (lin320.hip:118-126: two-pass statistics, (x - mean) rstd packed to 16 bits before the product)
         xn16, flip = ln_rows16(xf, K, dtype)
         r64, a64 = gemm_ref(xn16, w16, cvec, r, alpha=alpha)
         elem(got, r64, a64, dtype, K, {"16-bit normalised rows, boundary operands": alpha * (flip @ w16.double().abs().t())})
@@ -2447,7 +2447,7 @@ def test_lin320_fused_qkv_with_transposed_v(dtype):
     assert rel(qk.float().cpu(), alpha * ref[:, :2 * C]) < TOL[dtype]
     vref = ref[:, 2 * C:].reshape(B, Ntok, C).permute(0, 2, 1).reshape(B * C, Ntok)
     assert rel(vt[:, :Ntok].float().cpu(), vref) < TOL[dtype]
-    # element bound on the mirrored composition: lin320.hip:125-133 rounds the normalised rows to 16 bits; the product is of the
+    # element bound on the mirrored composition: lin320.hip:118-126 rounds the normalised rows to 16 bits; the product is of the
     # packed gamma W (pack_lin320_w); per-column alpha (vt_alpha = 1 for V), cvec added in fp32, one rounding per output
     xn16, flip = ln_rows16(x, K, dtype)
     w16 = (w * gamma[None, :]).to(dtype)
@@ -2483,7 +2483,7 @@ def test_lin320_applies_a_groupnorm_table_to_its_rows(dtype, res):
     assert rel(out.float().cpu(), ref.to(dtype).float()) < 0.3 * TOL[dtype]      # same roundings as the reference composition: only the fp32 summation order differs
     # element bound on the mirrored composition (lin320.hip rounds x * scale + shift to 16 bits as edtr_gn_apply stores it); where
     # the kernel's fp32 affine lands on the other side of a rounding boundary the operand moves by one ulp: 2 u |xn16| |W|^T
-    # (lin320.hip:95-99: x * scale + shift in fp32 from the exact table, packed to 16 bits)
+    # (lin320.hip:88-92: x * scale + shift in fp32 from the exact table, packed to 16 bits)
     xn16, flip = gn_apply16(x.float().reshape(B, HW, K), table[:, None, :, 0], table[:, None, :, 1], dtype, silu=False)
     xn16, flip, w16 = xn16.reshape(M, K), flip.reshape(M, K), w.to(dtype)
     elem(out, *gemm_ref(xn16, w16, bias, r), dtype, K, {"16-bit normalised rows, boundary operands": flip @ w16.double().abs().t()})

@@ -782,3 +782,32 @@ def test_object_dependencies_are_derived_from_the_include_lines():
         assert all(os.path.isfile(d) for d in build.object_deps(src))
     assert "attn_v3_loop.inc" in deps["attention.hip"]                           # reached through its #define, not a quoted line
     assert all("glue.h" in deps[src] for src in glue) and not any("glue.h" in deps[src] for src in mfma)
+    # the same wall for the inline-asm primitives: the units that use one see wave_prims.h, no glue unit does (norm.hip uses none)
+    prims = [src for src in mfma if src != "norm.hip"]
+    assert all("wave_prims.h" in deps[src] for src in prims)
+    assert not any("wave_prims.h" in [os.path.basename(d) for d in build.object_deps(src)] for src in glue + build.GLUE_SOURCES + ["norm.hip"])
+
+
+def test_wait_dma_and_descriptor_primitives_are_defined_in_wave_prims_only():
+    """csrc/*.hip and common.h, comments stripped: no asm string there holds a wait or an LDS-DMA, and none of the shared helpers is
+    defined there — wave_prims.h is the one place (attn_v3_loop.inc is generated with its waits inside whole asm strings: not read here)"""
+    import re
+    from edtr_amd import build
+    allowed = {}                  # (file, word) -> reason, for a hand-written asm block that legitimately embeds one: none today
+    names = sorted(f for f in os.listdir(build.CSRC) if f.endswith(".hip")) + ["common.h"]
+    assert set(build.SOURCES + build.GLUE_SOURCES) <= set(names)
+    helpers = ["srd_of", "make_srd", "key8", "swap23", "wait_vm", "lwait", "wait_vm_n", "dma4_buf", "block_sync"]
+    for name in names:
+        with open(os.path.join(build.CSRC, name)) as fh:
+            text = fh.read()
+        text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+        text = re.sub(r"//[^\n]*", "", text)
+        for stmt in re.findall(r"\basm\b[^;]*;", text):
+            for word in ("s_waitcnt", "buffer_load_dword", "global_load_lds"):
+                assert word not in stmt or (name, word) in allowed, (name, word, stmt[:80])
+        for h in helpers:
+            assert not re.search(r"\b(?:void|int|u32x4)\s+%s\s*\(" % h, text), (name, h)
+    with open(os.path.join(build.CSRC, "wave_prims.h")) as fh:
+        prims = fh.read()
+    for h in ["make_srd", "key8", "swap23", "wait_vm", "dma4_buf", "block_sync"]:
+        assert len(re.findall(r"\b(?:void|int|u32x4)\s+%s\s*\(" % h, prims)) == 1, h
