@@ -24,6 +24,7 @@ import torch
 import torch.nn.functional as F
 
 import attn_cases
+from glue16_reference import norm_ref
 from edtr_amd.testing import ACC_F32, GELU_APPROX, LIPSCHITZ, block_rel, geglu_err, geglu_slack, rounded_operand, unit_roundoff
 
 pytestmark = pytest.mark.gpu
@@ -140,18 +141,11 @@ def attn_elem(got, q, k, v, scale, dtype, out_dtype=None, causal=False):
 def norm_elem(got, x, gamma, beta, eps, dtype, silu=False):
     """Element bound of a normalisation of x's LAST axis (reshape groups there): (x - mean) rstd gamma + beta (+ SiLU) in fp64;
     the fp32 statistics add, per the reduction of k = x.shape[-1] terms, |dmean| rstd + |x - mean| rstd |drstd / rstd| <=
-    k 2^-24 rstd (E|x| + |x - mean| rstd^2 E[x^2]) (times |gamma|) — in the k 2^-22 absref form with absref below."""
-    xd = x.double().cpu()
-    g = gamma.double().cpu()
-    b = beta.double().cpu()
-    mu = xd.mean(-1, keepdim=True)
-    rstd = 1.0 / (xd.var(-1, unbiased=False, keepdim=True) + eps).sqrt()
-    ref = (xd - mu) * rstd * g + b
-    absref = g.abs() * rstd * (xd.abs().mean(-1, keepdim=True) + (xd - mu).abs() * rstd ** 2 * (xd * xd).mean(-1, keepdim=True)) + b.abs()
-    if silu:
-        ref, absref = F.silu(ref), LIPSCHITZ["silu"] * absref
-    r = elem(got, ref, absref, dtype, xd.shape[-1])
-    if xd.shape[-1] > 4096:
+    k 2^-24 rstd (E|x| + |x - mean| rstd^2 E[x^2]) (times |gamma|) — in the k 2^-22 absref form with the absref of
+    tests/glue16_reference.py norm_ref, where the formula is written out."""
+    ref, absref = norm_ref(x, gamma, beta, eps, silu)
+    r = elem(got, ref, absref, dtype, x.shape[-1])
+    if x.shape[-1] > 4096:
         # LIMITATION: at these reduction lengths the worst-case k 2^-22 term dominates the output ulp and the element bound only
         # catches errors of ~10 %.  The per-block check adds what it misses: every element is within u |ref| of the reference once
         # rounded, so each 32 x 32 block's relative L2 error is <= u; 1.25 u leaves a quarter of an ulp to the statistics.
