@@ -401,7 +401,7 @@ int edtr_window_attn(const edtr_window_attn_params* p, edtr_stream_t stream);
  *            pre[u] = rstd (acc[u] - mean c1[u]) + c2b[u]   — the folded LayerNorm of edtr_igemm's ln_stats, with the row
  *            statistics taken inside the kernel from the x rows it already holds
  *   b2     : fp32 [C] fc2 bias (pad entries zero)
- *   out    : [rows][ldo] 16-bit (may not alias x)
+ *   out    : [rows][ldo] 16-bit (may be x itself: a workgroup reads only the rows it writes, and has read them all before its first store)
  *   row_stats : optional fp32 [rows][C/32][2], the (sum, sum of squares) slots of the stored output rows in edtr_igemm's
  *            row_stats format (slots 0 and 3 carry the sums of columns 0..95 / 96..191, the others are zero), for the
  *            LayerNorm folded into the next layer's qkv projection.

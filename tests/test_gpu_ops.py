@@ -16,7 +16,11 @@ also sit in NaN-filled buffers with guard rows and columns (guarded / check_guar
 attention cases at the launch geometry of a batch-8 run (test_flash_attn64_launch_geometry and its neighbours) guard every operand
 and the output that way (HostileAttn) and assert edtr_flash_attn64_plan's answer before they launch.  igemm's z-batched launches
 (Z > 1 on every tile, zdiv > 1), its wide operands (the 64-bit-address form of tile 3), tile 14 against fp64 and split-K on tiles 8 /
-14 or with empty trailing splits live in tests/test_gpu_igemm_cells.py (case table: tests/igemm_cells.py), under the same two gates."""
+14 or with empty trailing splits live in tests/test_gpu_igemm_cells.py (case table: tests/igemm_cells.py), under the same two gates.
+The six MFMA kernels of csrc/swin.hip run here in the friendly layout only; their references live in tests/swin_cases.py, and
+tests/test_gpu_swin_edges.py launches them into guarded buffers with hostile strides at the smallest shape that reaches each branch
+(persistent-loop rounds, thin shifts, head width 32, row-count edges, rejections); tests/test_swin_edges_cpu.py shows on the CPU
+which defects those checks reject."""
 import math
 
 import pytest
@@ -24,7 +28,9 @@ import torch
 import torch.nn.functional as F
 
 import attn_cases
+import swin_cases as SC
 from glue16_reference import norm_ref
+from swin_cases import conv_ref, gn_apply16
 from edtr_amd.testing import ACC_F32, GELU_APPROX, LIPSCHITZ, block_rel, geglu_err, geglu_slack, rounded_operand, unit_roundoff
 
 pytestmark = pytest.mark.gpu
@@ -75,7 +81,7 @@ BLOCK = {}         # test id -> worst per-block relative L2 error (composite lau
 # Per-block tolerance of the one composite launch whose roundings the element bound cannot follow (the swin attention half: its
 # 16-bit P feeds a softmax inside a window): 1.5 x the worst 32 x 32 block measured on the MI355X (value in the comment).
 BLOCK_TOL = {                     # family: (bf16, fp16)
-    "swin_attn": (3.0e-3, 3.7e-4),    # measured 1.98e-3 / 2.47e-4 against the mirrored reference (16-bit weights, q / k / v and O)
+    "swin_attn": SC.BLOCK_TOL_SWIN_ATTN,    # (3.0e-3, 3.7e-4): measured 1.98e-3 / 2.47e-4 against the mirrored reference (16-bit weights, q / k / v and O)
 }
 
 
@@ -101,13 +107,6 @@ def gemm_ref(a, w, bias=None, res=None, alpha=1.0, rowvec=None):
             t = t.double().cpu()
             ref, absref = ref + t, absref + t.abs()
     return ref, absref
-
-
-def conv_ref(x, w, bias=None, **kw):
-    """fp64 conv2d and conv2d(|x|, |w|) + |bias| (NCHW)."""
-    xd, wd = x.double().cpu(), w.double().cpu()
-    b = None if bias is None else bias.double().cpu()
-    return F.conv2d(xd, wd, b, **kw), F.conv2d(xd.abs(), wd.abs(), None if b is None else b.abs(), **kw)
 
 
 def guarded(M, N, dtype, d, rows=3, cols=8):
@@ -166,19 +165,6 @@ def ln_rows16(x, n, dtype, eps=1e-5):
     v16, flip = rounded_operand(xn, dv, dtype)
     pad = x.shape[1] - n
     return F.pad(v16, (0, pad)), F.pad(flip, (0, pad))
-
-
-def gn_apply16(x, scale, shift, dtype, silu=True):
-    """x * scale + shift (+ SiLU) from an exact fp32 (scale, shift) table, rounded to 16 bits as edtr_gn_apply stores it (the fused
-    forms round it the same way before their product): fp64 mirror and flip spacing for the fp32 fma (2^-23 (|x scale| + |shift|))
-    and SiLU's exp2 / rcp (2^-22 |silu|)."""
-    xd, sc, sh = x.double().cpu(), scale.double().cpu(), shift.double().cpu()
-    y = xd * sc + sh
-    dv = 2.0 ** -23 * ((xd * sc).abs() + sh.abs())
-    if silu:
-        y = F.silu(y)
-        dv = LIPSCHITZ["silu"] * dv + 2.0 ** -22 * y.abs()
-    return rounded_operand(y, dv, dtype)
 
 
 def rnd(shape, seed, scale=1.0):
@@ -1208,40 +1194,13 @@ def test_gemm_leaky_relu_epilogue(dtype, tile):
         ops.launch(p_bad)
 
 
-def _window_attn_reference(qkv, table_bias, H, W, heads, d, shift):
-    """plain torch fp32 restatement of model/swinir.py:254-279 + :120-148 without the two linears: qkv [B, H, W, 3, heads, d]."""
-    from edtr_amd.model import swinir as S
-    B = qkv.shape[0]
-    C = heads * d
-    h = qkv.reshape(B, H, W, 3 * C)
-    if shift:
-        h = torch.roll(h, (-shift, -shift), (1, 2))
-    win = h.reshape(B, H // 8, 8, W // 8, 8, 3 * C).permute(0, 1, 3, 2, 4, 5).reshape(-1, 64, 3, heads, d)
-    q, k, v = win.permute(2, 0, 3, 1, 4)
-    att = (q * d ** -0.5) @ k.transpose(-1, -2) + table_bias
-    if shift:
-        m = torch.from_numpy(S.shift_mask(H, W, 8, shift))
-        att = (att.reshape(B, -1, heads, 64, 64) + m[None, :, None]).reshape(-1, heads, 64, 64)
-    o = (torch.softmax(att, -1) @ v).transpose(1, 2).reshape(B, H // 8, W // 8, 8, 8, C).permute(0, 1, 3, 2, 4, 5).reshape(B, H, W, C)
-    return torch.roll(o, (shift, shift), (1, 2)) if shift else o
+_window_attn_reference = SC.window_attn_reference         # (the references of the six swin.hip kernels live in tests/swin_cases.py)
 
 
 def _window_elem(got, qkv, bias, H, W, heads, d, shift, scale, dtype):
-    """Element bound of the windowed attention (attn_elem's terms; _window_attn_reference in fp64 gives P V, and with |V| in
-    place of V gives P|V|).  The logit term uses each query's bound delta_i = d 2^-22 scale |q_i|_1 max|k| for all its keys,
-    which moves the output by at most 2 delta_i P|V|."""
-    q64 = qkv.double()
-    ref = _window_attn_reference(q64, bias.double(), H, W, heads, d, shift)
-    vabs = q64.clone()
-    vabs[..., 2, :, :] = vabs[..., 2, :, :].abs()
-    pv = _window_attn_reference(vabs, bias.double(), H, W, heads, d, shift)
-    C = heads * d
-    qn = q64[..., 0, :, :].abs().sum(-1, keepdim=True)                                 # [B, H, W, heads, 1]
-    delta = d * 2.0 ** -22 * scale * qn * float(q64[..., 1, :, :].abs().max())
-    delta = delta.expand(*qn.shape[:-1], d).reshape(*ref.shape)
-    rows = got.shape[0]
-    extra = {"16-bit P before P V": 2.0 * unit_roundoff(dtype) * pv.reshape(rows, C), "fp32 logits": (2.0 * delta * pv).reshape(rows, C)}
-    return elem(got, ref.reshape(rows, C), pv.reshape(rows, C), dtype, 64, extra)
+    """Element bound of the windowed attention: swin_cases.window_elem's (ref, absref, k, extra)."""
+    ref, pv, k, extra = SC.window_elem(qkv, bias, H, W, heads, d, shift, scale, dtype)
+    return elem(got, ref, pv, dtype, k, extra)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -1253,14 +1212,10 @@ def test_window_attention(dtype, B, H, W, heads, d, cp, shift):
     from edtr_amd.model import swinir as S
     ops = _ops()
     dv = dev()
-    qkv = (rnd((B, H, W, 3, heads, d), 170) * 1.5).to(dtype)
-    table = rnd((225, heads), 171, 0.7)
-    bias = S.expand_bias(table, 8)
-    packed = torch.zeros((B * H * W, 3, heads, 32), dtype=dtype)
-    packed[..., :d] = qkv.reshape(B * H * W, 3, heads, d)
+    qkv, bias = SC.window_qkv(B, H, W, heads, d, dtype)
     out = torch.full((B * H * W, cp), float("nan"), dtype=dtype, device=dv)
     lab = torch.from_numpy(S.region_labels(H, W, 8, shift)).to(dv) if shift else None
-    ops.launch(ops.make_window_attn(dtype=dtype, qkv=packed.reshape(B * H * W, -1).to(dv), ld_qkv=3 * heads * 32, out=out, ld_out=cp,
+    ops.launch(ops.make_window_attn(dtype=dtype, qkv=SC.pack_window_qkv(qkv).to(dv), ld_qkv=3 * heads * 32, out=out, ld_out=cp,
                                     B=B, H=H, W=W, heads=heads, head_dim=d, c_pad=cp, shift=shift, bias=bias.to(dv), labels=lab,
                                     scale=d ** -0.5))
     torch.cuda.synchronize()
@@ -1282,10 +1237,7 @@ def test_conv64_persistent(dtype, B, H, W, ups, cout, nchw):
     from edtr_amd import lib as L
     d = dev()
     SH, SW = (H // 2, W // 2) if ups else (H, W)
-    x = rnd((B, SH, SW, 64), 210, 1.2).to(dtype)
-    w = rnd((cout, 64, 3, 3), 211, 1 / math.sqrt(576))
-    bias = torch.zeros(64)
-    bias[:cout] = 0.3 * rnd((cout,), 212)
+    x, w, bias = SC.conv64_operands(B, SH, SW, cout, dtype)
     img = ops.pack_conv64_weight(w, dtype)
     alpha, slope = (0.7, 0.0) if nchw else (1.0, 0.2)
     if nchw:
@@ -1296,24 +1248,17 @@ def test_conv64_persistent(dtype, B, H, W, ups, cout, nchw):
                                act=L.ACT_NONE if nchw else L.ACT_LRELU, act_slope=slope, alpha=alpha, ldo=0 if nchw else 64, out_nchw_f32=nchw,
                                n_valid=cout if nchw else 0))
     torch.cuda.synchronize()
-    xin = x.float().permute(0, 3, 1, 2)
-    if ups:
-        xin = F.interpolate(xin, scale_factor=2, mode="nearest")
-    ref = alpha * F.conv2d(xin, w.to(dtype).float(), None, padding=1) + bias[:cout, None, None]
+    act_slope = None if nchw else slope
+    ref = SC.conv64_plain(x, w, bias, dtype, alpha, act_slope, ups)
     if nchw:
         got = out.cpu()
     else:
-        ref = F.leaky_relu(ref, slope)
         got = out.float().cpu().reshape(B, H, W, 64).permute(0, 3, 1, 2)
         assert float(got[:, cout:].abs().max()) == 0.0 if cout < 64 else True
         got = got[:, :cout]
     assert torch.isfinite(got).all()
     assert rel(got, ref) < TOL[dtype]
-    r64, a64 = conv_ref(xin, w.to(dtype).float(), None, padding=1)
-    bd = bias[:cout, None, None].double()
-    r64, a64 = alpha * r64 + bd, abs(alpha) * a64 + bd.abs()
-    if not nchw:
-        r64 = F.leaky_relu(r64, slope)
+    r64, a64 = SC.conv64_reference(x, w, bias, dtype, alpha, act_slope, ups)
     elem(got, r64, a64, torch.float32 if nchw else dtype, 576)
 
 
@@ -1325,11 +1270,8 @@ def test_conv128_out_one_launch(dtype, B, H, W, gn):
     ops = _ops()
     d = dev()
     HW = H * W
-    x = (rnd((B * HW, 128), 240, 1.3) + 0.3).to(dtype)
-    w = rnd((3, 128, 3, 3), 241, 1 / math.sqrt(1152))
-    bias = torch.zeros(32)
-    bias[:3] = 0.3 * rnd((3,), 242)
-    gamma, beta = (1 + 0.2 * rnd((128,), 243)).to(d), (0.2 * rnd((128,), 244)).to(d)
+    x, w, bias, gamma, beta = SC.conv128_operands(B, HW, dtype)
+    gamma, beta = gamma.to(d), beta.to(d)
     xd = x.to(d)
     table = None
     if gn:
@@ -1343,22 +1285,12 @@ def test_conv128_out_one_launch(dtype, B, H, W, gn):
     ops.launch(ops.make_conv128_out(dtype=dtype, x=xd, ldx=128, w=ops.pack_conv128_out_weight(w, dtype).to(d), bias=bias.to(d), out=out, B=B, H=H, W=W,
                                     n_valid=3, gn_table=table, alpha=0.9))
     torch.cuda.synchronize()
-    xin = x.float().reshape(B, H, W, 128).permute(0, 3, 1, 2)
-    if gn:
-        xin = F.silu(F.group_norm(xin, 32, gamma.cpu(), beta.cpu(), 1e-6)).to(dtype).float()      # (the kernel rounds the normalised operand to 16 bits)
-    ref = 0.9 * F.conv2d(xin, w.to(dtype).float(), None, padding=1) + bias[:3, None, None]
+    ref = SC.conv128_plain(x, w, bias, dtype, gamma.cpu() if gn else None, beta.cpu(), 0.9, B, H, W)
     assert torch.isfinite(out).all()
     assert rel(out.cpu(), ref) < TOL[dtype]
-    r64, a64 = conv_ref(xin, w.to(dtype).float(), None, padding=1)
-    bd = bias[:3, None, None].double()
-    extra = None
-    if gn:      # swin.hip:1079-1109: GroupNorm apply + SiLU from the table, packed to 16 bits in place before the product: mirrored
-        tb = table.cpu()
-        xg, flip = gn_apply16(x.float().reshape(B, HW, 128), tb[:, None, :, 0], tb[:, None, :, 1], dtype)
-        xg, flip = (t.reshape(B, H, W, 128).permute(0, 3, 1, 2) for t in (xg, flip))
-        r64, a64 = conv_ref(xg, w.to(dtype).float(), None, padding=1)
-        extra = {"16-bit normalised operand, boundary values": 0.9 * F.conv2d(flip, w.to(dtype).double().abs(), None, padding=1)}
-    elem(out, 0.9 * r64 + bd, 0.9 * a64 + bd.abs(), torch.float32, 1152, extra)
+    # with a table: GroupNorm apply + SiLU from it, packed to 16 bits in place before the product (swin.hip:1079-1109), mirrored
+    r64, a64, extra = SC.conv128_reference(x, w, bias, dtype, table, 0.9, B, H, W)
+    elem(out, r64, a64, torch.float32, 1152, extra)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -1371,56 +1303,24 @@ def test_swin_attention_half_one_launch(dtype, B, H, W, shift):
     from edtr_amd.model import swinir as S
     ops = _ops()
     dv = dev()
-    heads, d, C, CP = 6, 30, 180, ops.SWIN_MLP_C
+    d, C, CP = 30, 180, ops.SWIN_MLP_C
     rows = B * H * W
-    x = torch.zeros((rows, CP))
-    x[:, :C] = rnd((rows, C), 200, 1.5) + 0.3
-    x = x.to(dtype)
-    gamma, beta = 1 + 0.2 * rnd((C,), 201), 0.3 * rnd((C,), 202)
-    wqkv, bqkv = rnd((3 * C, C), 203, 1.5 / math.sqrt(C)), 0.2 * rnd((3 * C,), 204)
-    wp, bp = rnd((C, C), 205, 1 / math.sqrt(C)), 0.2 * rnd((C,), 206)
-    table = rnd((225, heads), 207, 0.7)
-    bias = S.expand_bias(table, 8)
-    # packing exactly as model/swinir.py does it
-    wq32, bq32 = S.pack_qkv(wqkv, bqkv, heads, CP)                  # [(s, h, e), CP] with zero pad rows / columns
-    g_pad, b_pad = torch.zeros(CP), torch.zeros(CP)
-    g_pad[:C], b_pad[:C] = gamma, beta
-    scale = torch.ones(3 * heads * 32)
-    scale[: heads * 32] = d ** -0.5
-    wg = wq32 * g_pad[None, :] * scale[:, None]
-    c2b = ((wq32 @ b_pad) + bq32) * scale
-    wpp = torch.zeros((CP, heads, 32))
-    wpp[:C, :, :d] = wp.reshape(C, heads, d)
-    img_qkv, img_proj = ops.pack_swin_attn_weights(wg, wpp.reshape(CP, heads * 32), dtype)
-    c1 = wg.to(dtype).float().sum(1).contiguous()
-    bpp = torch.zeros(CP)
-    bpp[:C] = bp
+    x = SC.attn_rows(rows, C, dtype)
+    P = SC.attn_operands(dtype, C)                                  # packed exactly as model/swinir.py does it
+    img_qkv, img_proj = ops.pack_swin_attn_weights(P["wg"], P["wpp"], dtype)
     out = torch.full((rows, CP), float("nan"), dtype=dtype, device=dv)
     lab = torch.from_numpy(S.region_labels(H, W, 8, shift)).to(dv) if shift else None
     ops.launch(ops.make_swin_attn(dtype=dtype, x=x.to(dv), ldx=CP, out=out, ldo=CP, B=B, H=H, W=W, head_dim=d, shift=shift, c_valid=C, eps=1e-5,
-                                  wqkv=img_qkv.to(dv), wproj=img_proj.to(dv), c1=c1.to(dv), c2b=c2b.contiguous().to(dv), bproj=bpp.to(dv),
-                                  bias=ops.swin_attn_bias(bias).to(dv), labels=lab))
+                                  wqkv=img_qkv.to(dv), wproj=img_proj.to(dv), c1=P["c1"].to(dv), c2b=P["c2b"].to(dv), bproj=P["bpp"].to(dv),
+                                  bias=ops.swin_attn_bias(P["bias"]).to(dv), labels=lab))
     torch.cuda.synchronize()
-    xf = x.float()[:, :C]
-    qkv = F.layer_norm(xf, (C,), gamma, beta, 1e-5) @ wqkv.t() + bqkv
-    att = _window_attn_reference(qkv.reshape(B, H, W, 3, heads, d), bias, H, W, heads, d, shift).reshape(rows, C)
-    ref = xf + att @ wp.t() + bp
+    ref = SC.attn_reference(x, P, B, H, W, shift)
     got = out.float().cpu()
     assert torch.isfinite(got).all()
     assert rel(got[:, :C], ref) < TOL[dtype]
-    # per-block check against a reference that mirrors the kernel's roundings: the 16-bit weights it reads (gamma and the q scale in
-    # wg, beta and the qkv bias in c2b, the padded proj), LayerNorm folded into the raw rows (swin.hip:643-658), q / k / v packed to
-    # 16 bits (swin.hip:665-705), O packed to 16 bits before proj (swin.hip:759-773).  The 16-bit P (swin.hip:754) is not mirrored:
-    # its rounding, like the flips of the other roundings, is what the tolerance carries.
-    xd = x.double()
-    mu = xd[:, :C].mean(1, keepdim=True)
-    rstd = 1.0 / ((xd[:, :C] ** 2).mean(1, keepdim=True) - mu * mu + 1e-5).sqrt()
-    q16 = (rstd * (xd @ wg.to(dtype).double().t() - mu * c1.double()) + c2b.double()).to(dtype).double()
-    q16 = q16.reshape(rows, 3, heads, 32)[..., :d].clone()
-    q16[:, 0] /= d ** -0.5                                           # (_window_attn_reference applies the scale itself)
-    att16 = _window_attn_reference(q16.reshape(B, H, W, 3, heads, d), bias.double(), H, W, heads, d, shift).reshape(rows, C).to(dtype).double()
-    wp16 = wpp.to(dtype).double()[:C].reshape(C, heads, 32)[..., :d].reshape(C, C)
-    block(got[:, :C], xd[:, :C] + att16 @ wp16.t() + bp.double(), C, "swin_attn", dtype)
+    # per-block check against the reference that mirrors the kernel's roundings (swin_cases.attn_mirror: 16-bit weights, q / k / v and
+    # O); the 16-bit P is not mirrored: its rounding, like the flips of the other roundings, is what the tolerance carries.
+    block(got[:, :C], SC.attn_mirror(x, P, B, H, W, shift, dtype), C, "swin_attn", dtype)
     assert float(got[:, C:].abs().max()) == 0.0
 
 
@@ -1485,50 +1385,22 @@ def test_swin_mlp_one_launch(dtype, rows):
     next layer's folded LayerNorm are those of the stored values."""
     ops = _ops()
     d = dev()
-    C, HID, CP, HP = 180, 360, ops.SWIN_MLP_C, ops.SWIN_MLP_HIDDEN
-    x = torch.zeros((rows, CP))
-    x[:, :C] = rnd((rows, C), 190, 1.5) + 0.4
-    x = x.to(dtype)
-    gamma, beta = 1 + 0.2 * rnd((C,), 191), 0.3 * rnd((C,), 192)
-    w1, b1 = rnd((HID, C), 193, 1 / math.sqrt(C)), 0.2 * rnd((HID,), 194)
-    w2, b2 = rnd((C, HID), 195, 1 / math.sqrt(HID)), 0.2 * rnd((C,), 196)
-    w1g = torch.zeros((HP, CP))
-    w1g[:HID, :C] = w1 * gamma[None, :]
-    w2p = torch.zeros((CP, HP))
-    w2p[:C, :HID] = w2
-    img1, img2 = ops.pack_swin_mlp_weights(w1g, w2p, dtype)
-    c1 = w1g.to(dtype).float().sum(1).contiguous()
-    c2b = torch.zeros(HP)
-    c2b[:HID] = w1 @ beta + b1
-    b2p = torch.zeros(CP)
-    b2p[:C] = b2
+    C, CP = 180, ops.SWIN_MLP_C
+    x = SC.mlp_rows(rows, C, dtype)
+    P = SC.mlp_operands(dtype, C, 360)
+    img1, img2 = ops.pack_swin_mlp_weights(P["w1g"], P["w2p"], dtype)
     out = torch.full((rows, CP), float("nan"), dtype=dtype, device=d)
     stats = torch.full((rows, CP // 32, 2), float("nan"), dtype=torch.float32, device=d)
-    ops.launch(ops.make_swin_mlp(dtype=dtype, x=x.to(d), ldx=CP, rows=rows, c_valid=C, eps=1e-5, w1=img1.to(d), w2=img2.to(d), c1=c1.to(d),
-                                 c2b=c2b.to(d), b2=b2p.to(d), out=out, ldo=CP, row_stats=stats))
+    ops.launch(ops.make_swin_mlp(dtype=dtype, x=x.to(d), ldx=CP, rows=rows, c_valid=C, eps=1e-5, w1=img1.to(d), w2=img2.to(d), c1=P["c1"].to(d),
+                                 c2b=P["c2b"].to(d), b2=P["b2p"].to(d), out=out, ldo=CP, row_stats=stats))
     torch.cuda.synchronize()
-    xf = x.float()[:, :C]
-    h = F.gelu(F.layer_norm(xf, (C,), gamma, beta, 1e-5) @ w1.t() + b1)
-    ref = xf + h @ w2.t() + b2
+    ref = SC.mlp_reference(x, P)
     got = out.float().cpu()
     assert torch.isfinite(got).all()
     assert rel(got[:, :C], ref) < TOL[dtype]
-    # element bound on a reference that mirrors the kernel: LayerNorm folded into the first product over the RAW rows (swin.hip:
-    # 306-324, one-pass statistics: pre = rstd (acc - mean c1) + c2b), GELU, the hidden units packed to 16 bits (swin.hip:390), the
-    # second product over the 16-bit W2, + b2 + x, one rounding.  Hidden values whose fp32 error bound reaches a 16-bit rounding
-    # boundary may land one spacing away (rounded_operand), propagated through |W2|.
-    W1, W2 = w1g.to(dtype).double(), w2p.to(dtype).double()
-    xd = x.double()
-    mu = xd[:, :C].mean(1, keepdim=True)
-    ex2 = (xd[:, :C] ** 2).mean(1, keepdim=True)
-    rstd = 1.0 / (ex2 - mu * mu + 1e-5).sqrt()
-    cen = xd @ W1.t() - mu * c1.double()
-    pre = rstd * cen + c2b.double()
-    epre = C * ACC_F32 * (rstd * (xd.abs() @ W1.abs().t() + mu.abs() * c1.double().abs() + cen.abs() * rstd ** 2 * ex2) + c2b.double().abs())
-    g16, flip = rounded_operand(F.gelu(pre), LIPSCHITZ["gelu"] * epre + GELU_APPROX * pre.abs(), dtype)
-    ref64 = xd + g16 @ W2.t() + b2p.double()
-    abs64 = xd.abs() + g16.abs() @ W2.abs().t() + b2p.double().abs()
-    elem(got[:, :C], ref64[:, :C], abs64[:, :C], dtype, HP, {"16-bit hidden units, boundary values": (flip @ W2.abs().t())[:, :C]})
+    # element bound on the reference that mirrors the kernel (swin_cases.mlp_mirror: folded one-pass LayerNorm, 16-bit hidden units)
+    ref64, abs64, k, extra = SC.mlp_mirror(x, P, dtype)
+    elem(got[:, :C], ref64, abs64, dtype, k, extra)
     assert float(got[:, C:].abs().max()) == 0.0
     tot = stats.double().sum(1).cpu()
     st = out.double().cpu()
