@@ -264,6 +264,16 @@ struct RoiArgs {
     float canonical_scale, canonical_level;
 };
 
+// LevelMapper: the level of a roi, the ONE expression the forward and the backward's pre-pass both evaluate
+__device__ __forceinline__ int roi_level(const RoiLevels& t, f32x4 box, float canonical_scale, float canonical_level) {
+    if (t.n <= 1) return 0;
+    const float s = sqrtf(mul_rn(add_rn(box.z, -box.x), add_rn(box.w, -box.y)));
+    const float k = floorf(add_rn(add_rn(canonical_level, log2f(div_rn(s, canonical_scale))), 1e-6f));
+    const float lo = (float)t.k_min, hi = (float)t.k_max;
+    const int l = (int)(!(k >= lo) ? lo : (k > hi ? hi : k)) - t.k_min;   // (NaN and -inf: the finest level)
+    return clamp_index(l, t.n);
+}
+
 // One tap position of one axis: start + ph bin and the offset of sample i inside the bin, then roi_align's bilinear_interpolate for
 // that axis.  low < 0 marks a sample outside [-1, extent], which adds nothing (a NaN coordinate is outside).
 __device__ __forceinline__ void roi_tap(float start, float bin, int ph, int i, int S, int extent, int& low, int& high, float& l, float& h) {
@@ -293,14 +303,7 @@ __global__ void __launch_bounds__(256) roi_align_kernel(RoiLevels t, RoiArgs a) 
     const int tid = (int)threadIdx.x, P = a.P, S = a.S, PS = P * S, PP = P * P;
     const int64_t roi = blockIdx.x;
     const f32x4 box = *reinterpret_cast<const f32x4*>(a.rois + 4 * roi);
-    int l = 0;
-    if (t.n > 1) {
-        const float s = sqrtf(mul_rn(add_rn(box.z, -box.x), add_rn(box.w, -box.y)));
-        const float k = floorf(add_rn(add_rn(a.canonical_level, log2f(div_rn(s, a.canonical_scale))), 1e-6f));
-        const float lo = (float)t.k_min, hi = (float)t.k_max;
-        l = (int)(!(k >= lo) ? lo : (k > hi ? hi : k)) - t.k_min;         // (NaN and -inf: the finest level)
-        l = clamp_index(l, t.n);
-    }
+    const int l = roi_level(t, box, a.canonical_scale, a.canonical_level);
     const int H = t.H[l], W = t.W[l];
     const float scale = t.scale[l];
     if (tid < PS) {
@@ -339,6 +342,190 @@ __global__ void __launch_bounds__(256) roi_align_kernel(RoiLevels t, RoiArgs a) 
             }
         }
         a.out[(roi * a.C + c0 + c) * PP + r] = div_rn(sum, count);
+    }
+}
+
+// ---- RoIAlign's backward -----------------------------------------------------------------------------------------------------------
+// The gradient is GATHERED: a workgroup owns a 16 x 16 tile of one level of one image and kBwdChunk channels, and adds to it the
+// contribution of every roi that reaches it in k order; no word has two writers and no sum depends on timing.
+
+constexpr int kBwdMaxP = 16;            // EDTR_ROI_BWD_MAX_P
+constexpr int kBwdChunk = 32;           // EDTR_ROI_BWD_CHUNK: channels whose sums a lane holds in registers
+constexpr int kBwdStride = kBwdChunk + 4;   // floats between two bins of the staged g': 16-byte aligned rows; a staging wave writes 8 banks
+constexpr int kRecHead = 8;             // words of a record before its taps: level, image, ymin, ymax, xmin, xmax, 0, 0
+
+struct RoiBwdArgs {
+    const float* rois;          // [K][4]
+    const int32_t* batch;       // [K], not decreasing
+    const float* grad;          // [K][C][P][P]
+    int32_t* ws;                // image_start [N + 1] (padded to 4 words), then K records of kRecHead + 8 P S words
+    void* out[kMaxLevels];      // [N][C][H_l][W_l]
+    int64_t tile_start[kMaxLevels + 1];
+    int tiles_x[kMaxLevels];
+    int N, C, K, P, S, rec0;
+    float canonical_scale, canonical_level;
+};
+
+inline int64_t bwd_image_words(int N) { return ((int64_t)N + 1 + 3) / 4 * 4; }
+inline int64_t bwd_record_words(int P, int S) { return kRecHead + 8 * (int64_t)P * S; }
+
+// Workgroup k of 128 lanes: lanes 0 .. P S - 1 the rows' taps and lanes 64 .. 64 + P S - 1 the columns', as the forward works them
+// out; lane 0 then the footprint of the valid ones and image_start[n] = the first roi of image n (for the n that begin at k).
+__global__ void __launch_bounds__(128) roi_backward_records_kernel(RoiLevels t, RoiBwdArgs a) {
+    __shared__ int lo[2][kMaxTaps], hi[2][kMaxTaps];
+    const int tid = (int)threadIdx.x, P = a.P, S = a.S, PS = P * S, k = (int)blockIdx.x;
+    const f32x4 box = *reinterpret_cast<const f32x4*>(a.rois + 4 * (int64_t)k);
+    const int l = roi_level(t, box, a.canonical_scale, a.canonical_level);
+    int32_t* rec = a.ws + a.rec0 + (int64_t)k * (kRecHead + 8 * PS);
+    const int axis = tid >> 6, i = tid & 63;            // axis 0: rows (y), axis 1: columns (x)
+    if (i < PS) {
+        const float scale = t.scale[l];
+        const float p1 = mul_rn(axis ? box.x : box.y, scale), p2 = mul_rn(axis ? box.z : box.w, scale);
+        const float ext = add_rn(p2, -p1), size = ext < 1.0f ? 1.0f : ext;
+        int low, high;
+        float wl, wh;
+        roi_tap(p1, div_rn(size, (float)P), i / S, i % S, S, axis ? t.W[l] : t.H[l], low, high, wl, wh);
+        lo[axis][i] = low, hi[axis][i] = high;
+        int4 w;
+        w.x = low, w.y = high, w.z = __float_as_int(wl), w.w = __float_as_int(wh);
+        *reinterpret_cast<int4*>(rec + kRecHead + 4 * (axis * PS + i)) = w;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int ymin = kLimit, ymax = -1, xmin = kLimit, xmax = -1;
+        for (int j = 0; j < PS; ++j) {
+            if (lo[0][j] >= 0) ymin = lo[0][j] < ymin ? lo[0][j] : ymin, ymax = hi[0][j] > ymax ? hi[0][j] : ymax;
+            if (lo[1][j] >= 0) xmin = lo[1][j] < xmin ? lo[1][j] : xmin, xmax = hi[1][j] > xmax ? hi[1][j] : xmax;
+        }
+        if (ymax < 0 || xmax < 0) ymin = xmin = 1, ymax = xmax = 0;     // no valid sample: the empty footprint
+        const int b = clamp_index(a.batch[k], a.N);
+        int4 h0, h1;
+        h0.x = l, h0.y = b, h0.z = ymin, h0.w = ymax, h1.x = xmin, h1.y = xmax, h1.z = h1.w = 0;
+        *reinterpret_cast<int4*>(rec) = h0, *reinterpret_cast<int4*>(rec + 4) = h1;
+        const int prev = k > 0 ? clamp_index(a.batch[k - 1], a.N) : -1;
+        for (int n = prev + 1; n <= b; ++n) a.ws[n] = k;
+        if (k == a.K - 1)
+            for (int n = b + 1; n <= a.N; ++n) a.ws[n] = a.K;
+    }
+}
+
+template <int DT>
+__device__ __forceinline__ void store_rounded(void* base, int64_t i, float v) {
+    if (DT == EDTR_LOGITS_F32) static_cast<float*>(base)[i] = v;
+    else static_cast<uint16_t*>(base)[i] = DT == EDTR_LOGITS_F16 ? F16::from_f32(v) : BF16::from_f32(v);
+}
+
+// Workgroup (tile of a level, chunk of channels, image) of 256 lanes, lane -> pixel (ty, tx) = (tid / 16, tid % 16) of the tile.
+//   keep     the image's rois 256 per round: those of this level whose footprint meets the tile, by an ordered ballot compaction, so
+//            `kept` holds them k ascending;
+//   weights  per kept roi a[ph] of the tile's 16 rows and b[pw] of its 16 columns, one lane each, into LDS: a wave (4 rows) reads 4
+//            consecutive words of `wa` and 16 of `wb`, each a broadcast within its lanes;
+//   stage    g' = grad / (S S) of the chunk as gs[bin][channel]: the gather reads the 32 channels of a bin as eight 16-byte words at
+//            ONE address for the whole wave (a broadcast, no bank conflict);
+//   gather   t[c] over pw, contrib[c] over ph, acc[c] += contrib[c]: 3 x 32 sums in registers.  A zero weight skips its term: the
+//            pixels of a tile that a roi does not reach cost a compare.
+// The tile's 16 x 16 x chunk results are stored once at the end, per channel four 64-byte (fp32) row segments per wave.
+template <int DT>
+__global__ void __launch_bounds__(256) roi_backward_gather_kernel(RoiLevels t, RoiBwdArgs a) {
+    __shared__ __attribute__((aligned(16))) float gs[kBwdMaxP * kBwdMaxP * kBwdStride];
+    __shared__ float wa[kBwdMaxP][16], wb[kBwdMaxP][16];
+    __shared__ int kept[256];
+    __shared__ int wsum[4];
+    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63, ty = tid >> 4, tx = tid & 15;
+    const int P = a.P, S = a.S, PS = P * S, PP = P * P;
+    int l = 0;
+    while (l + 1 < t.n && (int64_t)blockIdx.x >= a.tile_start[l + 1]) ++l;
+    const int tile = (int)((int64_t)blockIdx.x - a.tile_start[l]), tile_y = tile / a.tiles_x[l], tile_x = tile - tile_y * a.tiles_x[l];
+    const int H = t.H[l], W = t.W[l], y0 = tile_y * 16, x0 = tile_x * 16;
+    const int n = (int)blockIdx.z, c0 = (int)blockIdx.y * kBwdChunk, cn = a.C - c0 < kBwdChunk ? a.C - c0 : kBwdChunk;
+    int kb = a.ws[n], ke = a.ws[n + 1];
+    kb = kb < 0 ? 0 : (kb > a.K ? a.K : kb), ke = ke < kb ? kb : (ke > a.K ? a.K : ke);
+    const int rec_words = kRecHead + 8 * PS;
+    const int32_t* recs = a.ws + a.rec0;
+    const float count = (float)(S * S);
+
+    float acc[kBwdChunk];
+#pragma unroll
+    for (int c = 0; c < kBwdChunk; ++c) acc[c] = 0.0f;
+
+    for (int k0 = kb; k0 < ke; k0 += 256) {
+        const int k = k0 + tid;
+        bool flag = false;
+        if (k < ke) {
+            const int32_t* rec = recs + (int64_t)k * rec_words;
+            const int4 h0 = *reinterpret_cast<const int4*>(rec), h1 = *reinterpret_cast<const int4*>(rec + 4);
+            flag = h0.x == l && h0.y == n && h0.z <= y0 + 15 && h0.w >= y0 && h1.x <= x0 + 15 && h1.y >= x0;
+        }
+        const uint64_t vote = __ballot(flag);
+        __syncthreads();                        // the list and the sums of the round before have been read
+        if (lane == 0) wsum[wave] = __popcll(vote);
+        __syncthreads();
+        int pos = __popcll(vote & lanes_below(lane));
+        for (int w = 0; w < wave; ++w) pos += wsum[w];
+        if (flag) kept[pos] = k;
+        const int total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        for (int j = 0; j < total; ++j) {
+            __syncthreads();                    // the list is written; gs, wa and wb of the roi before have been read
+            const int kk = kept[j];
+            const int32_t* rec = recs + (int64_t)kk * rec_words;
+            if (tid < 16 * P) {
+                const int ph = tid >> 4, r = tid & 15;
+                float wy = 0.0f, wx = 0.0f;
+                for (int i = 0; i < S; ++i) {
+                    const int4 yt = *reinterpret_cast<const int4*>(rec + kRecHead + 4 * (ph * S + i));
+                    const int4 xt = *reinterpret_cast<const int4*>(rec + kRecHead + 4 * (PS + ph * S + i));
+                    if (yt.x >= 0) {
+                        if (yt.x == y0 + r) wy = add_rn(wy, __int_as_float(yt.w));
+                        if (yt.y == y0 + r) wy = add_rn(wy, __int_as_float(yt.z));
+                    }
+                    if (xt.x >= 0) {
+                        if (xt.x == x0 + r) wx = add_rn(wx, __int_as_float(xt.w));
+                        if (xt.y == x0 + r) wx = add_rn(wx, __int_as_float(xt.z));
+                    }
+                }
+                wa[ph][r] = wy, wb[ph][r] = wx;
+            }
+            const float* g = a.grad + ((int64_t)kk * a.C + c0) * PP;
+            for (int e = tid; e < kBwdChunk * PP; e += 256) {
+                const int c = e / PP, r = e - c * PP;
+                gs[r * kBwdStride + c] = c < cn ? div_rn(g[e], count) : 0.0f;
+            }
+            __syncthreads();
+            float contrib[kBwdChunk];
+#pragma unroll
+            for (int c = 0; c < kBwdChunk; ++c) contrib[c] = 0.0f;
+            for (int ph = 0; ph < P; ++ph) {
+                const float wy = wa[ph][ty];
+                if (wy == 0.0f) continue;
+                float ts[kBwdChunk];
+#pragma unroll
+                for (int c = 0; c < kBwdChunk; ++c) ts[c] = 0.0f;
+                for (int pw = 0; pw < P; ++pw) {
+                    const float wx = wb[pw][tx];
+                    if (wx == 0.0f) continue;
+                    const f32x4* g4 = reinterpret_cast<const f32x4*>(gs + (ph * P + pw) * kBwdStride);
+#pragma unroll
+                    for (int q = 0; q < kBwdChunk / 4; ++q) {
+                        const f32x4 v = g4[q];
+                        ts[4 * q] = add_rn(ts[4 * q], mul_rn(wx, v.x)), ts[4 * q + 1] = add_rn(ts[4 * q + 1], mul_rn(wx, v.y));
+                        ts[4 * q + 2] = add_rn(ts[4 * q + 2], mul_rn(wx, v.z)), ts[4 * q + 3] = add_rn(ts[4 * q + 3], mul_rn(wx, v.w));
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < kBwdChunk; ++c) contrib[c] = add_rn(contrib[c], mul_rn(wy, ts[c]));
+            }
+#pragma unroll
+            for (int c = 0; c < kBwdChunk; ++c) acc[c] = add_rn(acc[c], contrib[c]);
+        }
+    }
+
+    const int y = y0 + ty, x = x0 + tx;
+    if (y < H && x < W) {
+        const int64_t HW = (int64_t)H * W, base = ((int64_t)n * a.C + c0) * HW + (int64_t)y * W + x;
+        void* out = a.out[l];
+#pragma unroll
+        for (int c = 0; c < kBwdChunk; ++c)
+            if (c < cn) store_rounded<DT>(out, base + c * HW, acc[c]);
     }
 }
 
@@ -472,6 +659,60 @@ extern "C" int edtr_roi_align(int dtype, const void* const* features_host, const
     if (dtype == EDTR_LOGITS_F32) hipLaunchKernelGGL(roi_align_kernel<EDTR_LOGITS_F32>, grid, block, 0, st, t, a);
     else if (dtype == EDTR_LOGITS_F16) hipLaunchKernelGGL(roi_align_kernel<EDTR_LOGITS_F16>, grid, block, 0, st, t, a);
     else hipLaunchKernelGGL(roi_align_kernel<EDTR_LOGITS_BF16>, grid, block, 0, st, t, a);
+    EDTR_LAUNCH_CHECK();
+    return EDTR_OK;
+}
+
+extern "C" int64_t edtr_roi_align_backward_workspace(int N, int K, int P, int S) {
+    if (N <= 0 || K <= 0 || P <= 0 || S <= 0 || (int64_t)P * S > kMaxTaps) return 0;
+    return 4 * (bwd_image_words(N) + (int64_t)K * bwd_record_words(P, S));
+}
+
+extern "C" int edtr_roi_align_backward(int dtype, void* const* grads_out_host, const int32_t* level_hw_host, const float* scales_host, int L,
+                                       int N, int C, const float* rois, const int32_t* batch_index, int K, int P, int S, int k_min, int k_max,
+                                       float canonical_scale, float canonical_level, const float* grad, void* workspace,
+                                       int64_t workspace_bytes, edtr_stream_t stream) {
+    static_assert(kBwdMaxP == EDTR_ROI_BWD_MAX_P && kBwdChunk == EDTR_ROI_BWD_CHUNK, "edtr_hip.h and rois.hip disagree on a cap");
+    static_assert(kBwdMaxP * 16 <= 256 && kBwdChunk % 4 == 0, "one lane per (bin, row) of a tile; the staged channels are read four at a time");
+    if (!grads_out_host || !level_hw_host || !scales_host || !rois || !batch_index || !grad || !workspace) return EDTR_E_NULL;
+    if (L <= 0 || N <= 0 || C <= 0 || K <= 0 || P <= 0 || S <= 0 || k_max < k_min || !(canonical_scale > 0.0f)) return EDTR_E_SHAPE;
+    if (L > kMaxLevels || N > 65535 || (int64_t)P * S > kMaxTaps || (C + kRoiChunk - 1) / kRoiChunk > 65535 || C >= kLimit) return EDTR_E_UNSUPPORTED;
+    if (P > kBwdMaxP || (C + kBwdChunk - 1) / kBwdChunk > 65535) return EDTR_E_UNSUPPORTED;
+    if (L > 1 && k_max - k_min != L - 1) return EDTR_E_SHAPE;
+    if (!known_dtype(dtype)) return EDTR_E_DTYPE;
+    RoiLevels t;
+    RoiBwdArgs a;
+    t.n = L, t.k_min = k_min, t.k_max = k_max;
+    int64_t tiles = 0;
+    for (int l = 0; l < kMaxLevels; ++l) {
+        const bool have = l < L;
+        t.H[l] = have ? level_hw_host[2 * l] : 1, t.W[l] = have ? level_hw_host[2 * l + 1] : 1;
+        t.scale[l] = have ? scales_host[l] : 1.0f, t.feat[l] = nullptr;
+        a.out[l] = have ? grads_out_host[l] : nullptr;
+        a.tile_start[l] = tiles, a.tiles_x[l] = 1;
+        if (!have) continue;
+        if (!a.out[l]) return EDTR_E_NULL;
+        if (t.H[l] <= 0 || t.W[l] <= 0 || !(t.scale[l] > 0.0f)) return EDTR_E_SHAPE;
+        if (t.H[l] >= kLimit || t.W[l] >= kLimit) return EDTR_E_UNSUPPORTED;
+        if (!aligned_to(a.out[l], dtype == EDTR_LOGITS_F32 ? 4 : 2)) return EDTR_E_ALIGN;
+        a.tiles_x[l] = (t.W[l] + 15) / 16;
+        tiles += (int64_t)a.tiles_x[l] * ((t.H[l] + 15) / 16);
+        if (tiles >= ((int64_t)1 << 31)) return EDTR_E_UNSUPPORTED;
+    }
+    a.tile_start[kMaxLevels] = tiles;
+    for (int l = L; l < kMaxLevels; ++l) a.tile_start[l] = tiles;
+    if (!aligned_to(rois, 16) || !aligned_to(batch_index, 4) || !aligned_to(grad, 4) || !aligned_to(workspace, 16)) return EDTR_E_ALIGN;
+    if (workspace_bytes < edtr_roi_align_backward_workspace(N, K, P, S)) return EDTR_E_SHAPE;
+    a.rois = rois, a.batch = batch_index, a.grad = grad, a.ws = static_cast<int32_t*>(workspace);
+    a.N = N, a.C = C, a.K = K, a.P = P, a.S = S, a.rec0 = (int)bwd_image_words(N);
+    a.canonical_scale = canonical_scale, a.canonical_level = canonical_level;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(roi_backward_records_kernel, dim3((unsigned)K), dim3(128), 0, st, t, a);
+    EDTR_LAUNCH_CHECK();
+    const dim3 grid((unsigned)tiles, (unsigned)((C + kBwdChunk - 1) / kBwdChunk), (unsigned)N), block(256);
+    if (dtype == EDTR_LOGITS_F32) hipLaunchKernelGGL(roi_backward_gather_kernel<EDTR_LOGITS_F32>, grid, block, 0, st, t, a);
+    else if (dtype == EDTR_LOGITS_F16) hipLaunchKernelGGL(roi_backward_gather_kernel<EDTR_LOGITS_F16>, grid, block, 0, st, t, a);
+    else hipLaunchKernelGGL(roi_backward_gather_kernel<EDTR_LOGITS_BF16>, grid, block, 0, st, t, a);
     EDTR_LAUNCH_CHECK();
     return EDTR_OK;
 }

@@ -255,22 +255,35 @@ class DetectorTransform:
         return result
 
 
-def assemble_features(backbone, transform: Optional[DetectorTransform] = None, autocast_dtype=None):
+def assemble_features(backbone, transform: Optional[DetectorTransform] = None, autocast_dtype=None, grad: bool = False):
     """The ``features_fn`` that `rois.assemble_detector` takes, from the learned ``backbone`` (backbone + FPN: a torch module from the
     batch to an ordered mapping of feature levels, or to one tensor) alone: `DetectorTransform.batch`, then the backbone under
     no_grad (and under `torch.autocast` of ``autocast_dtype``, if given).  ``transform``: default the reference detector's 800 / 1333
-    with the ImageNet constants.  Returns (batch, image_sizes, original_sizes, features)."""
+    with the ImageNet constants.  Returns (batch, image_sizes, original_sizes, features).
+
+    ``grad`` = True is the form `rois.assemble_training_detector` takes: the backbone runs in the caller's grad mode, so a loss can
+    reach it, and ``features_fn(images, targets)`` sends the targets' boxes through `DetectorTransform.__call__` and returns them,
+    resized to the batch, as a fifth value."""
     prepare = transform if transform is not None else DetectorTransform(800, 1333, IMAGENET_MEAN, IMAGENET_STD)
 
-    def features_fn(images):
+    def features_fn(images, targets=None):
         import contextlib
         import torch
-        batch, image_sizes, original_sizes = prepare.batch(images)
+        if targets is not None and not grad:
+            raise TypeError("features_fn takes targets only when it was assembled with grad=True")
+        resized = None
+        if targets is None:
+            batch, image_sizes, original_sizes = prepare.batch(images)
+        else:
+            original_sizes = [(int(v.shape[-2]), int(v.shape[-1])) for v in _image_list(images)]
+            (batch, image_sizes), resized = prepare(images, targets)
         cast = torch.autocast("cuda", dtype=autocast_dtype) if autocast_dtype is not None else contextlib.nullcontext()
-        with torch.no_grad(), cast:
+        with contextlib.nullcontext() if grad else torch.no_grad(), cast:
             features = backbone(batch)
         if isinstance(features, torch.Tensor):
             features = OrderedDict([("0", features)])
-        return batch, image_sizes, original_sizes, features
+        if resized is None:
+            return batch, image_sizes, original_sizes, features
+        return batch, image_sizes, original_sizes, features, resized
 
     return features_fn

@@ -1211,6 +1211,30 @@ def make_roi_align(*, features, scales, rois, batch_index, out, sampling_ratio: 
     return Rec(L.load().edtr_roi_align, args, keep, name, 9.0 * out.numel() * int(sampling_ratio) ** 2, nbytes)
 
 
+def roi_align_backward_workspace(N: int, K: int, P: int, S: int) -> int:
+    """bytes of the workspace `make_roi_align_backward` takes (edtr_hip.h `edtr_roi_align_backward_workspace`)"""
+    return int(L.load().edtr_roi_align_backward_workspace(int(N), int(K), int(P), int(S)))
+
+
+def make_roi_align_backward(*, grad, grads_out, scales, rois, batch_index, workspace, sampling_ratio: int, k_min: int, k_max: int,
+                            canonical_scale: float, canonical_level: float, name="rois.roi_align_backward") -> Rec:
+    """``grads_out`` (a list of contiguous [N, C, H, W] tensors of one dtype, every word written) = the gradient of `make_roi_align`
+    with respect to its features for the fp32 ``grad`` [K, C, P, P]: the launch pair of edtr_hip.h `edtr_roi_align_backward`.
+    ``workspace``: a uint8 device tensor of `roi_align_backward_workspace` bytes; ``batch_index`` must not decrease."""
+    dt, ptrs = _one_dtype(grads_out, "grads_out"), _pointer_table(grads_out)
+    hw = [int(v) for f in grads_out for v in f.shape[-2:]]
+    hw_host, sc_host = (ct.c_int32 * len(hw))(*hw), (ct.c_float * len(grads_out))(*[float(v) for v in scales])
+    N, C = grads_out[0].shape[:2]
+    K, P = grad.shape[0], grad.shape[-1]
+    if grad.dtype != torch.float32 or tuple(grad.shape) != (K, C, P, P):
+        raise TypeError(f"grad is fp32 [K, {C}, P, P], got {grad.dtype} {tuple(grad.shape)}")
+    args = (dt, ptrs, hw_host, sc_host, len(grads_out), N, C, ptr(rois), ptr(batch_index), K, P, int(sampling_ratio), int(k_min), int(k_max),
+            float(canonical_scale), float(canonical_level), ptr(grad), ptr(workspace), int(workspace.numel()))
+    keep = (ptrs, hw_host, sc_host, tuple(grads_out), rois, batch_index, grad, workspace)
+    nbytes = 4.0 * grad.numel() + sum(float(f.element_size() * f.numel()) for f in grads_out)
+    return Rec(L.load().edtr_roi_align_backward, args, keep, name, 4.0 * grad.numel() * P * P, nbytes)
+
+
 # -- the detector's input transform (edtr_hip.h "Detector input"; the caller and the host restatement are edtr_amd/detinput.py) ---------
 def make_det_transform(*, descs_host, descs, mean: Sequence[float], std: Sequence[float], batch, keep=(), name="detinput.transform") -> Rec:
     """Every image of a ragged list normalised, resized and padded into its slot of ``batch`` [N, C, H, W] (fp32 / fp16 / bf16) in one

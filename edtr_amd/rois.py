@@ -5,9 +5,13 @@ pools every proposal from the feature level its size selects.  The reference imp
 (model/faster_rcnn.py:9), which do not exist on this stack.  With them a user can put the detector together from its learned parts —
 backbone + FPN, `RPNHead`, box head and predictor, all plain torch and all outside this project — and this project's launches:
 `proposals` and `roi_align` here, `boxes.detections` and `boxes.resize_boxes`; `assemble_detector` does exactly that.
+`roi_align` is differentiable in its features (`roi_align_backward`, a deterministic gather: one writer per word, a fixed summation
+order, no atomics), so `assemble_training_detector` puts the same parts together for the reference's "Train detnet" step
+(main/det/train_edtr.py:203-241) with `targets`' launches and losses.
 
 Three layers, as in `boxes`, `coco` and `cls`:
-  * `anchors`, `rpn_select`, `rpn_candidates`, `proposals`, `roi_align`, `assemble_detector`: thin wrappers over the launches of
+  * `anchors`, `rpn_select`, `rpn_candidates`, `proposals`, `roi_align`, `roi_align_backward`, `assemble_detector`,
+    `assemble_training_detector`: thin wrappers over the launches of
     include/edtr_hip.h "Region proposals and RoI pooling" (kernels in csrc/rois.hip; torch tensors on the device, the caller's stream);
   * `*_reference`: the numpy restatement of each.  They are the NORMATIVE definition: the kernels are tested against them — by equality
     wherever neither `exp` (decoding, sigmoid) nor `log2` (the level of a roi) enters — and they against the reference's own
@@ -38,6 +42,7 @@ from .boxes import BBOX_XFORM_CLIP, F32
 RPN_MAX_LEVELS = 8                      # EDTR_RPN_MAX_LEVELS: with RPN_MAX_PRE_NMS per level the NMS sees at most NMS_MAX_BOXES boxes
 RPN_MAX_PRE_NMS = 4096                  # EDTR_RPN_MAX_PRE_NMS: the selection of one level is ranked in LDS
 ROI_MAX_TAPS = 64                       # EDTR_ROI_MAX_TAPS: output_size * sampling_ratio
+ROI_BWD_MAX_P = 16                      # EDTR_ROI_BWD_MAX_P: output_size of the backward (a chunk's staged gradient must fit the LDS)
 LIMIT = 1 << 24
 # fasterrcnn_resnet50_fpn_v2 (configs/det/demo.yaml:88-92): one size and three aspect ratios on each of five levels
 RPN_SIZES = ((32,), (64,), (128,), (256,), (512,))
@@ -361,6 +366,85 @@ def roi_align_reference(features, rois, image_sizes, output_size: int = 7, sampl
     return out
 
 
+def _axis_weights(taps, extent: int) -> np.ndarray:
+    """a[k][y][ph] of `roi_align_backward_reference` for one axis from its `_taps`: fp32 [K, extent, P]"""
+    valid, low, high, l, h = taps
+    K, P, S = valid.shape
+    a = np.zeros((K, extent, P), dtype=F32)
+    kk, pp = np.arange(K)[:, None], np.arange(P)[None, :]
+    for i in range(S):                                                  # (k, ph) differ between the elements of one indexed sum
+        ok = valid[:, :, i]
+        a[kk, low[:, :, i], pp] = (a[kk, low[:, :, i], pp] + np.where(ok, h[:, :, i], F32(0))).astype(F32)
+        a[kk, high[:, :, i], pp] = (a[kk, high[:, :, i], pp] + np.where(ok, l[:, :, i], F32(0))).astype(F32)
+    return a
+
+
+def roi_align_backward_reference(grad, feature_shapes, rois, image_sizes, output_size: int = 7, sampling_ratio: int = 2,
+                                 canonical_scale: float = 224.0, canonical_level: float = 4.0, dtype: str = "float32") -> list:
+    """The gradient of `roi_align_reference` with respect to its features, THE RULE of `roi_align_backward`.  ``grad``: fp32
+    [sum k_i, C, P, P]; ``feature_shapes``: per level (N, C, H_l, W_l); returns one fp32 array of that shape per level.  The boxes get
+    no gradient, as in torchvision.  For roi k the level, the image, the scaled box and the per-axis tap tables (valid, low, high, l, h
+    of the P S positions) are the forward's, by `_taps`.  Every step is one rounded fp32 operation, nothing contracted:
+      * g'[c][ph][pw] = grad[k][c][ph][pw] / (S S);
+      * a[y][ph]: from +0, for iy = 0 .. S - 1 in order, if tap (ph, iy) is valid: + hy if y_low == y, then + ly if y_high == y (at
+        the clamped edge low == high and both are added: l = 0 and h = 1 there); b[x][pw] alike on the other axis;
+      * t[ph] = sum_pw b[x][pw] g'[c][ph][pw], pw ascending from +0; contrib_k[c][y][x] = sum_ph a[y][ph] t[ph], ph ascending from +0;
+      * out_l[n][c][y][x] = sum_k contrib_k over the rois of image n on level l, k ascending from +0.0; ``dtype`` "float16" /
+        "bfloat16" rounds that fp32 sum ONCE, to nearest even (and the array holds the rounded values, widened).
+    This is the exact adjoint of `roi_align_reference` in real arithmetic: weights and validity are both separable there.  A term
+    whose a or b is exactly zero may be skipped (the device does): a zero times a finite number is a zero, and no sum that starts at
+    +0 changes by one, so for finite gradients not a bit differs.  A non-finite ``grad`` is unspecified.  A level, image or pixel that
+    no roi touches is +0.0."""
+    from . import labels
+    P, S = _check_pool(output_size, sampling_ratio)
+    shapes = [tuple(int(v) for v in s) for s in _level_list(feature_shapes)]
+    if not 0 < len(shapes) <= RPN_MAX_LEVELS or any(len(s) != 4 or s[:2] != shapes[0][:2] for s in shapes):
+        raise ValueError("feature_shapes are (N, C, H_l, W_l) per level with one N and one C, for 1 to 8 levels")
+    N, C = shapes[0][:2]
+    if len(rois) != N or len(image_sizes) != N or not 0 < N <= 65535:
+        raise ValueError(f"{N} images in the features (1 to 65535), {len(rois)} lists of rois and {len(image_sizes)} image sizes")
+    boxes = np.concatenate([np.asarray(_host(r), dtype=F32).reshape(-1, 4) for r in rois])
+    batch = np.concatenate([np.full(int(np.asarray(_host(r)).reshape(-1, 4).shape[0]), n, dtype=np.int64) for n, r in enumerate(rois)])
+    K = boxes.shape[0]
+    grad = _host(grad)
+    if grad.shape != (K, C, P, P):
+        raise ValueError(f"grad is [{K}, {C}, {P}, {P}], got {grad.shape}")
+    if dtype not in ("float32", "float16", "bfloat16"):
+        raise ValueError(f"dtype is float32, float16 or bfloat16, got {dtype!r}")
+    out = [np.zeros(s, dtype=F32) for s in shapes]
+    if K:
+        scales, k_min, k_max = level_scales([s[-2:] for s in shapes], image_sizes)
+        levels = roi_levels_reference(boxes, k_min, k_max, canonical_scale, canonical_level) if len(shapes) > 1 else np.zeros(K, dtype=np.int64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            gp = (grad / F32(S * S)).astype(F32)
+    for l, (_, _, H, W) in enumerate(shapes):
+        pick = np.nonzero(levels == l)[0] if K else np.zeros(0, dtype=np.int64)
+        if not pick.size:
+            continue
+        with np.errstate(invalid="ignore", over="ignore"):
+            b = (boxes[pick] * F32(scales[l])).astype(F32)
+            ew, eh = b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]
+            roi_w, roi_h = np.where(ew < 1, F32(1), ew), np.where(eh < 1, F32(1), eh)
+            ay = _axis_weights(_taps(b[:, 1], (roi_h / F32(P)).astype(F32), P, S, H), H)
+            bx = _axis_weights(_taps(b[:, 0], (roi_w / F32(P)).astype(F32), P, S, W), W)
+        for j, k in enumerate(pick):                                    # k ascending: the order of the sum over rois
+            ys, xs = np.nonzero(ay[j].any(axis=1))[0], np.nonzero(bx[j].any(axis=1))[0]
+            if not ys.size or not xs.size:
+                continue
+            ys, xs = np.arange(ys[0], ys[-1] + 1), np.arange(xs[0], xs[-1] + 1)    # zero rows inside add +0: no bit changes
+            a, bb, g = ay[j][ys], bx[j][xs], gp[k]
+            with np.errstate(invalid="ignore", over="ignore"):
+                t = np.zeros((C, P, xs.size), dtype=F32)
+                for pw in range(P):
+                    t = (t + (bb[None, None, :, pw] * g[:, :, pw, None]).astype(F32)).astype(F32)
+                contrib = np.zeros((C, ys.size, xs.size), dtype=F32)
+                for ph in range(P):
+                    contrib = (contrib + (a[None, :, ph, None] * t[:, ph, None, :]).astype(F32)).astype(F32)
+                view = out[l][batch[k], :, ys[0]:ys[-1] + 1, xs[0]:xs[-1] + 1]
+                view[...] = (view + contrib).astype(F32)
+    return [labels._round_to(o, dtype) for o in out]
+
+
 def _np_image(v) -> np.ndarray:
     return v.detach().float().cpu().numpy() if hasattr(v, "detach") else np.asarray(v, dtype=F32)
 
@@ -430,6 +514,97 @@ def assemble_detector_reference(features_fn, rpn_head, box_head, box_predictor, 
         return out
 
     return detnet
+
+
+LOSS_NAMES = ("loss_classifier", "loss_box_reg", "loss_objectness", "loss_rpn_box_reg")     # model/faster_rcnn.py:1295-1296, 2221-2226
+
+
+def _training_options(kw: dict) -> dict:
+    from .targets import ROI_WEIGHTS
+    opts = dict(sizes=RPN_SIZES, aspect_ratios=RPN_ASPECT_RATIOS, rpn_pre_nms_top_n=2000, rpn_post_nms_top_n=2000, rpn_nms_thresh=0.7,
+                rpn_score_thresh=0.0, rpn_min_size=1e-3, rpn_fg_iou_thresh=0.7, rpn_bg_iou_thresh=0.3, rpn_batch_size_per_image=256,
+                rpn_positive_fraction=0.5, box_fg_iou_thresh=0.5, box_bg_iou_thresh=0.5, box_batch_size_per_image=512, box_positive_fraction=0.25,
+                bbox_reg_weights=ROI_WEIGHTS, output_size=7, sampling_ratio=2, canonical_scale=224.0, canonical_level=4.0, featmap_names=None)
+    unknown = set(kw) - set(opts)
+    if unknown:
+        raise TypeError(f"assemble_training_detector takes no {sorted(unknown)}; its thresholds are {sorted(opts)}")
+    opts.update(kw)
+    return opts
+
+
+def flatten_head_outputs(objectness, bbox_deltas):
+    """`concat_box_prediction_layers` (model/faster_rcnn.py:2231-2260) by permute / reshape: per level [N, A, H, W] and [N, 4 A, H, W]
+    -> ([N sum H W A], [N sum H W A, 4]) in the anchors' order, level after level and (y, x, a) inside one.  Torch tensors, any
+    device; autograd passes through."""
+    import torch
+    obj, deltas = [], []
+    for o, d in zip(objectness, bbox_deltas):
+        N, A, H, W = o.shape
+        obj.append(o.permute(0, 2, 3, 1).reshape(N, -1))
+        deltas.append(d.view(N, A, 4, H, W).permute(0, 3, 4, 1, 2).reshape(N, -1, 4))
+    return torch.cat(obj, dim=1).reshape(-1), torch.cat(deltas, dim=1).reshape(-1, 4)
+
+
+def assemble_training_detector_reference(features_fn, rpn_head, box_head, box_predictor, source, replay: Optional[dict] = None,
+                                         trace: Optional[dict] = None, loss_dtype=None, **thresholds):
+    """`assemble_training_detector` through the restatements on the host, in the manner of `assemble_detector_reference`: returns
+    ``train_step(images, targets, draw) -> (losses, features)``.  With ``replay`` (the ``trace`` of a device step) no learned part is
+    called: their recorded outputs — "features", "objectness", "bbox_deltas", "class_logits", "box_regression" — the resized
+    "targets", "batch_shape", "image_sizes" AND the device's "proposals" take their place (decoding uses exp, which numpy rounds
+    differently, so the proposals must be the device's), and every non-learned training step — anchors, both matchings, both samples,
+    both encodings, RoIAlign — is restated from exactly what the device's step was given.  Without ``replay`` the four parts are called
+    with CPU tensors and the proposals are `proposals_reference`'s.  The losses are `targets.rpn_loss` and `targets.fastrcnn_loss` on
+    the host in ``loss_dtype`` (default torch.float64).  ``trace`` receives "proposals", "rpn_targets", "roi_targets", "pooled"."""
+    o = _training_options(thresholds)
+
+    def train_step(images, targets, draw: int = 0):
+        import torch
+        from . import targets as _targets
+        dt = torch.float64 if loss_dtype is None else loss_dtype
+        tr = {} if trace is None else trace
+        if replay is None:
+            batch, image_sizes, _, features, resized = features_fn(images, targets)
+            levels = list(features.values())
+            objectness, deltas = rpn_head(levels)
+            batch_shape = tuple(batch.shape[-2:])
+            with torch.no_grad():
+                props = proposals_reference([v.detach() for v in objectness], [v.detach() for v in deltas], image_sizes, batch_shape, sizes=o["sizes"],
+                                            aspect_ratios=o["aspect_ratios"], pre_nms_top_n=o["rpn_pre_nms_top_n"],
+                                            post_nms_top_n=o["rpn_post_nms_top_n"], nms_thresh=o["rpn_nms_thresh"],
+                                            score_thresh=o["rpn_score_thresh"], min_size=o["rpn_min_size"])
+        else:
+            batch_shape, image_sizes, resized = replay["batch_shape"], replay["image_sizes"], replay["targets"]
+            features, objectness, deltas = replay["features"], replay["objectness"], replay["bbox_deltas"]
+            props = [(_host(b), _host(s)) for b, s in replay["proposals"]]
+        grids = [tuple(int(v) for v in ob.shape[-2:]) for ob in objectness]
+        anchors = anchors_reference(grids, batch_shape, o["sizes"], o["aspect_ratios"])
+        rpn_t = _targets.rpn_targets_reference(anchors, resized, high=o["rpn_fg_iou_thresh"], low=o["rpn_bg_iou_thresh"], allow_low_quality=True,
+                                               batch_size_per_image=o["rpn_batch_size_per_image"], positive_fraction=o["rpn_positive_fraction"],
+                                               source=source, draw=draw, log=_targets.torch_log)
+        roi_t = _targets.roi_targets_reference([b for b, _ in props], resized, high=o["box_fg_iou_thresh"], low=o["box_bg_iou_thresh"],
+                                               allow_low_quality=False, batch_size_per_image=o["box_batch_size_per_image"],
+                                               positive_fraction=o["box_positive_fraction"], weights=o["bbox_reg_weights"], source=source, draw=draw,
+                                               log=_targets.torch_log)
+        pooled_from = [_host(v) for v in _pooled_levels(features, o["featmap_names"])]
+        pooled = roi_align_reference(pooled_from, list(roi_t["proposals"]), image_sizes, o["output_size"], o["sampling_ratio"], o["canonical_scale"],
+                                     o["canonical_level"])
+        if replay is None:
+            logits, regression = box_predictor(box_head(torch.from_numpy(pooled)))
+        else:
+            logits, regression = replay["class_logits"], replay["box_regression"]
+
+        def on_host(v):
+            return v.detach().to("cpu", dt) if hasattr(v, "detach") else torch.from_numpy(np.asarray(v)).to(dt)
+        as_t = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in rpn_t.items()}
+        as_r = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in roi_t.items()}
+        obj_flat, delta_flat = flatten_head_outputs([on_host(v) for v in objectness], [on_host(v) for v in deltas])
+        loss_objectness, loss_rpn_box_reg = _targets.rpn_loss(obj_flat, delta_flat, as_t)
+        loss_classifier, loss_box_reg = _targets.fastrcnn_loss(on_host(logits), on_host(regression), as_r)
+        tr.update(proposals=props, rpn_targets=rpn_t, roi_targets=roi_t, pooled=pooled, anchors=anchors)
+        losses = dict(zip(LOSS_NAMES, (loss_classifier, loss_box_reg, loss_objectness, loss_rpn_box_reg)))
+        return losses, features
+
+    return train_step
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
@@ -565,12 +740,117 @@ def roi_align(features, rois, image_sizes, output_size: int = 7, sampling_ratio:
     out = torch.empty((K, C, P, P), dtype=torch.float32, device=dev)
     if K == 0 or C == 0:
         return out
+    flat, batch = _flat_rois(rois, N, dev)
+
+    def launch(levels):
+        ops.launch(ops.make_roi_align(features=list(levels), scales=scales, rois=flat, batch_index=batch, out=out, sampling_ratio=S, k_min=k_min,
+                                      k_max=k_max, canonical_scale=canonical_scale, canonical_level=canonical_level))
+        return out
+
+    if torch.is_grad_enabled() and any(f.requires_grad for f in feats):
+        if P > ROI_BWD_MAX_P:
+            raise ValueError(f"the backward of roi_align takes output_size up to {ROI_BWD_MAX_P}, got {P}")
+        shapes, dtype = [tuple(f.shape) for f in feats], feats[0].dtype
+
+        def backward(grad):
+            return _roi_backward_launch(grad, shapes, dtype, flat, batch, scales, k_min, k_max, S, canonical_scale, canonical_level)
+
+        return _differentiable_roi_align().apply(launch, backward, *feats)
+    return launch(feats)
+
+
+def _flat_rois(rois, N: int, dev):
+    """the launches' form of per-image lists of rois: (fp32 [K, 4], 16-byte aligned; int32 [K], the image of each roi, not decreasing)"""
+    import torch
     flat = torch.cat([_boxes._f32_on(r, dev, "rois").reshape(-1, 4) for r in rois]).contiguous()
     flat = flat.clone() if flat.data_ptr() % 16 else flat
     batch = torch.repeat_interleave(torch.arange(N, dtype=torch.int32), torch.tensor([int(r.shape[0]) for r in rois])).to(dev)
-    ops.launch(ops.make_roi_align(features=feats, scales=scales, rois=flat, batch_index=batch, out=out, sampling_ratio=S, k_min=k_min,
-                                  k_max=k_max, canonical_scale=canonical_scale, canonical_level=canonical_level))
-    return out
+    return flat, batch
+
+
+_ROI_ALIGN_FUNCTION = None
+
+
+def _differentiable_roi_align():
+    """the autograd.Function behind a `roi_align` whose features require grad (made on first use: this module imports without torch)"""
+    global _ROI_ALIGN_FUNCTION
+    if _ROI_ALIGN_FUNCTION is None:
+        import torch
+        from torch.autograd.function import once_differentiable
+
+        class RoiAlign(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, launch, backward, *levels):
+                ctx.backward_launch = backward
+                return launch(levels)
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, grad):
+                grads = ctx.backward_launch(grad.contiguous().float())
+                return (None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:]))
+
+        _ROI_ALIGN_FUNCTION = RoiAlign
+    return _ROI_ALIGN_FUNCTION
+
+
+def _roi_backward_launch(grad, shapes, dtype, flat, batch, scales, k_min, k_max, S, canonical_scale, canonical_level, out=None):
+    import torch
+    from . import ops
+    N, K, P = shapes[0][0], int(grad.shape[0]), int(grad.shape[-1])
+    dev = grad.device
+    grads = [torch.empty(s, dtype=dtype, device=dev) for s in shapes] if out is None else list(out)
+    workspace = torch.empty(ops.roi_align_backward_workspace(N, K, P, S), dtype=torch.uint8, device=dev)
+    ops.launch(ops.make_roi_align_backward(grad=grad, grads_out=grads, scales=scales, rois=flat, batch_index=batch, workspace=workspace,
+                                           sampling_ratio=S, k_min=k_min, k_max=k_max, canonical_scale=canonical_scale,
+                                           canonical_level=canonical_level))
+    return grads
+
+
+def roi_align_backward(grad, feature_shapes, rois, image_sizes, output_size: int = 7, sampling_ratio: int = 2, canonical_scale: float = 224.0,
+                       canonical_level: float = 4.0, dtype=None, device=None, out=None) -> list:
+    """`roi_align_backward_reference` on the device, a launch pair for all rois and all levels (edtr_hip.h `edtr_roi_align_backward`): a
+    pre-pass writes one record per roi (level, image, footprint, tap tables), then one workgroup per (image, level, 16 x 16 tile,
+    32 channels) gathers the rois that reach it in k order.  No atomics and no memset: two calls give equal bits.  ``grad``: fp32
+    [sum k_i, C, P, P]; ``feature_shapes``: per level (N, C, H_l, W_l); ``dtype``: torch.float32 (default), float16 or bfloat16, the
+    type of the returned per-level list, each sum rounded once.  ``out``: per level a contiguous device tensor of that shape and type
+    to write into (every word is written).  No rois at all, or no channels: zeros, without a launch.  output_size above 16: ValueError."""
+    import torch
+    from .imageio import _device
+    P, S = _check_pool(output_size, sampling_ratio)
+    if P > ROI_BWD_MAX_P:
+        raise ValueError(f"the backward of roi_align takes output_size up to {ROI_BWD_MAX_P}, got {P}")
+    dtype = torch.float32 if dtype is None else dtype
+    if dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(f"dtype is torch.float32, float16 or bfloat16, got {dtype}")
+    shapes = [tuple(int(v) for v in s) for s in _level_list(feature_shapes)]
+    if not 0 < len(shapes) <= RPN_MAX_LEVELS or any(len(s) != 4 or s[:2] != shapes[0][:2] for s in shapes):
+        raise ValueError("feature_shapes are (N, C, H_l, W_l) per level with one N and one C, for 1 to 8 levels")
+    N, C = shapes[0][:2]
+    if len(rois) != N or len(image_sizes) != N or not 0 < N <= 65535:
+        raise ValueError(f"{N} images in the features (1 to 65535), {len(rois)} lists of rois and {len(image_sizes)} image sizes")
+    if any(getattr(r, "ndim", 0) != 2 or r.shape[1] != 4 for r in rois):
+        raise ValueError("rois are [k_i, 4] per image")
+    grad = torch.from_numpy(np.ascontiguousarray(grad)) if isinstance(grad, np.ndarray) else grad
+    if not isinstance(grad, torch.Tensor) or grad.dtype != torch.float32:
+        raise TypeError("grad must be an fp32 array or tensor")
+    dev = grad.device if grad.is_cuda and device is None else _device(device)
+    K = sum(int(r.shape[0]) for r in rois)
+    if tuple(grad.shape) != (K, C, P, P):
+        raise ValueError(f"grad is [{K}, {C}, {P}, {P}], got {tuple(grad.shape)}")
+    if out is not None and (len(out) != len(shapes) or any(not isinstance(o, torch.Tensor) or tuple(o.shape) != s or o.dtype != dtype or
+                                                            o.device != dev or not o.is_contiguous() for o, s in zip(out, shapes))):
+        raise TypeError(f"out takes per level a contiguous {dtype} tensor of the level's shape on {dev}")
+    scales, k_min, k_max = level_scales([s[-2:] for s in shapes], image_sizes)
+    if K == 0 or C == 0:
+        if out is None:
+            return [torch.zeros(s, dtype=dtype, device=dev) for s in shapes]
+        for o in out:
+            o.zero_()
+        return list(out)
+    flat, batch = _flat_rois(rois, N, dev)
+    return _roi_backward_launch(grad.detach().to(dev).contiguous(), shapes, dtype, flat, batch, scales, k_min, k_max, S, canonical_scale,
+                                canonical_level, out)
 
 
 def assemble_detector(features_fn, rpn_head, box_head, box_predictor, trace: Optional[dict] = None, **thresholds):
@@ -621,3 +901,71 @@ def assemble_detector(features_fn, rpn_head, box_head, box_predictor, trace: Opt
         return out
 
     return detnet
+
+
+def assemble_training_detector(features_fn, rpn_head, box_head, box_predictor, source, trace: Optional[dict] = None, **thresholds):
+    """The reference's Faster R-CNN in TRAIN mode from its learned parts and this project's launches, with no compiled extension: what
+    `detnet(res_list + gt_list[bs2:], annot_list)` computes in the "Train detnet" step (main/det/train_edtr.py:228-241).  Returns
+    ``train_step(images, targets, draw) -> (losses, features)``: ``losses`` the four scalars "loss_classifier", "loss_box_reg",
+    "loss_objectness", "loss_rpn_box_reg" with autograd through the box head, the RPN head and — by `roi_align`'s backward — the
+    features; ``features`` the ordered mapping the reference returns with return_feat=True, for the feature-matching loss.
+
+    ``features_fn(images, targets) -> (batch, image_sizes, original_sizes, features, resized targets)`` is
+    `detinput.assemble_features(backbone, transform, grad=True)`; ``rpn_head``, ``box_head`` and ``box_predictor`` as in
+    `assemble_detector`; ``source`` the batch's `rng.NoiseSource` and ``draw`` the training step: the two samples are functions of
+    (seed, image id, draw), so a step repeats bit for bit.  ``targets``: per image {"boxes": [G, 4], "labels": [G]} in the images'
+    own coordinates.  The step:
+      1. features_fn, whose transform resizes the targets' boxes (`DetectorTransform.__call__`);
+      2. rpn_head;
+      3. `proposals` on the DETACHED head outputs under no_grad with the training counts (2000 / 2000);
+      4. `targets.rpn_targets` and `targets.rpn_loss`, the head outputs flattened in `concat_box_prediction_layers`' order;
+      5. `targets.roi_targets` (512 / 0.25; the ground truths join the proposals);
+      6. the differentiable `roi_align` over all N x batch slots: an unfilled slot is the zero box with label -1, which no loss reads,
+         so its gradient is zero;
+      7. box_head, box_predictor, `targets.fastrcnn_loss`.
+    Nothing is copied to the host but what `proposals` itself reads back (the candidate and kept counts); the targets, the pooling and
+    the losses wait for nothing.
+
+    ``thresholds``: sizes, aspect_ratios, rpn_pre_nms_top_n, rpn_post_nms_top_n, rpn_nms_thresh, rpn_score_thresh, rpn_min_size,
+    rpn_fg_iou_thresh = 0.7, rpn_bg_iou_thresh = 0.3, rpn_batch_size_per_image = 256, rpn_positive_fraction = 0.5, box_fg_iou_thresh =
+    box_bg_iou_thresh = 0.5, box_batch_size_per_image = 512, box_positive_fraction = 0.25, bbox_reg_weights = (10, 10, 5, 5),
+    output_size, sampling_ratio, canonical_scale, canonical_level, featmap_names.  ``trace``: a dict that receives every stage of a
+    step (what `assemble_training_detector_reference` replays)."""
+    o = _training_options(thresholds)
+    if source is None:
+        raise ValueError("assemble_training_detector needs the NoiseSource of the batch: the samples are functions of (seed, image id, draw)")
+
+    def train_step(images, targets, draw: int = 0):
+        import torch
+        from . import targets as _targets
+        batch, image_sizes, original_sizes, features, resized = features_fn(images, targets)
+        levels = list(features.values())
+        objectness, deltas = rpn_head(levels)
+        batch_shape = tuple(int(v) for v in batch.shape[-2:])
+        tr = {}
+        with torch.no_grad():
+            props = proposals([v.detach() for v in objectness], [v.detach() for v in deltas], image_sizes, batch_shape, sizes=o["sizes"],
+                              aspect_ratios=o["aspect_ratios"], pre_nms_top_n=o["rpn_pre_nms_top_n"], post_nms_top_n=o["rpn_post_nms_top_n"],
+                              nms_thresh=o["rpn_nms_thresh"], score_thresh=o["rpn_score_thresh"], min_size=o["rpn_min_size"], trace=tr)
+            grids = [tuple(int(v) for v in ob.shape[-2:]) for ob in objectness]
+            rpn_t = _targets.rpn_targets(grids, batch_shape, resized, sizes=o["sizes"], aspect_ratios=o["aspect_ratios"], high=o["rpn_fg_iou_thresh"],
+                                         low=o["rpn_bg_iou_thresh"], allow_low_quality=True, batch_size_per_image=o["rpn_batch_size_per_image"],
+                                         positive_fraction=o["rpn_positive_fraction"], source=source, draw=draw, device=batch.device)
+            roi_t = _targets.roi_targets([b for b, _ in props], resized, high=o["box_fg_iou_thresh"], low=o["box_bg_iou_thresh"],
+                                         allow_low_quality=False, batch_size_per_image=o["box_batch_size_per_image"],
+                                         positive_fraction=o["box_positive_fraction"], weights=o["bbox_reg_weights"], source=source, draw=draw)
+        obj_flat, delta_flat = flatten_head_outputs(objectness, deltas)
+        loss_objectness, loss_rpn_box_reg = _targets.rpn_loss(obj_flat.float(), delta_flat.float(), rpn_t)
+        pooled = roi_align(_pooled_levels(features, o["featmap_names"]), list(roi_t.proposals), image_sizes, o["output_size"], o["sampling_ratio"],
+                           o["canonical_scale"], o["canonical_level"])
+        logits, regression = box_predictor(box_head(pooled))
+        logits, regression = logits.float(), regression.float()
+        loss_classifier, loss_box_reg = _targets.fastrcnn_loss(logits, regression, roi_t)
+        losses = dict(zip(LOSS_NAMES, (loss_classifier, loss_box_reg, loss_objectness, loss_rpn_box_reg)))
+        if trace is not None:
+            trace.update(tr, batch_shape=batch_shape, image_sizes=list(image_sizes), original_sizes=list(original_sizes), targets=resized,
+                         features=features, objectness=objectness, bbox_deltas=deltas, proposals=props, rpn_targets=rpn_t, roi_targets=roi_t,
+                         pooled=pooled, class_logits=logits, box_regression=regression, losses=losses)
+        return losses, features
+
+    return train_step

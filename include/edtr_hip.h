@@ -1314,6 +1314,35 @@ int edtr_rpn_candidates(int dtype, const void* const* objectness_host, const voi
 int edtr_roi_align(int dtype, const void* const* features_host, const int32_t* level_hw_host, const float* scales_host, int L, int N,
                    int C, const float* rois, const int32_t* batch_index, int K, int P, int S, int k_min, int k_max,
                    float canonical_scale, float canonical_level, float* out, edtr_stream_t stream);
+/* The gradient of edtr_roi_align with respect to the features (the boxes get none, as in torchvision), deterministic: no atomics, no
+ * memset, every output word written by one lane, every sum in a fixed order.  grad [K][C][P][P] (fp32) -> grads_out_host: L device
+ * pointers in a HOST array, level l [N][C][H_l][W_l] in fp32 / fp16 / bf16 by dtype; every word of every level is written, +0.0 where no
+ * roi reaches.  The other arguments are edtr_roi_align's; batch_index must not decrease (the rois of an image are one range of k).
+ * For roi k the level, the image, the scaled box and the tap tables (valid, low, high, l, h of the P S positions per axis) are the
+ * forward's, by the same device functions.  Every step below is one rounded fp32 operation, nothing contracted:
+ *   g'[c][ph][pw] = grad[k][c][ph][pw] / (S S);
+ *   a[y][ph]: from +0, for iy = 0 .. S - 1 in order, if tap (ph, iy) is valid: + hy if y_low == y, then + ly if y_high == y (at the
+ *             clamped edge low == high and both are added: l = 0, h = 1 there); b[x][pw] alike on the other axis;
+ *   t[ph] = sum_pw b[x][pw] g'[c][ph][pw], pw ascending from +0;  contrib_k[c][y][x] = sum_ph a[y][ph] t[ph], ph ascending from +0;
+ *   out_l[n][c][y][x] = sum_k contrib_k over the rois of image n on level l, k ascending from +0, rounded ONCE to dtype (nearest even).
+ * A term whose a or b is exactly zero is skipped, which changes no bit for finite gradients; a non-finite grad is unspecified.
+ * Two launches.  Pre-pass, one 128-lane workgroup per roi: its record in the workspace (level, image, the footprint [ymin, ymax] x
+ * [xmin, xmax] of its valid taps, both tap tables) and the first roi of every image.  Gather, one 256-lane workgroup per (image, level,
+ * 16 x 16 pixel tile, EDTR_ROI_BWD_CHUNK channels): walks the image's rois 256 at a time, keeps those of its level whose footprint meets
+ * the tile by an ordered ballot compaction (k ascending), stages g' of the chunk in LDS per kept roi, and every lane accumulates its
+ * pixel's channels in registers.  workspace: 16-byte aligned, at least edtr_roi_align_backward_workspace(N, K, P, S) bytes, read by
+ * nothing afterwards.
+ * Errors: those of edtr_roi_align in its order, and P > EDTR_ROI_BWD_MAX_P (g' of a chunk must fit the LDS), more than 65535 chunks or
+ * 2^31 tiles EDTR_E_UNSUPPORTED; grad not aligned to 4 bytes, workspace to 16 EDTR_E_ALIGN; a workspace too small EDTR_E_SHAPE.
+ * replaces: the backward of torchvision.ops.roi_align (float atomicAdd, not repeatable) under `detnet(...)` + `backward()`,
+ * main/det/train_edtr.py:228-241. */
+#define EDTR_ROI_BWD_MAX_P 16
+#define EDTR_ROI_BWD_CHUNK 32
+int64_t edtr_roi_align_backward_workspace(int N, int K, int P, int S);
+int edtr_roi_align_backward(int dtype, void* const* grads_out_host, const int32_t* level_hw_host, const float* scales_host, int L, int N,
+                            int C, const float* rois, const int32_t* batch_index, int K, int P, int S, int k_min, int k_max,
+                            float canonical_scale, float canonical_level, const float* grad, void* workspace, int64_t workspace_bytes,
+                            edtr_stream_t stream);
 
 /* ---- Detector input: normalise, resize and pad a ragged list of images in one launch (additive to ABI 10) -------------------------
  * GeneralizedRCNNTransform.forward in eval mode (model/faster_rcnn.py:2266-2435) from the point where every extent is known: the
