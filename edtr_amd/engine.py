@@ -14,7 +14,7 @@ import ctypes as ct
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -584,9 +584,10 @@ class Act:
     gn_silu: bool = True
     owns: bool = True
     # emits the ordinary apply launch of that GroupNorm and returns the normalised Act: what Emitter.conv falls back to when the
-    # convolution that receives the deferred Act turns out not to be one the halo tiles take (the decision is conv()'s)
+    # plan of the convolution that receives the deferred Act does not apply it (ConvPlan.gn_in)
     gn_apply: Optional[object] = None
     gn_slot: int = 128                    # rows per slot of ``gnp`` (64: the split-K reducer's statistics of 8 x 8 images, ops.gn_slot_rows)
+    stats_shared: bool = False            # the producer wrote its GroupNorm partials into the caller's shared slot buffer (gnp_into)
 
     @property
     def gn_tiles(self) -> int:
@@ -600,6 +601,32 @@ class Act:
     @property
     def rows(self) -> int:
         return self.B * self.H * self.W
+
+
+class Out(NamedTuple):
+    """What one gemm / lin320 / ffn / add launch produced: the output and the by-products the launch wrote beside it."""
+    t: torch.Tensor
+    gnp: Optional[torch.Tensor] = None        # its own GroupNorm partials (Act.gnp) ...
+    gn_slot: int = 128                        # ... and the rows each of their slots covers
+    row_stats: Optional[torch.Tensor] = None  # per-row statistics for a LayerNorm folded into the next GEMMs (gemm(row_stats=True))
+    stats_shared: bool = False                # the GroupNorm partials went into the caller's shared slot buffer (gnp_into / stats_into)
+
+
+class ConvPlan(NamedTuple):
+    """Everything Emitter.conv decides about one convolution before it emits anything (Emitter.conv_plan).  The promises made before
+    the convolution exists (gn_deferrable, tail_ok) read the same record, so promise and launch cannot disagree."""
+    N: int
+    OH: int
+    OW: int
+    M: int
+    parts: Optional[int]      # parts of the product and operand channels per tap incl. parts (None: asked without the GEMM class
+    Ce: Optional[int]         # ``name``, i.e. for a promise: only a one-part product keeps it, and that one has Ce == C)
+    img8: bool                # the 8 x 8-level halo geometry (ops.choose_splitk)
+    tile: int
+    splitk: int
+    subpix: bool              # a nearest-2x upsample convolution in its sub-pixel form
+    gn_in: bool               # applies the deferred GroupNorm of its input while staging the operand (edtr_hip.h: a_gn)
+    tail_tile: int            # the halo tile that takes the tail candidate's 1x1 convolution as a K tail (<= 0: none does)
 
 
 class Emitter:
@@ -658,11 +685,6 @@ class Emitter:
         # halo tile of that shape takes one.  ``ktail=False``: a fast SECTION of a parity mode (hybrid), whose margin stays as measured;
         # EDTR_KTAIL=0: the A/B switch
         self.ktail = precision == "fast" and bool(ktail) and ops.ktail_enabled()
-        self.last_gnp = None
-        self.last_gn_slot = 128
-        self.last_row_stats = None
-        self.gnp_into_done = False       # did the last gemm / conv write its GroupNorm partials into the caller's shared slot buffer?
-        self.add_stats_done = False      # ... and the last add()
 
     # -- precision plumbing ---------------------------------------------------------------------
     def parts_for(self, name: str, M: int = 0, N: int = 0, K: int = 0) -> int:
@@ -745,24 +767,28 @@ class Emitter:
                 return
 
     # -- multi-part operands --------------------------------------------------------------------
-    def _operand(self, a, rows: int, C: int, parts: int):
-        """(16-bit operand tensor, temporary to free or None, parts actually used) of an fp32 / 16-bit activation or of a
-        ready OpN."""
+    def _operand_form(self, a, C: int, parts: int):
+        """What _operand hands a GEMM for an fp32 / 16-bit activation or a ready OpN, before anything is emitted: (the ready 16-bit
+        tensor, or None where a split launch has to write one; parts actually used; the operand's row stride)."""
         ap = ops.op_parts(parts)          # (parts == ops.PARTS_2W: the weights-exact form reads ONE activation part twice)
         if isinstance(a, OpN):
             if a.C != C or a.parts < ap:
                 raise ValueError(f"operand has {a.parts} part(s) of {a.C} columns, the GEMM wants {ap} of {C}")
-            return a.t, None, parts
+            return a.t, parts, a.t.stride(0)
         if a.dtype == self.dtype:
             # already the MFMA operand type (mixed mode: an fp16 attention / GEGLU output): its low part is exactly zero, so
             # more activation parts buy nothing — the one-part product (or the weights-exact one)
-            return a, None, (parts if parts == ops.PARTS_2W else 1)
-        if ap == 1:
-            m = self.mirror_view(a)       # the producer's epilogue already wrote the fp16 copy
-            if m is not None:
-                return m, None, parts
-        t = self.arena.alloc((rows, ap * C), self.dtype)
-        self.prog.add(ops.make_split_operand(src=a, rows=rows, C=C, dst=t, fmt=self.op_fmt(ap)))
+            return a, (parts if parts == ops.PARTS_2W else 1), a.stride(0)
+        m = self.mirror_view(a) if ap == 1 else None      # the producer's epilogue already wrote the fp16 copy
+        return m, parts, (m.stride(0) if m is not None else ap * C)
+
+    def _operand(self, a, rows: int, C: int, parts: int):
+        """(16-bit operand tensor, temporary to free or None, parts actually used): _operand_form, with the split launch emitted."""
+        t, parts, ld = self._operand_form(a, C, parts)
+        if t is not None:
+            return t, None, parts
+        t = self.arena.alloc((rows, ld), self.dtype)
+        self.prog.add(ops.make_split_operand(src=a, rows=rows, C=C, dst=t, fmt=self.op_fmt(ops.op_parts(parts))))
         return t, t, parts
 
     def to16(self, x: torch.Tensor, rows: int, C: int, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
@@ -808,16 +834,15 @@ class Emitter:
 
     def lin320(self, x: torch.Tensor, rows: int, N: int, names, biases=None, *, ln_prefix: Optional[str] = None, alpha: float = 1.0,
                residual: Optional[torch.Tensor] = None, gn_table: Optional[torch.Tensor] = None, rows_per_image: int = 0,
-               name: str = "lin320") -> torch.Tensor:
+               name: str = "lin320") -> Out:
         """out = alpha LayerNorm?(x) W^T + bias (+ residual) on raw 16-bit rows (edtr_lin320: the rows live in registers, the LayerNorm is
         applied there — no normalisation launch, no normalised tensor)."""
-        self.last_gnp, self.last_row_stats, self.gnp_into_done = None, None, False
         w, cvec = self.store.lin320(names, biases, ln_prefix, alpha)
         out = self.new(rows, N)
         self.prog.add(ops.make_lin320(dtype=self.dtype, x=x, ldx=x.stride(0), M=rows, N=N, w=w, cvec=cvec, alpha=alpha, ln=ln_prefix is not None,
                                       eps=1e-5, residual=residual, ldr=residual.stride(0) if residual is not None else 0, out=out,
                                       ldo=out.stride(0), gn_table=gn_table, rows_per_image=rows_per_image, name=name))
-        return out
+        return Out(out)
 
     def qkv_lin320(self, x: torch.Tensor, names, *, B: int, N: int, C: int, ln_prefix: str, alpha: float, name: str = "attn1.qkv"):
         """qkv_gemm on the RAW rows with norm1 applied in the launch's registers (edtr_lin320 with its transposed V part): (qk [B*N, 2C]
@@ -830,41 +855,52 @@ class Emitter:
                                       ldo=2 * C, vt_out=vt, vt_col0=2 * C, vt_ld=N, vt_alpha=1.0, rows_per_image=N, name=name))
         return qk, vt, N
 
-    def ffn(self, x: torch.Tensor, rows: int, C: int, tb: str, name: str = "ff.fused") -> torch.Tensor:
+    def ffn(self, x: torch.Tensor, rows: int, C: int, tb: str, name: str = "ff.fused") -> Out:
         """out = x + W2 GEGLU(W1 LayerNorm(x) + b1) + b2 on the RAW rows x (model/attention.py:233) as one launch."""
         w1, w2, cst, b2 = self.store.ffn(tb + "ff.net.0.proj.weight", tb + "ff.net.0.proj.bias", tb + "ff.net.2.weight", tb + "ff.net.2.bias",
                                          tb + "norm3.")
         out = self.new(rows, C)
         self.prog.add(ops.make_ffn(dtype=self.dtype, x=x, ldx=x.stride(0), M=rows, w1=w1, w2=w2, cst=cst, b2=b2, out=out, ldo=out.stride(0),
                                    name=name))
-        self.last_gnp = None
-        self.last_row_stats = None
-        return out
+        return Out(out)
 
-    def _gnp_into_args(self, gnp_into, M: int, N: int, K: int, hw: int, splitk: int, C2: int = 0):
-        """A producer that writes a COLUMN SLICE of a concatenation can still hand the concatenation's GroupNorm its statistics: the
-        two halves share one buffer of slots (``gnp_into`` = (buffer [slots][Ctot][2], first column, rows per slot); edtr_hip.h:
-        gn_ld).  Returns the extra edtr_igemm arguments, or None where this launch cannot write them (the caller then keeps the
-        edtr_gn_stats pass over the concatenated tensor).  Fast modes only."""
-        if gnp_into is None or self.hp:
-            return None
-        buf, col, slot = gnp_into
-        want = ops.gn_slot_rows(hw) if splitk > 1 else 128
-        if want != slot or not ops.gn_fusable(M, N, K, hw, splitk=splitk, C2=C2, invariant=self.invariant):
-            return None
-        return dict(gn_partial=buf.reshape(-1)[2 * col:], gn_ld=buf.shape[1], gn_slot_rows=slot if splitk > 1 else 0)
+    def _output(self, out, M: int, N: int, out_f32: bool, mirror: bool):
+        """(the output buffer, a new one unless the caller gave one; the fp16 mirror the epilogue writes beside it, or None)"""
+        if out is None:
+            out = self.new(M, N, torch.float32 if out_f32 else (self.dtype if self.hp else None))
+            return out, (self.add_mirror(out) if mirror and self.mirrors_on and out_f32 else None)
+        return out, (self.mirror_view(out) if self.mirrors_on and out_f32 else None)      # a column slice of a mirrored stream buffer
+
+    def _tile_splitk(self, M: int, N: int, C1: int, taps: int = 1, C2: int = 0, Z: int = 1, act: int = 0, img8: bool = False):
+        """(tile, splitk) of an edtr_igemm launch: ops.choose_splitk, or the one geometry of the batch-invariant mode."""
+        return (ops.invariant_tile(C1, C2), 1) if self.invariant else ops.choose_splitk(M, N, taps * C1, Z, act, img8)
+
+    def _slabs_and_stats(self, out, M: int, N: int, C1: int, hw: int, splitk: int, own: bool, gnp_into, out_f32: bool, C2: int = 0):
+        """The buffers an edtr_igemm launch writes beside its output: (split-K workspace or None, own GroupNorm partials or None, rows
+        per slot, did the partials go into ``gnp_into``?, the launch's GroupNorm keyword arguments).  ``own``: the caller wants the
+        output's GroupNorm partials (``hw`` pixels per image) — written where the tile can (ops.gn_fusable) into a buffer of the
+        launch's own.  Otherwise a producer that fills a COLUMN SLICE of a concatenation can still hand the concatenation's GroupNorm
+        its statistics: the halves share one buffer of slots (``gnp_into`` = (buffer [slots][Ctot][2], first column, rows per slot);
+        edtr_hip.h: gn_ld; fast modes).  Where the launch can do neither, the consumer keeps its edtr_gn_stats pass."""
+        ws = self.arena.alloc((splitk * M * N,), torch.float32) if splitk > 1 else None
+        slot = ops.gn_slot_rows(hw) if splitk > 1 else 128
+        fusable = bool(hw) and ops.gn_fusable(M, N, C1, hw, splitk=splitk, C2=C2, invariant=self.invariant)
+        if own and (self.hp or not out_f32) and out.stride(0) == N and fusable:
+            gnp = self.arena.alloc((M // slot, N, 2), torch.float32)
+            return ws, gnp, slot, False, dict(gn_partial=gnp, gn_slot_rows=slot if splitk > 1 else 0)
+        if gnp_into is not None and not out_f32 and not self.hp and fusable and gnp_into[2] == slot:
+            buf, col, _ = gnp_into
+            return ws, None, 128, True, dict(gn_partial=buf.reshape(-1)[2 * col:], gn_ld=buf.shape[1], gn_slot_rows=slot if splitk > 1 else 0)
+        return ws, None, 128, False, {}
 
     def gemm(self, a, w, M: int, N: int, K: int, *, bias=None, out=None, act=0,
              residual=None, rowvec=None, rows_per_image=0, out_f32=False, alpha=1.0, name="linear", stats_hw=0,
-             out16=False, feeds=None, row_stats=False, ln_vec=None, mirror=False, gnp_into=None, **kw) -> torch.Tensor:
+             out16=False, feeds=None, row_stats=False, ln_vec=None, mirror=False, gnp_into=None, **kw) -> Out:
         """out[M, N'] = epilogue(a[M, K] @ w[N, K]^T).  ``a``/``out``/``residual`` are 2-D views (row stride = ld); ``w`` is a
         WRef of the store (or a ready packed tensor).  fp32-stream modes: the output is fp32 unless ``out16`` (an attention
-        operand, mixed mode only) or ``feeds`` names a GEMM class that takes it as a one-part operand."""
+        operand, mixed mode only) or ``feeds`` names a GEMM class that takes it as a one-part operand.  ``stats_hw`` (pixels per image):
+        the output's GroupNorm partials are wanted (Out.gnp, or ``gnp_into``: _slabs_and_stats); ``row_stats``: its per-row statistics."""
         n_out = N // 2 if act == L.ACT_GEGLU else N
-        self.last_gnp = None     # fused GroupNorm partials of this output (stats_hw = pixels per image), if eligible
-        self.last_gn_slot = 128  # ... and the rows each of their slots covers
-        self.gnp_into_done = False   # ... or whether they went into the caller's shared buffer (gnp_into)
-        self.last_row_stats = None   # per-row statistics of this output for a LayerNorm folded into the next GEMMs (row_stats=True)
         parts = self.parts_for(name, M, N, K)
         if parts == ops.PARTS_2W and (K % 64 or "Z" in kw or isinstance(a, LNRef) or kw.get("C2", 0)):
             parts = 3           # (the weights-exact form needs whole 64-column K-tiles of a plain GEMM)
@@ -880,40 +916,22 @@ class Emitter:
             else:
                 want16 = self.direct16 and (out16 or (feeds is not None and ops.op_parts(self.parts_for(feeds, M)) == 1))
                 out_f32 = not want16
-        m16 = None
-        if out is None:
-            out = self.new(M, n_out, torch.float32 if out_f32 else (self.dtype if self.hp else None))
-            if mirror and self.mirrors_on and out_f32:
-                m16 = self.add_mirror(out)
-        elif self.mirrors_on and out_f32:
-            m16 = self.mirror_view(out)       # a column slice of a mirrored stream buffer
+        out, m16 = self._output(out, M, n_out, out_f32, mirror)
         if m16 is not None:
             kw["out16"] = m16
         wt = self._w(w, parts)
         Ke = ops.k_mult(parts) * K
         if parts == ops.PARTS_2W:
             kw["a_wrap"] = K
-        if "tile" in kw:
-            tile, splitk = kw.pop("tile"), 1
-        else:
-            tile, splitk = ops.choose_splitk(M, N, Ke, kw.get("Z", 1), act)
-        if self.invariant and tile == 0:
-            tile, splitk = ops.invariant_tile(Ke, kw.get("C2", 0)), 1
-        if row_stats and not self.hp and splitk == 1 and act != L.ACT_GEGLU and N % 32 == 0 and "Z" not in kw:
-            self.last_row_stats = self.arena.alloc((M, N // 32, 2), torch.float32)
-            kw["row_stats"] = self.last_row_stats
-        ws = self.arena.alloc((splitk * M * N,), torch.float32) if splitk > 1 else None
-        if (stats_hw and act == 0 and (self.hp or not out_f32) and out.stride(0) == N and "Z" not in kw
-                and ops.gn_fusable(M, N, Ke, stats_hw, splitk=splitk, C2=kw.get("C2", 0), invariant=self.invariant)):
-            self.last_gn_slot = ops.gn_slot_rows(stats_hw) if splitk > 1 else 128
-            self.last_gnp = self.arena.alloc((M // self.last_gn_slot, N, 2), torch.float32)
-            kw["gn_partial"] = self.last_gnp
-            kw["gn_slot_rows"] = self.last_gn_slot if splitk > 1 else 0
-        elif gnp_into is not None and stats_hw and act == 0 and not out_f32 and "Z" not in kw:
-            into = self._gnp_into_args(gnp_into, M, N, Ke, stats_hw, splitk, kw.get("C2", 0))
-            if into is not None:
-                kw.update(into)
-                self.gnp_into_done = True
+        tile, splitk = self._tile_splitk(M, N, Ke, C2=kw.get("C2", 0), Z=kw.get("Z", 1), act=act)
+        if "tile" in kw:         # the caller's geometry, never split (0: left to the library, or to the invariant mode)
+            tile, splitk = kw.pop("tile") or tile, 1
+        rs_ok = row_stats and not self.hp and splitk == 1 and act != L.ACT_GEGLU and N % 32 == 0 and "Z" not in kw
+        rs = kw["row_stats"] = self.arena.alloc((M, N // 32, 2), torch.float32) if rs_ok else None
+        stats = bool(stats_hw) and act == 0 and "Z" not in kw
+        ws, gnp, gn_slot, shared, gnkw = self._slabs_and_stats(out, M, N, Ke, stats_hw, splitk, stats, gnp_into if stats else None, out_f32,
+                                                               kw.get("C2", 0))
+        kw.update(gnkw)
         res32 = residual is not None and residual.dtype == torch.float32
         self.prog.add(ops.make_igemm(
             dtype=self.dtype, a1=a, w=wt, out=out, M=M, N=N, C1=Ke, ld1=a.stride(0), ldw=wt.stride(0), ldc=out.stride(0),
@@ -922,7 +940,7 @@ class Emitter:
             out_f32=out_f32, alpha=alpha, name=name, tile=tile, splitk=splitk, workspace=ws, **kw))
         self.arena.free(ws)
         self.arena.free(tmp)
-        return out
+        return Out(out, gnp, gn_slot, rs, shared)
 
     def fused_qkv_ok(self, N: int, C: int) -> bool:
         """Can a self-attention's q / k / v^T come out of ONE edtr_igemm launch (transposed second output)?  Needs a 16-bit
@@ -955,23 +973,63 @@ class Emitter:
         return qk, vt, N
 
     def tail_ok(self, x: Act, prefix: str, skip_x: Act) -> bool:
-        """Can the 3x3 convolution ``prefix`` of ``x`` take the 1x1 convolution of ``skip_x`` (same pixels) as a K tail?  Fast modes
-        with the switch on (Emitter.ktail), whole 64-channel chunks on both operands, and edtr_igemm_plan's word that the halo tile
-        it picks for this shape runs a tail (the split-K count and the fused input GroupNorm are the ones conv() will pass)."""
-        if not self.ktail or self.invariant or x.C % 64 or skip_x.C % 64 or (x.B, x.H, x.W) != (skip_x.B, skip_x.H, skip_x.W):
-            return False
-        if isinstance(x.t, OpN) or isinstance(skip_x.t, OpN) or x.t.dtype != self.dtype or skip_x.t.dtype != self.dtype:
-            return False
-        N = round_up(self.store.shape_of(prefix + "weight")[0], 8)
-        splitk = ops.choose_splitk(x.rows, N, 9 * x.C, img8=(x.H, x.W) == (8, 8))[1]
-        gnin = x.gn_in is not None and ops.gn_in_conv_ok(x.B, x.H, x.W, x.C, N, splitk, x.ld)
-        tile = ops.ktail_plan(self.dtype, x.B, x.H, x.W, x.C, x.ld, N, skip_x.C, skip_x.ld, splitk, gnin)
-        # tile 16's 16 x 16-patch form with a tail three times as wide as the 3x3's input (the 32 x 32 decoder block 1920 -> 640):
-        # measured slower than the launch it replaces (+37.2 us in the loop against 32.6 us, profiles/ktail) — the tail loop runs
-        # its K-tiles at about half the main loop's rate; up to twice the width it wins (+20.7 against 25.1 us)
-        if tile == 16 and (x.H, x.W) != (8, 8) and skip_x.C > 2 * x.C:
-            return False
-        return tile > 0
+        """Can the 3x3 convolution ``prefix`` of ``x`` take the 1x1 convolution of ``skip_x`` (same pixels) as a K tail?  The plan of
+        that convolution says (ConvPlan.tail_tile)."""
+        return self.conv_plan(x, prefix, tail=skip_x).tail_tile > 0
+
+    def conv_plan(self, x: Act, w, *, taps=9, stride=1, pad_tl=1, ups=False, name: Optional[str] = None, tail: Optional[Act] = None,
+                  defer: bool = False) -> ConvPlan:
+        """The one place that decides what Emitter.conv launches for the convolution of ``x`` with the weight prefix ``w`` (or an output
+        width alone, where no more is promised: group_norm's conv_n).  ``name``: the convolution's GEMM class; None while it is only
+        promised — the parts are then unknown.  ``tail``: the input of a 1x1 convolution that would ride as a K tail.  ``defer``: would
+        this convolution apply a GroupNorm of ``x`` that is not deferred yet (asked by gn_deferrable; an ``x`` that carries gn_in asks
+        by itself)?
+
+        Promise and launch used to derive the split-K count each in their own way; they are one derivation now because
+          * with img8 (gn_deferrable passed none): at 8 x 8 ops.gn_in_conv_ok refuses whatever the split is, and nothing else of a
+            promise depends on it;
+          * K = taps * Ce against 9 * C (tail_ok, the first check of conv): a tail exists in the fast modes only and a deferred
+            GroupNorm is applied by a one-part product only — parts == 1 and Ce == C in both;
+          * N from the packed weight against round_up(rows of the parameter, 8): WeightStore.conv and .conv_tail pack exactly
+            that many rows."""
+        N = w if isinstance(w, int) else round_up(self.store.shape_of(w + "weight")[0], 8)
+        plain = taps == 9 and stride == 1 and pad_tl == 1 and not ups
+        OH, OW = x.H, x.W
+        if taps == 9:            # bottom / right halo always exists (zero); only the top / left pad differs (VAE downsample)
+            OH, OW = ((2 * x.H if ups else x.H) + pad_tl - 2) // stride + 1, ((2 * x.W if ups else x.W) + pad_tl - 2) // stride + 1
+        M = x.B * OH * OW
+        native = not isinstance(x.t, OpN) and x.t.dtype == self.dtype          # stored in the MFMA operand type
+        parts = asked = Ce = None
+        ld = x.ld
+        if name is not None:
+            parts = asked = self.parts_for(name, M, N, taps * x.C)
+            if parts == ops.PARTS_2W and (taps != 1 or x.C % 64):
+                parts = asked = 3       # (the weights-exact form exists for 1x1 convolutions = plain GEMMs)
+            if self.hp:
+                _, parts, ld = self._operand_form(x.t, x.C, parts)
+            Ce = ops.k_mult(parts) * x.C
+        C1 = Ce or x.C
+        # nearest-2x upsample convolutions run in their sub-pixel form (four 2x2 convolutions of the source image with pre-summed
+        # weights: 4 instead of 9 multiply-adds per output element) wherever the halo kernel's geometry takes them
+        subpix = ups and taps == 9 and stride == 1 and pad_tl == 1 and not self.invariant and ops.subpixel_ok(x.H, x.W, C1, N, x.B, ld)
+        img8 = plain and (x.H, x.W) == (8, 8) and C1 % 64 == 0
+        tile, splitk = (16, 1) if subpix else self._tile_splitk(M, N, C1, taps, img8=img8)
+        gn_in = ((defer or x.gn_in is not None) and plain and not self.invariant and (not self.hp or (native and asked in (None, 1)))
+                 and ops.gn_in_conv_ok(x.B, x.H, x.W, x.C, N, splitk, x.ld))
+        if gn_in:
+            tile = 0             # (edtr_igemm picks the halo geometry itself: tile 17 from 256 units of 512 pixels, tile 16 below)
+        tail_tile = 0
+        if (tail is not None and self.ktail and plain and not self.invariant and x.C % 64 == 0 and tail.C % 64 == 0 and native
+                and (x.B, x.H, x.W) == (tail.B, tail.H, tail.W) and not isinstance(tail.t, OpN) and tail.t.dtype == self.dtype):
+            # fast modes with the switch on (Emitter.ktail), whole 64-channel chunks on both operands, and edtr_igemm_plan's word that
+            # the halo tile it picks for this shape, split-K count and fused input GroupNorm runs a tail
+            tail_tile = ops.ktail_plan(self.dtype, x.B, x.H, x.W, x.C, x.ld, N, tail.C, tail.ld, splitk, gn_in)
+            # tile 16's 16 x 16-patch form with a tail three times as wide as the 3x3's input (the 32 x 32 decoder block 1920 -> 640):
+            # measured slower than the launch it replaces (+37.2 us in the loop against 32.6 us, profiles/ktail) — the tail loop runs
+            # its K-tiles at about half the main loop's rate; up to twice the width it wins (+20.7 against 25.1 us)
+            if tail_tile == 16 and (x.H, x.W) != (8, 8) and tail.C > 2 * x.C:
+                tail_tile = 0
+        return ConvPlan(N, OH, OW, M, parts, Ce, img8, tile, splitk, subpix, gn_in, tail_tile)
 
     def conv(self, x: Act, prefix: str, *, taps=9, stride=1, pad_tl=1, ups=False, rowvec=None, residual=None,
              out=None, out_f32=False, alpha=1.0, name=None, stats=False, feeds=None, mirror=False, gnp_into=None,
@@ -981,97 +1039,50 @@ class Emitter:
         anyway — so it is stored as fp16 instead of joining the fp32 stream (Emitter.branch16).  ``tail`` = (activation, prefix of a
         1x1 convolution): that convolution is summed into this one as a K tail (edtr_hip.h: a3; the caller has asked tail_ok)."""
         name = name or ("conv3x3" if taps == 9 else "conv1x1")
+        plan = self.conv_plan(x, prefix, taps=taps, stride=stride, pad_tl=pad_tl, ups=ups, name=name)
+        N, OH, OW, M, parts, Ce, tile, splitk = plan.N, plan.OH, plan.OW, plan.M, plan.parts, plan.Ce, plan.tile, plan.splitk
+        if x.gn_in is not None and not plan.gn_in:
+            # the caller's conv_n promised another convolution than the one that arrived (stride 2; a tensor that is not 32-bit addressable
+            # after all): the GroupNorm gets its own apply launch, on the same statistics, and the convolution runs on the normalised tensor
+            if x.gn_apply is None:
+                raise RuntimeError(f"{name}: a deferred GroupNorm reached a convolution that cannot apply it")
+            xn = x.gn_apply()
+            y = self.conv(xn, prefix, taps=taps, stride=stride, pad_tl=pad_tl, ups=ups, rowvec=rowvec, residual=residual, out=out,
+                          out_f32=out_f32, alpha=alpha, name=name, stats=stats, feeds=feeds, mirror=mirror, gnp_into=gnp_into, tail=tail)
+            self.free(xn)
+            return y
         if tail is not None:
             if residual is not None or taps != 9 or stride != 1 or pad_tl != 1 or ups or self.hp or alpha != 1.0:
                 raise RuntimeError(f"{name}: a K tail rides in a plain 3x3 convolution of the fast modes, in place of its residual")
             w, bias = self.store.conv_tail(prefix, tail[1], cin_pad=x.C, tail_pad=tail[0].C)
+        elif plan.subpix:
+            w, bias = self.store.conv_subpixel(prefix, cin_pad=x.C, bias_scale=alpha)
         else:
             w, bias = self.store.conv(prefix, cin_pad=x.C, bias_scale=alpha)      # the epilogue applies alpha before the bias
-        N = w.shape[0]
-        if taps == 9:
-            LH, LW = (x.H * 2, x.W * 2) if ups else (x.H, x.W)
-            pad_br = 1  # bottom/right halo always exists (zero); only the top/left pad differs (VAE downsample)
-            OH = (LH + pad_tl + pad_br - 3) // stride + 1
-            OW = (LW + pad_tl + pad_br - 3) // stride + 1
-            spatial = (x.H, x.W, OH, OW, stride, pad_tl, pad_tl, int(ups))
-        else:
-            OH, OW, spatial = x.H, x.W, None
-        M = x.B * OH * OW
-        parts = self.parts_for(name, M, N, taps * x.C)
-        if parts == ops.PARTS_2W and (taps != 1 or x.C % 64):
-            parts = 3           # (the weights-exact form exists for 1x1 convolutions = plain GEMMs)
-        if x.gn_in is not None:          # a deferred GroupNorm: is this one of the convolutions that apply it while staging their operand?
-            img8_ = taps == 9 and stride == 1 and pad_tl == 1 and not ups and (x.H, x.W) == (8, 8) and x.C % 64 == 0
-            fusable = (taps == 9 and stride == 1 and pad_tl == 1 and not ups and not self.invariant
-                       and (not self.hp or (x.t.dtype == self.dtype and parts == 1))
-                       and ops.gn_in_conv_ok(x.B, x.H, x.W, x.C, N, ops.choose_splitk(M, N, taps * x.C, img8=img8_)[1], x.ld))
-            if not fusable:
-                # the caller's conv_n promised another convolution than the one that arrived (ADVICE r04): the GroupNorm gets its
-                # own apply launch after all, on the same statistics, and the convolution runs on the normalised tensor
-                if x.gn_apply is None:
-                    raise RuntimeError(f"{name}: a deferred GroupNorm reached a convolution that cannot apply it")
-                xn = x.gn_apply()
-                y = self.conv(xn, prefix, taps=taps, stride=stride, pad_tl=pad_tl, ups=ups, rowvec=rowvec, residual=residual, out=out,
-                              out_f32=out_f32, alpha=alpha, name=name, stats=stats, feeds=feeds, mirror=mirror, gnp_into=gnp_into,
-                              tail=tail)
-                self.free(xn)
-                return y
+        spatial = (x.H, x.W, OH, OW, stride, pad_tl, pad_tl, 2 if plan.subpix else int(ups)) if taps == 9 else None
         a, tmp = x.t, None
         if self.hp:
             a, tmp, parts = self._operand(x.t, x.rows, x.C, parts)
             out_f32 = True if out is None else out.dtype == torch.float32
             if out is None and self.branch16 and feeds and self.feeds_parts(feeds, M) == 1:
                 out_f32 = False
-        Ce = ops.k_mult(parts) * x.C
-        # nearest-2x upsample convolutions run in their sub-pixel form (four 2x2 convolutions of the source image with pre-summed
-        # weights: 4 instead of 9 multiply-adds per output element) wherever the halo kernel's geometry takes them
-        subpix = (ups and taps == 9 and stride == 1 and pad_tl == 1 and not self.invariant
-                  and ops.subpixel_ok(x.H, x.W, Ce, N, x.B, a.stride(0)))
-        if subpix:
-            w, bias = self.store.conv_subpixel(prefix, cin_pad=x.C, bias_scale=alpha)
-            spatial = spatial[:7] + (2,)
         wt = self._w(w, parts)
-        m16 = None
-        if out is None:
-            out = self.new(M, N, torch.float32 if out_f32 else (self.dtype if self.hp else None))
-            if mirror and self.mirrors_on and out_f32:
-                m16 = self.add_mirror(out)
-        elif self.mirrors_on and out_f32:
-            m16 = self.mirror_view(out)
-        img8 = taps == 9 and stride == 1 and pad_tl == 1 and not ups and (x.H, x.W) == (8, 8) and Ce % 64 == 0
-        tile, splitk = ops.choose_splitk(M, N, taps * Ce, img8=img8)
-        if self.invariant:
-            tile, splitk = ops.invariant_tile(Ce, 0), 1
-        if subpix:
-            tile, splitk = 16, 1
-        if x.gn_in is not None:          # the input's GroupNorm rides in this convolution's patch staging (group_norm(..., conv_n=N))
-            if (taps != 9 or stride != 1 or pad_tl != 1 or ups or (self.hp and (a.dtype != self.dtype or parts != 1 or a is not x.t))
-                    or not ops.gn_in_conv_ok(x.B, x.H, x.W, x.C, N, splitk, x.ld)):
-                raise RuntimeError(f"{name}: a deferred GroupNorm reached a convolution that cannot apply it")      # (checked above)
-            tile = 0             # (edtr_igemm picks the halo geometry itself: tile 17 from 256 units of 512 pixels, tile 16 below)
-        ws = self.arena.alloc((splitk * M * N,), torch.float32) if splitk > 1 else None
-        gnp, gn_slot, into = None, 128, None
-        self.gnp_into_done = False
-        if stats and (self.hp or not out_f32) and out.stride(0) == N and ops.gn_fusable(M, N, Ce, OH * OW, splitk=splitk, invariant=self.invariant):
-            gn_slot = ops.gn_slot_rows(OH * OW) if splitk > 1 else 128
-            gnp = self.arena.alloc((M // gn_slot, N, 2), torch.float32)
-        elif gnp_into is not None and not out_f32:
-            into = self._gnp_into_args(gnp_into, M, N, Ce, OH * OW, splitk)
-            self.gnp_into_done = into is not None
+        out, m16 = self._output(out, M, N, out_f32, mirror)
+        ws, gnp, gn_slot, shared, gnkw = self._slabs_and_stats(out, M, N, Ce, OH * OW, splitk, stats, gnp_into, out_f32)
+        # (a split-K convolution without statistics has always named the 128-row slot; edtr_igemm reads it beside gn_partial only)
+        gnkw = gnkw or dict(gn_slot_rows=128 if splitk > 1 else 0)
         res32 = residual is not None and residual.dtype == torch.float32
         self.prog.add(ops.make_igemm(
             dtype=self.dtype, a1=a, w=wt, out=out, taps=taps, M=M, N=N, C1=Ce, ld1=a.stride(0), ldw=wt.stride(0),
             ldc=out.stride(0), spatial=spatial, bias_n=bias, rowvec=rowvec,
             rowvec_ld=rowvec.stride(0) if rowvec is not None else 0, rows_per_image=OH * OW, residual=residual,
             ldr=residual.stride(0) if residual is not None else 0, residual_f32=res32, out_f32=out_f32, alpha=alpha, tile=tile,
-            splitk=splitk, workspace=ws, name=name,
-            **(into if into is not None else dict(gn_partial=gnp, gn_slot_rows=gn_slot if splitk > 1 else 0)),
-            w_phase_stride=(N * wt.stride(0)) if subpix else 0,
+            splitk=splitk, workspace=ws, name=name, **gnkw, w_phase_stride=(N * wt.stride(0)) if plan.subpix else 0,
             out16=m16, a_wrap=x.C if parts == ops.PARTS_2W else 0, a_gn=x.gn_in, a_gn_silu=x.gn_silu,
             a3=tail[0].t if tail is not None else None, C3=tail[0].C if tail is not None else 0))
         self.arena.free(ws)
         self.arena.free(tmp)
-        return Act(out, x.B, OH, OW, N, gnp, gn_slot=gn_slot)
+        return Act(out, x.B, OH, OW, N, gnp, gn_slot=gn_slot, stats_shared=shared)
 
     def conv128_out(self, x: Act, prefix: str, out_nchw: torch.Tensor, n_valid: int, alpha: float = 1.0, name="vae.conv_out") -> None:
         """The VAE decoder's conv_out on edtr_conv128_out: ``x`` carries its deferred GroupNorm (group_norm / gn_stats_into with
@@ -1116,8 +1127,7 @@ class Emitter:
             return False
         if conv_n < 0:
             return ops.conv128_out_ok(x.H, x.W, x.C, -conv_n)
-        _, splitk = ops.choose_splitk(x.rows, conv_n, 9 * x.C)
-        return ops.gn_in_conv_ok(x.B, x.H, x.W, x.C, conv_n, splitk, x.ld)
+        return self.conv_plan(x, conv_n, defer=True).gn_in
 
     def _deferred(self, x: Act, table: torch.Tensor, silu: bool, take: bool, apply=None) -> Act:
         y = Act(x.t, x.B, x.H, x.W, x.C, x.gnp if take else None, gn_in=table, gn_silu=silu, owns=take, gn_apply=apply)
@@ -1248,9 +1258,9 @@ class Emitter:
         return carried
 
     # -- elementwise --------------------------------------------------------------------------
-    def add(self, a: torch.Tensor, b: Optional[torch.Tensor], rows: int, C: int, out=None, stats_into=None) -> torch.Tensor:
+    def add(self, a: torch.Tensor, b: Optional[torch.Tensor], rows: int, C: int, out=None, stats_into=None) -> Out:
         """``stats_into`` = (buffer [slots][Ctot][2], first column, rows per slot): the launch also writes the result's GroupNorm partials
-        into the shared slot buffer of the concatenation it fills a column slice of (fast modes; Emitter._gnp_into_args)."""
+        into the shared slot buffer of the concatenation it fills a column slice of (fast modes; Emitter._slabs_and_stats)."""
         if out is None:
             out = self.new(rows, C)
         if stats_into is not None and not self.hp and C % 32 == 0 and rows % stats_into[2] == 0:
@@ -1258,19 +1268,17 @@ class Emitter:
             self.prog.add(ops.make_add_stats(dtype=self.io, a=a, lda=a.stride(0), b=b, ldb=b.stride(0) if b is not None else 0, out=out,
                                              ldo=out.stride(0), rows=rows, C=C, gn_partial=buf.reshape(-1)[2 * col:], gn_ld=buf.shape[1],
                                              slot_rows=slot))
-            self.add_stats_done = True
-            return out
-        self.add_stats_done = False
+            return Out(out, stats_shared=True)
         m16 = self.mirror_view(out) if self.mirrors_on else None
         if m16 is not None and C % 8:
             raise ValueError(f"add into a mirrored stream buffer needs C % 8 == 0 (got {C}): its fp16 mirror would go stale")
         if m16 is not None:
             self.prog.add(ops.make_add_mirror(a=a, lda=a.stride(0), b=b, ldb=b.stride(0) if b is not None else 0, out=out,
                                               ldo=out.stride(0), out16=m16, rows=rows, C=C))
-            return out
+            return Out(out)
         self.prog.add(ops.make_add(dtype=self.io, a=a, lda=a.stride(0), b=b, ldb=b.stride(0) if b is not None else 0,
                                    out=out, ldo=out.stride(0), rows=rows, C=C))
-        return out
+        return Out(out)
 
     def to_nhwc(self, src: torch.Tensor, B: int, C: int, HW: int, dst: torch.Tensor, coff=0, pad_to=0, scale=1.0,
                 shift=0.0) -> None:

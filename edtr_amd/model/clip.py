@@ -197,7 +197,7 @@ class _TextEngine:
             p = f"model.transformer.resblocks.{i}."
             h = em.layer_norm(x, rows, W, p + "ln_1.")
             wqk, bqk = store.rows(p + "attn.in_proj_weight", 0, 2 * W, p + "attn.in_proj_bias")
-            qk = em.gemm(h, wqk, rows, 2 * W, W, bias=bqk, name="clip.qk")
+            qk = em.gemm(h, wqk, rows, 2 * W, W, bias=bqk, name="clip.qk").t
             wv, _ = store.rows(p + "attn.in_proj_weight", 2 * W, 3 * W)
             bv = store.raw(p + "attn.in_proj_bias")[2 * W:3 * W]
             vt, ldv = em.vt_gemm(wv, h, B=B, Ntok=Lc, Cin=W, bias_m=bv, name="clip.vT")
@@ -205,14 +205,14 @@ class _TextEngine:
                          vt_ld=ldv, causal=True)
             em.free(h, qk, vt)
             wo, bo = store.linear([p + "attn.out_proj.weight"], [p + "attn.out_proj.bias"])
-            x1 = em.gemm(o, wo, rows, W, W, bias=bo, residual=x, name="clip.attn_out")
+            x1 = em.gemm(o, wo, rows, W, W, bias=bo, residual=x, name="clip.attn_out").t
             em.free(o, x)
             h2 = em.layer_norm(x1, rows, W, p + "ln_2.")
             wf, bf = store.linear([p + "mlp.c_fc.weight"], [p + "mlp.c_fc.bias"])
-            g = em.gemm(h2, wf, rows, 4 * W, W, bias=bf, act=L.ACT_GELU, name="clip.c_fc")
+            g = em.gemm(h2, wf, rows, 4 * W, W, bias=bf, act=L.ACT_GELU, name="clip.c_fc").t
             em.free(h2)
             wp, bp = store.linear([p + "mlp.c_proj.weight"], [p + "mlp.c_proj.bias"])
-            x = em.gemm(g, wp, rows, W, 4 * W, bias=bp, residual=x1, name="clip.c_proj")
+            x = em.gemm(g, wp, rows, W, 4 * W, bias=bp, residual=x1, name="clip.c_proj").t
             em.free(g, x1)
         y = em.layer_norm(x, rows, W, "model.ln_final.")
         self.prog.add(ops_mod.make_nhwc_to_nchw(dtype=dt, src=y, src_f32=False, B=1, C=1, HW=rows * W, ld=1, dst=self.out,

@@ -301,11 +301,11 @@ class _SwinEngine:
                 wq, bq, bias, wq32 = store.cache[key]
                 if r_stats is not None:       # r came out of the previous layer's fc2 with its row statistics: no norm1 launch
                     wqf, _, c1, c2 = folded("qkv", p, p + "norm1.", wq32, bq)
-                    qkv = em.gemm(LNRef(r, r_stats, CP, p + "norm1.", C), wqf, rows, 3 * QW, CP, bias=bq, name="swin.qkv", ln_vec=(c1, c2))
+                    qkv = em.gemm(LNRef(r, r_stats, CP, p + "norm1.", C), wqf, rows, 3 * QW, CP, bias=bq, name="swin.qkv", ln_vec=(c1, c2)).t
                     em.free(r_stats)
                 else:
                     h = ln(r, p + "norm1.")
-                    qkv = em.gemm(h, wq, rows, 3 * QW, CP, bias=bq, name="swin.qkv")
+                    qkv = em.gemm(h, wq, rows, 3 * QW, CP, bias=bq, name="swin.qkv").t
                     em.free(h)
                 lab = None
                 if shift:
@@ -318,8 +318,8 @@ class _SwinEngine:
                                                        scale=d ** -0.5))
                 em.free(qkv)
                 wp, bp = linear(p + "attn.proj.", CP, CP)
-                x1 = em.gemm(o, wp, rows, CP, CP, bias=bp, residual=r, name="swin.proj", row_stats=fold_ln and not fuse_mlp)
-                x1_stats = em.last_row_stats
+                proj = em.gemm(o, wp, rows, CP, CP, bias=bp, residual=r, name="swin.proj", row_stats=fold_ln and not fuse_mlp)
+                x1, x1_stats = proj.t, proj.row_stats
                 em.free(o)
                 if r is not t:
                     em.free(r)
@@ -334,15 +334,15 @@ class _SwinEngine:
                 w1, b1 = linear(p + "mlp.fc1.", CP, HP)
                 if x1_stats is not None:
                     w1f, _, c1, c2 = folded("fc1", p, p + "norm2.", fc1_f32(p, HP), b1)
-                    g = em.gemm(LNRef(x1, x1_stats, CP, p + "norm2.", C), w1f, rows, HP, CP, bias=b1, act=L.ACT_GELU, name="swin.fc1", ln_vec=(c1, c2))
+                    g = em.gemm(LNRef(x1, x1_stats, CP, p + "norm2.", C), w1f, rows, HP, CP, bias=b1, act=L.ACT_GELU, name="swin.fc1", ln_vec=(c1, c2)).t
                     em.free(x1_stats)
                 else:
                     h2 = ln(x1, p + "norm2.")
-                    g = em.gemm(h2, w1, rows, HP, CP, bias=b1, act=L.ACT_GELU, name="swin.fc1")
+                    g = em.gemm(h2, w1, rows, HP, CP, bias=b1, act=L.ACT_GELU, name="swin.fc1").t
                     em.free(h2)
                 w2, b2 = linear(p + "mlp.fc2.", HP, CP)
-                r = em.gemm(g, w2, rows, CP, HP, bias=b2, residual=x1, name="swin.fc2", row_stats=fold_ln and not last_of_group)
-                r_stats = em.last_row_stats
+                fc2 = em.gemm(g, w2, rows, CP, HP, bias=b2, residual=x1, name="swin.fc2", row_stats=fold_ln and not last_of_group)
+                r, r_stats = fc2.t, fc2.row_stats
                 em.free(g, x1)
             t2 = conv3(Act(r, B, th, tw, CP), f"layers.{i}.conv.", CP, residual=t, name="swin.rstb_conv")
             em.free(r)

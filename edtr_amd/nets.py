@@ -21,7 +21,7 @@ import torch
 from . import lib as L
 from . import ops
 from .arch import Layer, UNetArch, VaeLayer
-from .engine import Act, Emitter, LNRef, LNReg
+from .engine import Act, Emitter, LNRef, LNReg, Out
 from .ops import round_up
 
 
@@ -36,14 +36,14 @@ def emit_time_rows(em: Emitter, P: str, a: UNetArch, t_dev: torch.Tensor, B: int
     temb = em.new(B, mc)
     em.prog.add(ops.make_timestep_embedding(dtype=em.io, t=t_dev, B=B, dim=mc, out=temb, ld=mc))
     w0, b0 = em.store.linear([P + "time_embed.0.weight"], [P + "time_embed.0.bias"])
-    h = em.gemm(temb, w0, B, ted, mc, bias=b0, act=L.ACT_SILU, name="time_embed.0")
+    h = em.gemm(temb, w0, B, ted, mc, bias=b0, act=L.ACT_SILU, name="time_embed.0").t
     w2, b2 = em.store.linear([P + "time_embed.2.weight"], [P + "time_embed.2.bias"])
-    semb = em.gemm(h, w2, B, ted, ted, bias=b2, act=L.ACT_SILU, name="time_embed.2")   # SiLU(emb): all consumers want it
+    semb = em.gemm(h, w2, B, ted, ted, bias=b2, act=L.ACT_SILU, name="time_embed.2").t   # SiLU(emb): all consumers want it
     res = a.res_layers()
     wall, ball = em.store.linear([P + l.prefix + "emb_layers.1.weight" for l in res],
                                  [P + l.prefix + "emb_layers.1.bias" for l in res])
     total = wall.shape[0]
-    table = em.gemm(semb, wall, B, total, ted, bias=ball, out_f32=True, name="emb_layers(all)")
+    table = em.gemm(semb, wall, B, total, ted, bias=ball, out_f32=True, name="emb_layers(all)").t
     em.free(temb, h, semb)
     offs, o = {}, 0
     for l in res:
@@ -77,7 +77,7 @@ def emit_context_kv(em: Emitter, P: str, a: UNetArch, ctx16: torch.Tensor, B: in
     wv, _ = em.store.linear([P + l.prefix + t + "to_v.weight" for l in layers])
     kv.sumC, kv.Nctx = wk.shape[0], Nctx
     kv.split = em.attn_split
-    kv.k_all = em.gemm(ctx16, wk, B * Nctx, kv.sumC, a.context_dim, name="ctx_k(all)", out16=kv.split < 1)
+    kv.k_all = em.gemm(ctx16, wk, B * Nctx, kv.sumC, a.context_dim, name="ctx_k(all)", out16=kv.split < 1).t
     kv.vt_all, kv.ldv = em.vt_gemm(wv, ctx16, B=B, Ntok=Nctx, Cin=a.context_dim, name="ctx_vT(all)", out16=kv.split < 2)
     # fp32 projections (high mode: bf16 MFMA type; split attention in any fp32-stream mode): the attention operands are fp16, cut
     # once per prompt — hi + lo pairs ([hi | lo] columns) where the attention is split, one part otherwise
@@ -119,20 +119,18 @@ def emit_resblock(em: Emitter, P: str, l: Layer, x: Act, table: torch.Tensor, of
         skip = x.t
     y = em.conv(n2, p + "out_layers.3.", residual=skip, out=out, name="res.conv2", stats=out is None, mirror=mirror, gnp_into=gnp_into,
                 tail=tail)
-    into_done = em.gnp_into_done
     em.free(n2)
     if l.cin != l.cout and tail is None:
         em.free(skip)
-    em.gnp_into_done = into_done
     return y
 
 
 def emit_attention_core(em: Emitter, p: str, x, B: int, N: int, C: int, heads: int,
                         ctx: Optional[Tuple[torch.Tensor, torch.Tensor, int, int, int, int]], residual: torch.Tensor,
-                        row_stats: bool = False) -> torch.Tensor:
+                        row_stats: bool = False) -> Out:
     """One attention layer on tokens x [B*N, C] (already layer-normed, or an LNRef = the LayerNorm folded into the
-    projection): projections, fused attention, output projection with bias and residual.  ``row_stats``: the output
-    projection also writes the per-row statistics of its result (em.last_row_stats) for the next folded LayerNorm.
+    projection): projections, fused attention, output projection with bias and residual — whose Out is returned.  ``row_stats``:
+    the output projection also writes the per-row statistics of its result (Out.row_stats) for the next folded LayerNorm.
     model/attention.py:176-203."""
     fold = x.prefix if isinstance(x, LNRef) else None
     # softmax scale (1/sqrt(64)) and the exp -> exp2 factor log2(e) are folded into the projections' fp32 epilogues (q.k
@@ -156,7 +154,7 @@ def emit_attention_core(em: Emitter, p: str, x, B: int, N: int, C: int, heads: i
         em.free(qk, vt)
     elif ctx is None:   # (high mode / odd shapes) fused [Wq;Wk] projection, V^T via the operand-swapped GEMM
         wqk, _ = em.store.linear([p + "to_q.weight", p + "to_k.weight"])
-        qk = em.gemm(x, wqk, B * N, 2 * C, C, alpha=math.sqrt(c), name="attn1.qk", out16=em.attn_split < 1)
+        qk = em.gemm(x, wqk, B * N, 2 * C, C, alpha=math.sqrt(c), name="attn1.qk", out16=em.attn_split < 1).t
         wv, _ = em.store.linear([p + "to_v.weight"])
         vt, ldv = em.vt_gemm(wv, x, B=B, Ntok=N, Cin=C, name="attn1.vT", out16=em.attn_split < 2)
         o = em.flash(qk[:, :C], qk[:, C:], vt, B=B, H=heads, Nq=N, Nk=N, k_bs=N * qk.stride(0), vt_bs=C * ldv, vt_ld=ldv,
@@ -165,13 +163,13 @@ def emit_attention_core(em: Emitter, p: str, x, B: int, N: int, C: int, heads: i
     else:
         k, vt, k_bs, vt_bs, ldv, nctx, k_lo, vt_lo = ctx
         if isinstance(x, LNReg):    # norm2 + to_q as ONE launch on the raw rows (edtr_lin320: the rows are normalised in registers)
-            q = em.lin320(x.x, B * N, C, [p + "to_q.weight"], None, ln_prefix=x.prefix, alpha=c, name="attn2.q")
+            q = em.lin320(x.x, B * N, C, [p + "to_q.weight"], None, ln_prefix=x.prefix, alpha=c, name="attn2.q").t
         elif fold:
             wq, _, c1, c2 = em.store.ln_fold("linear", [p + "to_q.weight"], None, fold)
-            q = em.gemm(x, wq, B * N, C, C, alpha=c, name="attn2.q", out16=True, ln_vec=(c1, c2))
+            q = em.gemm(x, wq, B * N, C, C, alpha=c, name="attn2.q", out16=True, ln_vec=(c1, c2)).t
         else:
             wq, _ = em.store.linear([p + "to_q.weight"])
-            q = em.gemm(x, wq, B * N, C, C, alpha=c, name="attn2.q", out16=em.attn_split < 1)
+            q = em.gemm(x, wq, B * N, C, C, alpha=c, name="attn2.q", out16=em.attn_split < 1).t
         o = em.flash(q, k, vt, B=B, H=heads, Nq=N, Nk=nctx, k_bs=k_bs, vt_bs=vt_bs, vt_ld=ldv, prescaled=True, k_lo=k_lo, vt_lo=vt_lo)
         em.free(q)
     if not row_stats and em.lin320_ok(B * N, C, C) and o.dtype == residual.dtype:
@@ -196,11 +194,9 @@ def emit_spatial_transformer(em: Emitter, P: str, l: Layer, x: Act, kv: ContextK
     wi, bi = em.store.linear([p + "proj_in.weight"], [p + "proj_in.bias"])
     # The three LayerNorms of the block are not launched in the fast modes: the GEMM that writes their input also writes
     # per-row statistics, the GEMMs that read them run on the raw rows with gamma folded into the weights (Emitter.layer_norm).
-    if lin and not fold1:
-        t = em.lin320(n.t, rows, C, [p + "proj_in.weight"], [p + "proj_in.bias"], gn_table=n.gn_in, rows_per_image=N, name="st.proj_in")
-    else:
-        t = em.gemm(n.t, wi, rows, C, C, bias=bi, name="st.proj_in", row_stats=fold1)
-    st = em.last_row_stats
+    pi = (em.lin320(n.t, rows, C, [p + "proj_in.weight"], [p + "proj_in.bias"], gn_table=n.gn_in, rows_per_image=N, name="st.proj_in")
+          if lin and not fold1 else em.gemm(n.t, wi, rows, C, C, bias=bi, name="st.proj_in", row_stats=fold1))
+    t, st = pi.t, pi.row_stats
     em.free(n)
     tb = p + "transformer_blocks.0."
     if (st is None and em.fused_qkv_ok(N, C) and em.lin320_ok(rows, 3 * C, C, ln=True) and N % 32 == 0 and em.attn_dtype == em.dtype
@@ -208,8 +204,8 @@ def emit_spatial_transformer(em: Emitter, P: str, l: Layer, x: Act, kv: ContextK
         l1 = LNReg(t, C, tb + "norm1.")
     else:
         l1 = em.layer_norm(t, rows, C, tb + "norm1.", feeds=("attn1.qkv",) if em.fused_qkv_ok(N, C) else ("attn1.qk", "attn1.vT"), stats=st)
-    t1 = emit_attention_core(em, tb + "attn1.", l1, B, N, C, l.heads, None, t, row_stats=fold)
-    st = em.last_row_stats
+    a1 = emit_attention_core(em, tb + "attn1.", l1, B, N, C, l.heads, None, t, row_stats=fold)
+    t1, st = a1.t, a1.row_stats
     em.free(l1, t)
     l2 = (LNReg(t1, C, tb + "norm2.") if (st is None and em.lin320_ok(rows, C, C, ln=True))
           else em.layer_norm(t1, rows, C, tb + "norm2.", feeds=("attn2.q",), stats=st))
@@ -222,32 +218,30 @@ def emit_spatial_transformer(em: Emitter, P: str, l: Layer, x: Act, kv: ContextK
     vt_lo = vt3[:, off:off + C, kv.ldv:] if kv.split >= 2 else None
     ctx = (k_view, vt_view, kv.Nctx * kv.k_all.stride(0), kv.sumC * ldv_all, ldv_all, kv.Nctx, k_lo, vt_lo)
     fused_ff = em.ffn_ok(rows, C)           # (edtr_ffn takes the row statistics from the rows it holds: no row_stats from attn.out)
-    t2 = emit_attention_core(em, tb + "attn2.", l2, B, N, C, l.heads, ctx, t1, row_stats=fold and not fused_ff)
-    st = em.last_row_stats
+    a2 = emit_attention_core(em, tb + "attn2.", l2, B, N, C, l.heads, ctx, t1, row_stats=fold and not fused_ff)
+    t2, st = a2.t, a2.row_stats
     em.free(l2, t1)
     if fused_ff:
         # norm3 + ff.geglu + ff.out + residual as ONE launch on the raw rows (edtr_ffn: the (rows, 4 C) hidden tensor stays on chip)
-        t3 = em.ffn(t2, rows, C, tb)
+        t3 = em.ffn(t2, rows, C, tb).t
         em.free(t2)
     else:
         l3 = em.layer_norm(t2, rows, C, tb + "norm3.", feeds=("ff.geglu",), stats=st)
         if isinstance(l3, LNRef):
             wg, bg, c1, c2 = em.store.ln_fold("geglu", [tb + "ff.net.0.proj.weight"], [tb + "ff.net.0.proj.bias"], l3.prefix)
-            g = em.gemm(l3, wg, rows, 8 * C, C, bias=bg, act=L.ACT_GEGLU, name="ff.geglu", feeds="ff.out", ln_vec=(c1, c2))
+            g = em.gemm(l3, wg, rows, 8 * C, C, bias=bg, act=L.ACT_GEGLU, name="ff.geglu", feeds="ff.out", ln_vec=(c1, c2)).t
         else:
             wg, bg = em.store.geglu(tb + "ff.net.0.proj.weight", tb + "ff.net.0.proj.bias")
-            g = em.gemm(l3, wg, rows, 8 * C, C, bias=bg, act=L.ACT_GEGLU, name="ff.geglu", feeds="ff.out")
+            g = em.gemm(l3, wg, rows, 8 * C, C, bias=bg, act=L.ACT_GEGLU, name="ff.geglu", feeds="ff.out").t
         em.free(l3)
         wf, bf = em.store.linear([tb + "ff.net.2.weight"], [tb + "ff.net.2.bias"])
-        t3 = em.gemm(g, wf, rows, C, 4 * C, bias=bf, residual=t2, name="ff.out", feeds="st.proj_out" if em.branch16 else None)
+        t3 = em.gemm(g, wf, rows, C, 4 * C, bias=bf, residual=t2, name="ff.out", feeds="st.proj_out" if em.branch16 else None).t
         em.free(g, t2)
     wo, bo = em.store.linear([p + "proj_out.weight"], [p + "proj_out.bias"])
     y = em.gemm(t3, wo, rows, C, C, bias=bo, residual=x.t, out=out, name="st.proj_out", stats_hw=N if (out is None or gnp_into is not None) else 0,
                 mirror=mirror, gnp_into=gnp_into if out is not None else None)
-    into_done = em.gnp_into_done
     em.free(t3)
-    em.gnp_into_done = into_done
-    return Act(y, x.B, x.H, x.W, C, em.last_gnp, gn_slot=em.last_gn_slot)
+    return Act(y.t, x.B, x.H, x.W, C, y.gnp, gn_slot=y.gn_slot, stats_shared=y.stats_shared)
 
 
 def mirror_for(em: Emitter, nxt: Optional[Layer]) -> bool:
@@ -288,11 +282,9 @@ def emit_block(em: Emitter, P: str, layers: List[Layer], x: Act, table, offs, kv
             y = em.conv(h, P + l.prefix + "conv.", ups=True, out=tgt, name="upsample.conv", stats=tgt is None, mirror=mir, gnp_into=into)  # unet.py:70-79
         else:
             raise ValueError(l.kind)
-        into_done = em.gnp_into_done if last else False
         if h is not x or not keep_input:
             em.free(h)
         h = y
-    em.gnp_into_done = bool(gnp_into is not None and into_done)
     return h
 
 
@@ -344,8 +336,8 @@ def emit_unet(em: Emitter, P: str, a: UNetArch, x8: Act, table, offs, kv, contro
     cat = em.new_stream(skip.rows, mid.C + skip.C, mirror=em.want_mirror("res.skip1x1"))
     cg, cslot = concat_slots(skip.rows, skip.H * skip.W, mid.C + skip.C)
     c = control.pop() if control is not None else None      # a None entry = no control at that tap (only_mid_control)
-    em.add(mid.t, c.t if c is not None else None, mid.rows, mid.C, out=cat[:, :mid.C], stats_into=(cg, 0, cslot) if cg is not None else None)
-    if cg is not None and not em.add_stats_done:
+    left = em.add(mid.t, c.t if c is not None else None, mid.rows, mid.C, out=cat[:, :mid.C], stats_into=(cg, 0, cslot) if cg is not None else None)
+    if cg is not None and not left.stats_shared:
         em.arena.free(cg)
         cg = None
     if c is not None:
@@ -357,9 +349,9 @@ def emit_unet(em: Emitter, P: str, a: UNetArch, x8: Act, table, offs, kv, contro
     for j, layers in enumerate(a.output_blocks):
         # right half of the concat: skip (+ control)
         c = control.pop() if control is not None else None
-        em.add(skip.t, c.t if c is not None else None, skip.rows, skip.C, out=cat[:, cur_C:],
-               stats_into=(cg, cur_C, cslot) if cg is not None else None)
-        if cg is not None and not em.add_stats_done:
+        right = em.add(skip.t, c.t if c is not None else None, skip.rows, skip.C, out=cat[:, cur_C:],
+                       stats_into=(cg, cur_C, cslot) if cg is not None else None)
+        if cg is not None and not right.stats_shared:
             em.arena.free(cg)
             cg = None
         if c is not None:
@@ -373,7 +365,7 @@ def emit_unet(em: Emitter, P: str, a: UNetArch, x8: Act, table, offs, kv, contro
             ncg, nslot = concat_slots(nskip.rows, nskip.H * nskip.W, out_C + nskip.C)
             y = emit_block(em, P, layers, xin, table, offs, kv, out=ncat[:, :out_C], keep_input=True,
                            gnp_into=(ncg, 0, nslot) if ncg is not None else None)
-            if ncg is not None and not em.gnp_into_done:      # the block's last layer could not write its half: keep the statistics launch
+            if ncg is not None and not y.stats_shared:      # the block's last layer could not write its half: keep the statistics launch
                 em.arena.free(ncg)
                 ncg = None
             em.free(cat)
@@ -438,7 +430,7 @@ def _g_vae_attn(em: Emitter, p: str, x: Act):
         raise ValueError("VAE attention needs h*w to be a multiple of 4")
     n = yield from _g_norm(em, x, p + "norm.", False, ("vae.attn.qk", "vae.attn.vT"))
     wqk, bqk = em.store.linear([p + "q.weight", p + "k.weight"], [p + "q.bias", p + "k.bias"])
-    qk = em.gemm(n.t, wqk, rows, 2 * C, C, bias=bqk, name="vae.attn.qk", out16=True)
+    qk = em.gemm(n.t, wqk, rows, 2 * C, C, bias=bqk, name="vae.attn.qk", out16=True).t
     wv, _ = em.store.linear([p + "v.weight"])
     vt, ldv = em.vt_gemm(wv, n.t, B=B, Ntok=N, Cin=C, bias_m=em.store.vec(p + "v.bias"), name="vae.attn.vT")
     em.free(n)
@@ -473,7 +465,7 @@ def _g_vae_attn(em: Emitter, p: str, x: Act):
     wo, bo = em.store.linear([p + "proj_out.weight"], [p + "proj_out.bias"])
     y = em.gemm(o, wo, rows, C, C, bias=bo, residual=x.t, name="vae.attn.proj_out", stats_hw=N)
     em.free(o)
-    return Act(y, x.B, x.H, x.W, C, em.last_gnp, gn_slot=em.last_gn_slot)
+    return Act(y.t, x.B, x.H, x.W, C, y.gnp, gn_slot=y.gn_slot)
 
 
 def gen_vae_net(em: Emitter, P: str, layers: List[VaeLayer], x: Act, final_f32: bool, final_nchw: Optional[torch.Tensor] = None):

@@ -130,6 +130,55 @@ def release_graphs(cldm: ControlLDM) -> None:
         e.prog.release_graph()
 
 
+def program_signature(recs, arenas) -> list:
+    """One line per launch record of a program: name, tag, flops, bytes, then every scalar argument and every field of every
+    parameter struct verbatim — except pointers, which would differ from run to run and are written as ``0``, as
+    ``A<arena>.<chunk>+<byte offset>`` inside a chunk of one of ``arenas`` (so allocation order and buffer reuse are part of the
+    signature) or as ``X<k>``, k = order of first appearance in the program (weights and static buffers: cache sharing is part
+    of it too).  Which arguments are pointers is read off the C prototypes (edtr_amd/lib.py).  tests/golden/program_signatures.json
+    holds the hashes of these listings as recorded from the commit before a change (tools/make_program_signatures.py)."""
+    import ctypes as ct
+    chunks = sorted((c.data_ptr(), c.data_ptr() + c.numel(), f"A{ai}.{ci}") for ai, a in enumerate(arenas) for ci, c in enumerate(a.chunks))
+    starts = [c[0] for c in chunks]
+    foreign: Dict[int, int] = {}
+
+    def pointer(v) -> str:
+        if not v:
+            return "0"
+        i = bisect.bisect_right(starts, v) - 1
+        if i >= 0 and v < chunks[i][1]:
+            return f"{chunks[i][2]}+{v - chunks[i][0]}"
+        return f"X{foreign.setdefault(v, len(foreign))}"
+
+    def struct(s) -> str:
+        return "{" + " ".join(f"{f}={pointer(getattr(s, f)) if t is ct.c_void_p else repr(getattr(s, f))}" for f, t in s._fields_) + "}"
+
+    lines = []
+    for r in recs:
+        out = [r.name, r.tag, repr(float(r.flops)), repr(float(r.bytes))]
+        for a, t in zip(r.args, r.fn.argtypes):
+            if isinstance(getattr(a, "_obj", None), ct.Structure):      # byref(parameter struct)
+                out.append(struct(a._obj))
+            elif t is ct.c_void_p and (a is None or isinstance(a, int)):
+                out.append(pointer(a))
+            elif isinstance(a, (bool, int, float)):
+                out.append(repr(a))
+            else:
+                raise TypeError(f"{r.name}: no canonical form for argument {a!r}")
+        lines.append(" | ".join(out))
+    return lines
+
+
+def signature_summary(lines) -> Dict[str, object]:
+    """What the golden table keeps of a listing: record count, SHA-256, launches per name (the counts make a mismatch legible) and
+    six hex digits of every record's own SHA-256, in order (they name the first record that differs)."""
+    import collections
+    import hashlib
+    names = collections.Counter(ln.split(" | ", 1)[0] for ln in lines)
+    return {"records": len(lines), "sha256": hashlib.sha256("\n".join(lines).encode()).hexdigest(), "launches": dict(sorted(names.items())),
+            "record_hashes": "".join(hashlib.sha256(ln.encode()).hexdigest()[:6] for ln in lines)}
+
+
 def rel_err(a, b) -> float:
     a = torch.as_tensor(a).double().cpu()
     b = torch.as_tensor(b).double().cpu()
