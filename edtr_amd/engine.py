@@ -983,7 +983,8 @@ class Emitter:
         width alone, where no more is promised: group_norm's conv_n).  ``name``: the convolution's GEMM class; None while it is only
         promised — the parts are then unknown.  ``tail``: the input of a 1x1 convolution that would ride as a K tail.  ``defer``: would
         this convolution apply a GroupNorm of ``x`` that is not deferred yet (asked by gn_deferrable; an ``x`` that carries gn_in asks
-        by itself)?
+        by itself)?  What a tile accepts (fused GroupNorm, sub-pixel form, K tail) is edtr_igemm_plan's answer for the shape
+        (ops.conv3x3_plan, ops.ktail_plan); only the measured policy is decided in Python.
 
         Promise and launch used to derive the split-K count each in their own way; they are one derivation now because
           * with img8 (gn_deferrable passed none): at 8 x 8 ops.gn_in_conv_ok refuses whatever the split is, and nothing else of a

@@ -34,8 +34,8 @@ def stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
-def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
+def ptr(t) -> Optional[int]:      # the address of a tensor; None and integer addresses pass through
+    return t if t is None or isinstance(t, int) else t.data_ptr()
 
 
 class Rec:
@@ -59,27 +59,27 @@ def launch(rec: Rec) -> None:
 # --------------------------------------------------------------------------------------------
 # igemm
 # --------------------------------------------------------------------------------------------
-def make_igemm(*, dtype: torch.dtype, a1: torch.Tensor, w: torch.Tensor, out: torch.Tensor, M: int, N: int,
-               C1: int, ld1: int, ldw: int, ldc: int, taps: int = 1, a2: Optional[torch.Tensor] = None, C2: int = 0,
-               ld2: int = 0, spatial: Optional[Tuple[int, int, int, int, int, int, int, int]] = None, Z: int = 1,
-               zdiv: int = 1, a_zs=(0, 0), w_zs=(0, 0), o_zs=(0, 0), alpha: float = 1.0,
-               bias_n: Optional[torch.Tensor] = None, bias_m: Optional[torch.Tensor] = None,
-               rowvec: Optional[torch.Tensor] = None, rowvec_ld: int = 0, rows_per_image: int = 0, act: int = 0,
-               residual: Optional[torch.Tensor] = None, ldr: int = 0, out_f32: bool = False, n_valid: int = 0,
-               tile: int = 0, splitk: int = 1, workspace: Optional[torch.Tensor] = None,
-               gn_partial: Optional[torch.Tensor] = None, act_slope: float = 0.0, residual_f32: bool = False,
-               vt_out: Optional[torch.Tensor] = None, vt_col0: int = 0, vt_ld: int = 0, vt_alpha: float = 1.0,
-               row_stats: Optional[torch.Tensor] = None, ln_stats: Optional[torch.Tensor] = None, ln_C: int = 0, ln_valid: int = 0,
-               ln_eps: float = 1e-5, ln_c1: Optional[torch.Tensor] = None, ln_c2: Optional[torch.Tensor] = None,
-               w_phase_stride: int = 0, out16: Optional[torch.Tensor] = None, a_wrap: int = 0, a_gn: Optional[torch.Tensor] = None,
-               a_gn_silu: bool = True, gn_slot_rows: int = 0, gn_ld: int = 0, a3: Optional[torch.Tensor] = None, C3: int = 0,
-               name: str = "igemm") -> Rec:
-    p = L.IgemmParams()
-    if a3 is None:
-        C3 = 0
+IGEMM_POINTERS = ("a1", "a2", "w", "out", "bias_n", "bias_m", "rowvec", "residual", "workspace", "gn_partial", "vt_out", "row_stats",
+                  "ln_stats", "ln_c1", "ln_c2", "out16", "a_gn", "a3")       # igemm_params' pointer keywords, in the order a record keeps them alive
+PLAN_ADDR = 0x1000      # a 16-byte-aligned placeholder for the shape-only queries: the planner looks at addresses, never through them
+
+
+def igemm_params(*, dtype: torch.dtype, a1, w, out, M: int, N: int, C1: int, ld1: int, ldw: int, ldc: int, taps: int = 1, a2=None,
+                 C2: int = 0, ld2: int = 0, spatial: Optional[Tuple[int, int, int, int, int, int, int, int]] = None, Z: int = 1,
+                 zdiv: int = 1, a_zs=(0, 0), w_zs=(0, 0), o_zs=(0, 0), alpha: float = 1.0, bias_n=None, bias_m=None, rowvec=None,
+                 rowvec_ld: int = 0, rows_per_image: int = 0, act: int = 0, residual=None, ldr: int = 0, out_f32: bool = False,
+                 n_valid: int = 0, tile: int = 0, splitk: int = 1, workspace=None, workspace_bytes: int = 0, gn_partial=None,
+                 act_slope: float = 0.0, residual_f32: bool = False, vt_out=None, vt_col0: int = 0, vt_ld: int = 0, vt_alpha: float = 1.0,
+                 row_stats=None, ln_stats=None, ln_C: int = 0, ln_valid: int = 0, ln_eps: float = 1e-5, ln_c1=None, ln_c2=None,
+                 w_phase_stride: int = 0, out16=None, ld16: int = 0, a_wrap: int = 0, a_gn=None, a_gn_silu: bool = True,
+                 gn_slot_rows: int = 0, gn_ld: int = 0, a3=None, C3: int = 0, ld3: int = 0, raw: Optional[dict] = None) -> L.IgemmParams:
+    """edtr_igemm_params from keyword arguments: the one place that fills the struct.  Every pointer keyword (IGEMM_POINTERS) takes a
+    tensor, an integer address or None; ``ld3``, ``ld16`` and ``workspace_bytes`` describe an a3 / out16 / workspace that is given as an
+    address (a tensor says them itself).  ``raw``: struct fields set after everything else."""
+    p, C3 = L.IgemmParams(), C3 if a3 is not None else 0
     p.dtype, p.taps, p.M, p.N, p.K = dt_code(dtype), taps, M, N, taps * (C1 + C2) + C3
     if a3 is not None:                    # K tail of a 3x3 convolution: C3 more columns read at the output pixel itself (the 1x1 skip)
-        p.a3, p.C3, p.ld3 = ptr(a3), C3, a3.stride(0)
+        p.a3, p.C3, p.ld3 = ptr(a3), C3, ld3 or a3.stride(0)
     p.n_valid, p.Z, p.zdiv = n_valid, Z, zdiv
     p.a1, p.a2, p.C1, p.C2, p.ld1, p.ld2 = ptr(a1), ptr(a2), C1, C2, ld1, ld2
     p.a_zs_outer, p.a_zs_inner = a_zs
@@ -88,63 +88,74 @@ def make_igemm(*, dtype: torch.dtype, a1: torch.Tensor, w: torch.Tensor, out: to
     p.w, p.ldw = ptr(w), ldw
     p.w_phase_stride = w_phase_stride     # sub-pixel upsample convolution (spatial[7] == 2): four pre-summed phase matrices
     if out16 is not None:                 # fp16 mirror of an fp32 stream output (mixed mode)
-        p.out16, p.ld16 = ptr(out16), out16.stride(0)
+        p.out16, p.ld16 = ptr(out16), ld16 or out16.stride(0)
     p.a_wrap = a_wrap                     # weights-exact two-part product: A columns read twice against [Wh | Wl]
     p.a_gn, p.a_gn_silu = ptr(a_gn), int(a_gn_silu)     # GroupNorm apply (+ SiLU) of the input fused into the halo tile's staging
     p.gn_slot_rows, p.gn_ld = int(gn_slot_rows), int(gn_ld)
     p.w_zs_outer, p.w_zs_inner = w_zs
-    p.alpha = alpha
-    p.bias_n, p.bias_m, p.rowvec = ptr(bias_n), ptr(bias_m), ptr(rowvec)
+    p.alpha, p.bias_n, p.bias_m, p.rowvec = alpha, ptr(bias_n), ptr(bias_m), ptr(rowvec)
     p.rowvec_ld, p.rows_per_image, p.act = rowvec_ld, rows_per_image, act
     p.residual, p.ldr = ptr(residual), ldr
     p.out, p.ldc, p.out_f32 = ptr(out), ldc, int(out_f32)
     p.o_zs_outer, p.o_zs_inner = o_zs
-    p.tile = tile
-    p.splitk = splitk
+    p.tile, p.splitk = tile, splitk
     if splitk > 1:
-        p.workspace, p.workspace_bytes = ptr(workspace), workspace.numel() * workspace.element_size()
-    p.gn_partial = ptr(gn_partial)
-    p.act_slope = act_slope
-    p.residual_f32 = int(residual_f32)
+        p.workspace, p.workspace_bytes = ptr(workspace), workspace_bytes or workspace.numel() * workspace.element_size()
+    p.gn_partial, p.act_slope, p.residual_f32 = ptr(gn_partial), act_slope, int(residual_f32)
     if vt_out is not None:
         p.vt_out, p.vt_col0, p.vt_ld, p.vt_alpha = ptr(vt_out), vt_col0, vt_ld, vt_alpha
     p.row_stats = ptr(row_stats)
     if ln_stats is not None:
         p.ln_stats, p.ln_slots, p.ln_C, p.ln_eps, p.ln_c1, p.ln_c2 = ptr(ln_stats), ln_C // 32, ln_valid or ln_C, ln_eps, ptr(ln_c1), ptr(ln_c2)
+    for k, v in (raw or {}).items():
+        setattr(p, k, v)
+    return p
+
+
+def make_igemm(*, name: str = "igemm", **kw) -> Rec:
+    """The launch record of one edtr_igemm call.  The keywords are igemm_params', with tensors for the pointers."""
+    p = igemm_params(**kw)
+    has = {k: kw.get(k) is not None for k in IGEMM_POINTERS}
+    M, N, Z, C1, C2, taps, act, splitk, spatial = p.M, p.N, p.Z, p.C1, p.C2, p.taps, p.act, p.splitk, kw.get("spatial")
     flops = 2.0 * M * N * p.K * Z
     # algorithmic HBM bytes: every operand once (a conv reads its input image once, not once per tap)
     a_rows = (M // (p.OH * p.OW)) * p.IH * p.IW if spatial else M
     n_out = N // 2 if act == L.ACT_GEGLU else N
-    nbytes = Z * (2.0 * a_rows * (C1 + C2) + 2.0 * M * C3 + 2.0 * N * p.K + (4.0 if out_f32 else 2.0) * M * n_out
-                  + ((4.0 if residual_f32 else 2.0) * M * n_out if residual is not None else 0.0))
-    rec = Rec(L.load().edtr_igemm, (ct.byref(p),), (p, a1, a2, w, out, bias_n, bias_m, rowvec, residual, workspace,
-                                                    gn_partial, vt_out, row_stats, ln_stats, ln_c1, ln_c2, out16, a_gn, a3), name, flops, nbytes)
+    nbytes = Z * (2.0 * a_rows * (C1 + C2) + 2.0 * M * p.C3 + 2.0 * N * p.K + (4.0 if p.out_f32 else 2.0) * M * n_out
+                  + ((4.0 if p.residual_f32 else 2.0) * M * n_out if has["residual"] else 0.0))
+    rec = Rec(L.load().edtr_igemm, (ct.byref(p),), (p,) + tuple(kw.get(k) for k in IGEMM_POINTERS), name, flops, nbytes)
     rec.tag = (f"taps{taps} M{M} N{N} K{p.K} Z{Z}" + (f" C2={C2}" if C2 else "") + (f" s{p.stride}" if spatial and p.stride != 1 else "")
                + ((" up2" if p.upsample2x == 1 else " up2sp") if spatial and p.upsample2x else "") + (f" sk{splitk}" if splitk > 1 else "") + (f" act{act}" if act else "")
-               + (" f32" if out_f32 else "") + (" gnp" if gn_partial is not None else "") + (" vT" if vt_out is not None else "")
-               + (" ln" if ln_stats is not None else "") + (" rs" if row_stats is not None else "")
-               + (" m16" if out16 is not None else "") + (" 2w" if a_wrap else "") + (" gnin" if a_gn is not None else "")
-               + (" kt" if a3 is not None else ""))
+               + (" f32" if p.out_f32 else "") + (" gnp" if has["gn_partial"] else "") + (" vT" if has["vt_out"] else "") + (" ln" if has["ln_stats"] else "")
+               + (" rs" if has["row_stats"] else "") + (" m16" if has["out16"] else "") + (" 2w" if p.a_wrap else "") + (" gnin" if has["a_gn"] else "")
+               + (" kt" if has["a3"] else ""))
     return rec
 
 
-def ktail_plan(dtype: torch.dtype, B: int, H: int, W: int, C1: int, ld1: int, N: int, C3: int, ld3: int, splitk: int = 1,
-               a_gn: bool = False) -> int:
-    """edtr_igemm_plan for the 3x3 / stride 1 / pad 1 convolution of a [B, H, W, C1] activation with a K tail of C3 columns and the
-    library's own tile choice: the tile that would run (16 / 17 / 20), or < 0 where no tile takes the tail at that shape.  Shapes
-    only (the pointers are placeholders), no launch, no device."""
-    p = L.IgemmParams()
-    M, fake = B * H * W, 0x1000
-    p.dtype, p.taps, p.M, p.N, p.K, p.Z, p.zdiv = dt_code(dtype), 9, M, N, 9 * C1 + C3, 1, 1
-    p.a1, p.C1, p.ld1, p.a3, p.C3, p.ld3 = fake, C1, ld1, fake, C3, ld3
-    p.IH, p.IW, p.OH, p.OW, p.stride, p.pad_t, p.pad_l = H, W, H, W, 1, 1, 1
-    p.w, p.ldw, p.out, p.ldc, p.alpha, p.bias_n = fake, 9 * C1 + C3, fake, N, 1.0, fake
-    p.rows_per_image, p.splitk = H * W, splitk
-    if splitk > 1:
-        p.workspace, p.workspace_bytes = fake, splitk * M * N * 4
-    if a_gn:
-        p.a_gn, p.a_gn_silu = fake, 1
-    return int(L.load().edtr_igemm_plan(ct.byref(p)))
+def igemm_plan(*, raw: Optional[dict] = None, **kw) -> int:
+    """edtr_igemm_plan for igemm_params' keywords, from shapes alone: the tile that would run, or the negative error.  PLAN_ADDR stands
+    in for a1, w and out, for a split-K workspace (of splitk * M * N * 4 bytes) and for every pointer keyword given as True.  No
+    launch, no device.  ``raw``: struct fields set after everything else (a K that does not count its tail ...)."""
+    slabs = dict(workspace=PLAN_ADDR, workspace_bytes=kw["splitk"] * kw["M"] * kw["N"] * 4) if kw.get("splitk", 1) > 1 else {}
+    kw = {"a1": PLAN_ADDR, "w": PLAN_ADDR, "out": PLAN_ADDR, **slabs,
+          **{k: (PLAN_ADDR if v else None) if k in IGEMM_POINTERS and isinstance(v, bool) else v for k, v in kw.items()}}
+    return int(L.load().edtr_igemm_plan(ct.byref(igemm_params(raw=raw, **kw))))
+
+
+def conv3x3_plan(B: int, H: int, W: int, C: int, N: int, *, dtype: torch.dtype = torch.bfloat16, ld: int = 0, splitk: int = 1,
+                 tail: Optional[Tuple[int, int]] = None, subpixel: bool = False, raw: Optional[dict] = None, **kw) -> int:
+    """igemm_plan for the 3x3 / stride 1 / pad 1 convolution of a [B, H, W, C] activation (row stride ``ld`` or C) into N channels.
+    ``tail`` = (C3, ld3): with a K tail of C3 columns; ``subpixel``: the sub-pixel form of the nearest-2x upsample convolution (four
+    phase matrices of [N][4 C]).  Further keywords (a_gn=True, tile, residual ...) are igemm_plan's."""
+    up, (C3, ld3) = 2 if subpixel else 1, tail or (0, 0)
+    weights = dict(ldw=4 * C, w_phase_stride=N * 4 * C) if subpixel else dict(ldw=9 * C + C3)
+    return igemm_plan(dtype=dtype, taps=9, M=B * up * H * up * W, N=N, C1=C, ld1=ld or C, ldc=N, splitk=splitk,
+                      spatial=(H, W, up * H, up * W, 1, 1, 1, 2 if subpixel else 0), a3=bool(tail), C3=C3, ld3=ld3, raw=raw, **weights, **kw)
+
+
+def ktail_plan(dtype: torch.dtype, B: int, H: int, W: int, C1: int, ld1: int, N: int, C3: int, ld3: int, splitk: int = 1, a_gn: bool = False) -> int:
+    """conv3x3_plan with a K tail of C3 columns: the tile that would run (16 / 17 / 20), or < 0 where no tile takes the tail at that shape."""
+    return conv3x3_plan(B, H, W, C1, N, dtype=dtype, ld=ld1, splitk=splitk, a_gn=a_gn, tail=(C3, ld3))
 
 
 def ktail_enabled() -> bool:
@@ -578,30 +589,19 @@ def make_gn_table(*, partial, tiles_per_image, sums, B, C, HW, gamma, beta, eps,
                (partial, sums, gamma, beta, table), name)
 
 
-def igemm_fast_addressable(rows_in: int, ld: int, IW: int, K: int, N: int, ldw: int) -> bool:
-    """Mirror of csrc/igemm_plan.h: igemm_fast_addressable — the buffer-addressed kernels (every LDS-DMA tile, the halo tiles) reach their
-    operands through 32-bit byte offsets; edtr_igemm answers EDTR_E_UNSUPPORTED for an explicit halo request beyond that, so the
-    predicates below must not promise the halo tile there (the untiled 1024 x 1024 decode at batch 8 has a 4.29-GB
-    operand).  tests/test_host_logic.py checks the predicates against edtr_igemm_plan."""
-    a_bytes = (rows_in + 3 * IW + 3) * ld * 2 + K * 2
-    w_bytes = N * ldw * 2 + K * 2
-    return a_bytes < 0xF0000000 and w_bytes < 0xF0000000
-
-
 def gn_in_conv_ok(B: int, H: int, W: int, C: int, N: int, splitk: int = 1, ld: int = 0) -> bool:
-    """Does the halo tile take this 3x3 / stride 1 / pad 1 convolution in its 16 x 16-patch geometry with the GroupNorm of its input
-    fused into the patch staging (edtr_hip.h: a_gn)?  The shape rules of edtr_igemm's automatic halo choice: 128-column tiles
-    without padding and >= 48 units — and N <= EDTR_GN_IN_CONV_MAXN (default 128): measured on the MI355X (profiles/r04/gn_in_conv_ab.log),
+    """Should this 3x3 / stride 1 / pad 1 convolution run with the GroupNorm of its input fused into a halo tile's patch staging
+    (edtr_hip.h: a_gn)?  Measured policy first: the thresholds of edtr_igemm's automatic halo choice, 128-column tiles without padding
+    and >= 48 units — and N <= EDTR_GN_IN_CONV_MAXN (default 128): measured on the MI355X (profiles/r04/gn_in_conv_ab.log),
     the fused form wins where ONE 128-column tile covers the output channels (the VAE's 512 x 512 level: headline +1.4 %) and loses
     beyond (N = 256: -0.5 % against that, N = 512 / 640 / 1280: the whole path -1 .. -2 %), because every column tile of a patch
-    normalises the patch again.  EDTR_GN_IN_CONV=0 keeps the edtr_gn_apply launch everywhere (A/B runs)."""
+    normalises the patch again.  EDTR_GN_IN_CONV=0 keeps the edtr_gn_apply launch everywhere (A/B runs).  Whether a tile takes the
+    launch is the planner's word (conv3x3_plan): its geometry, split-K and addressability rules are stated in csrc/igemm_plan.h only."""
     if os.environ.get("EDTR_GN_IN_CONV", "1") == "0" or os.environ.get("EDTR_IGEMM_HALO", "1") == "0":
         return False
-    if H % 16 or W % 16 or C % 64 or N % 128 or (H, W) == (8, 8) or N > int(os.environ.get("EDTR_GN_IN_CONV_MAXN", "128")):
+    if N % 128 or N > int(os.environ.get("EDTR_GN_IN_CONV_MAXN", "128")) or (B * H * W // 256) * (N // 128) * max(splitk, 1) < 48:
         return False         # (every 128-column tile of the convolution normalises the whole patch again: N / 128 times the arithmetic of edtr_gn_apply)
-    if max(splitk, 1) > C // 64 or not igemm_fast_addressable(B * H * W, ld or C, W, 9 * C, N, 9 * C):
-        return False         # (edtr_igemm's own preconditions for the halo tile: split-K over whole chunks, 32-bit operand offsets)
-    return (B * H * W // 256) * (N // 128) * max(splitk, 1) >= 48
+    return conv3x3_plan(B, H, W, C, N, ld=ld, splitk=splitk, a_gn=True) > 0
 
 
 def gn_slot_rows(hw: int) -> int:
@@ -612,7 +612,7 @@ def gn_slot_rows(hw: int) -> int:
     return 64 if hw == 64 else 0
 
 
-def gn_fusable(M: int, N: int, C1: int, hw: int, taps: int = 1, C2: int = 0, splitk: int = 1, invariant: bool = False) -> bool:
+def gn_fusable(M: int, N: int, C1: int, hw: int, C2: int = 0, splitk: int = 1, invariant: bool = False) -> bool:
     """Can the producing edtr_igemm also emit GroupNorm partials?  Without split-K: whole 128-row tiles inside one image on the
     128x128 kernels.  With split-K (round 6) the REDUCER writes them: any slot size gn_slot_rows() knows, N % 32 == 0.
     EDTR_GN_SPLITK_STATS=0 keeps the edtr_gn_stats launch behind split-K producers (A/B runs)."""
@@ -1447,15 +1447,14 @@ def pack_conv_weight_subpixel(w: torch.Tensor, dtype, cin_pad: Optional[int] = N
 
 
 def subpixel_ok(H: int, W: int, Ce: int, N: int, B: int, ld: int = 0) -> bool:
-    """Does the halo kernel's sub-pixel geometry take this nearest-2x upsample convolution (source H x W, Ce operand channels incl.
-    parts, N output channels)?  16 x 16 source blocks, 64-channel chunks, 128-column tiles, and enough units to be worth a
-    146-KiB workgroup (the halo tile's own threshold).  EDTR_SUBPIXEL=0 keeps the 9-tap gather (A/B runs)."""
-    if os.environ.get("EDTR_SUBPIXEL", "1") == "0":
-        return False
+    """Should this nearest-2x upsample convolution (source H x W, Ce operand channels incl. parts, N output channels) run in its
+    sub-pixel form?  Policy: 128-column tiles and enough units to be worth a 146-KiB workgroup (the halo tile's own threshold);
+    whether the halo kernel's sub-pixel geometry takes the launch is the planner's word (conv3x3_plan answers 16).  EDTR_SUBPIXEL=0
+    keeps the 9-tap gather (A/B runs)."""
     units = B * (H // 16) * (W // 16) * 4 * ((N + 127) // 128)
-    if not igemm_fast_addressable(B * H * W, ld or Ce, W, 9 * Ce, 4 * N, 4 * Ce):     # (four phase matrices of [N][4 Ce])
+    if os.environ.get("EDTR_SUBPIXEL", "1") == "0" or N % 128 or units < 48:
         return False
-    return H % 16 == 0 and W % 16 == 0 and Ce % 64 == 0 and N % 128 == 0 and units >= 48
+    return conv3x3_plan(B, H, W, Ce, N, ld=ld, subpixel=True) == 16
 
 
 def pack_linear_weight(w: torch.Tensor, dtype, n_pad: Optional[int] = None, parts: int = 1) -> torch.Tensor:

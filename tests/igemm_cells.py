@@ -279,8 +279,8 @@ def layout(c, dtype_code=0, shape=None, tile=None):
     return f, ptrs, slabs
 
 
-def to_params(fields, ptrs, addr=None):
-    """edtr_igemm_params from layout()'s fields; pointer fields from `addr` (name -> address), placeholders without."""
+def to_params(fields, ptrs=(), addr=None):
+    """edtr_igemm_params from a dict of fields (layout()'s); the pointer fields `ptrs` from `addr` (name -> address), placeholders without."""
     from edtr_amd import lib as L
     p = L.IgemmParams()
     for k, v in fields.items():

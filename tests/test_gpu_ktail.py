@@ -204,15 +204,9 @@ def test_rejections():
     x2 = torch.zeros((c.M, 64), dtype=torch.bfloat16, device=c.d)
 
     def params(**kw):
-        p = L.IgemmParams()
-        p.dtype, p.taps, p.M, p.N, p.K, p.Z, p.zdiv = L.BF16, 9, c.M, c.N, c.K, 1, 1
-        p.a1, p.C1, p.ld1, p.a3, p.C3, p.ld3 = c.xn.data_ptr(), c.C1, c.C1, c.x.data_ptr(), c.C3, c.x.stride(0)
-        p.IH, p.IW, p.OH, p.OW, p.stride, p.pad_t, p.pad_l = c.H, c.W, c.H, c.W, 1, 1, 1
-        p.w, p.ldw, p.out, p.ldc, p.alpha, p.bias_n = c.wcat.data_ptr(), c.K, out.data_ptr(), c.N, 1.0, c.bsum.data_ptr()
-        p.rows_per_image, p.tile = c.H * c.W, 16
-        for k, v in kw.items():
-            setattr(p, k, v)
-        return p
+        return c.ops.igemm_params(dtype=torch.bfloat16, taps=9, M=c.M, N=c.N, a1=c.xn, C1=c.C1, ld1=c.C1, a3=c.x, C3=c.C3, w=c.wcat, ldw=c.K,
+                                  out=out, ldc=c.N, bias_n=c.bsum, spatial=(c.H, c.W, c.H, c.W, 1, 1, 1, 0), rows_per_image=c.H * c.W, tile=16,
+                                  raw=kw)
 
     stream = torch.cuda.current_stream().cuda_stream
     assert lib.edtr_igemm_plan(ctypes.byref(params())) == 16                          # the case itself is a valid launch

@@ -1647,15 +1647,8 @@ def test_halo160_fp32_residual_mirror_and_automatic_choice():
     torch.cuda.synchronize()
     assert rel(outs[20][0], outs[3][0]) < 2e-6 and torch.equal(outs[20][1], outs[20][0].to(dtype))
     # automatic: 256 units (8 images of 64 x 64, N = 320) -> tile 20; 128 units -> not
-    from edtr_amd import lib as L
-    import ctypes as C
     def plan(Bn, Hn, N):
-        p = L.IgemmParams()
-        p.dtype, p.taps, p.M, p.N, p.K, p.Z, p.zdiv = 0, 9, Bn * Hn * Hn, N, 9 * 320, 1, 1
-        p.a1, p.C1, p.ld1, p.w, p.ldw = x.data_ptr(), 320, 320, w.data_ptr(), 9 * 320
-        p.IH, p.IW, p.OH, p.OW, p.stride, p.pad_t, p.pad_l = Hn, Hn, Hn, Hn, 1, 1, 1
-        p.alpha, p.out, p.ldc = 1.0, outs[3][0].data_ptr(), N
-        return L.load().edtr_igemm_plan(C.byref(p))
+        return ops.conv3x3_plan(Bn, Hn, Hn, 320, N)
     assert plan(8, 64, 320) == 20 and plan(4, 64, 320) != 20 and plan(8, 64, 640) != 20
     with pytest.raises(RuntimeError):                        # N = 128 is not a multiple of 160
         ops.launch(ops.make_igemm(dtype=dtype, a1=x, w=w[:128], out=torch.empty((M, 128), dtype=dtype, device=d), taps=9, M=M, N=128, C1=cin, ld1=cin,

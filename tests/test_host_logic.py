@@ -557,54 +557,78 @@ def test_bench_dump_outputs_and_full_only_reports(tmp_path):
     assert res.returncode == 2 and "--full" in res.stderr
 
 
-def test_host_launch_predicates_imply_the_librarys_own(monkeypatch):
-    """ops.gn_in_conv_ok / ops.subpixel_ok decide in Python that the halo tile WILL take a convolution (the
-    emitter then has no edtr_gn_apply launch to fall back to).  They must therefore sit inside edtr_igemm's own rules, including the
-    two they used to omit: 32-bit addressability of the operand and split-K over whole 64-channel chunks.  edtr_igemm_plan answers
-    with the tile the library would run (no launch, no GPU)."""
-    import ctypes as C
-    from edtr_amd import lib as L
-    lib = L.load()
-    for k in ("EDTR_GN_IN_CONV", "EDTR_IGEMM_HALO", "EDTR_SUBPIXEL", "EDTR_GN_IN_CONV_MAXN", "EDTR_IGEMM_HALO512"):
+PREDICATE_TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "launch_predicates.json")
+# what the table is recorded for (tools/make_predicate_table.py) and checked for: name -> environment
+PREDICATE_SETTINGS = {"default": {}, "GN_IN_CONV_MAXN=512": {"EDTR_GN_IN_CONV_MAXN": "512"}, "GN_IN_CONV=0": {"EDTR_GN_IN_CONV": "0"},
+                      "SUBPIXEL=0": {"EDTR_SUBPIXEL": "0"}}
+PREDICATE_SWITCHES = ("EDTR_GN_IN_CONV", "EDTR_IGEMM_HALO", "EDTR_SUBPIXEL", "EDTR_GN_IN_CONV_MAXN", "EDTR_IGEMM_HALO512")
+
+
+def predicate_cases():
+    """{predicate: argument tuples of ops.gn_in_conv_ok / ops.subpixel_ok}: from 8 x 8 images to the 4.29-GB operands, split-K counts
+    above C / 64, dense and column-slice row strides."""
+    HW = [(8, 8), (8, 16), (16, 16), (16, 32), (24, 16), (32, 32), (40, 40), (64, 48), (64, 64), (128, 128), (256, 256), (512, 512),
+          (1024, 1024), (2048, 1024)]
+    shapes = [(B, H, W, C, N) for B in (1, 2, 3, 4, 8, 12, 16) for (H, W) in HW for C in (32, 64, 96, 128, 192, 256, 320, 512, 640, 1280)
+              for N in (64, 128, 160, 256, 320, 512) if 4 * B * H * W < 2 ** 31]          # (M of the upsampled output fits an int)
+    return {"gn_in_conv": [(B, H, W, C, N, splitk, ld) for (B, H, W, C, N) in shapes for splitk in (1, 2, 3, 6, 10) for ld in (C, 3 * C)],
+            "subpixel": [(H, W, C, N, B, ld) for (B, H, W, C, N) in shapes for ld in (C, 3 * C)]}
+
+
+def predicate_answers(ops_module, cases):
+    """{predicate: one bool per case} from ``ops_module`` under the environment as it stands."""
+    return {"gn_in_conv": [bool(ops_module.gn_in_conv_ok(*c)) for c in cases["gn_in_conv"]],
+            "subpixel": [bool(ops_module.subpixel_ok(*c)) for c in cases["subpixel"]]}
+
+
+def bits_hex(bits) -> str:
+    """The first case is the highest bit of the first hex digit; the last digit is padded with zeros."""
+    s = "".join("1" if b else "0" for b in bits)
+    s += "0" * (-len(s) % 4)
+    return format(int(s, 2), "0%dx" % (len(s) // 4))
+
+
+def test_launch_predicates_answer_as_recorded(monkeypatch):
+    """ops.gn_in_conv_ok / ops.subpixel_ok decide in Python that the halo tile WILL take a convolution (the emitter then has no
+    edtr_gn_apply launch to fall back to).  They are measured policy AND edtr_igemm_plan's answer; the table holds what the
+    hand-written rules they replaced answered (tools/make_predicate_table.py, from the commit before), bit for bit, per switch setting."""
+    with open(PREDICATE_TABLE) as fh:
+        table = json.load(fh)
+    assert os.path.getsize(PREDICATE_TABLE) < 100 * 1024
+    cases = predicate_cases()
+    assert table["cases"] == {k: len(v) for k, v in cases.items()} == {"gn_in_conv": 58800, "subpixel": 11760}
+    assert sorted(table["settings"]) == sorted(PREDICATE_SETTINGS)
+    for setting, env in PREDICATE_SETTINGS.items():
+        for k in PREDICATE_SWITCHES:
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        got = predicate_answers(ops, cases)
+        for name, want in table["settings"][setting].items():
+            assert len(want["bits"]) == (len(cases[name]) + 3) // 4
+            old = format(int(want["bits"], 16), "0%db" % (4 * len(want["bits"])))
+            first = next((i for i, g in enumerate(got[name]) if g != (old[i] == "1")), None)
+            assert first is None, f"{setting} / {name}: case {first} {cases[name][first]} was {old[first]}, is {got[name][first]}"
+            assert want["accepted"] == sum(got[name]) == old.count("1") and bits_hex(got[name]) == want["bits"]
+    default = table["settings"]["default"]
+    assert default["gn_in_conv"]["accepted"] == 2087 and default["subpixel"]["accepted"] == 2496        # (>= 1000 each: no all-refused table)
+    for k in PREDICATE_SWITCHES:
         monkeypatch.delenv(k, raising=False)
-    dummy = C.create_string_buffer(64)
-    base = C.addressof(dummy) & ~15
-
-    def plan(B, H, W, cin, N, *, ld=None, splitk=1, a_gn=False, ups=0, ldw=None, K=None, phase=0):
-        p = L.IgemmParams()
-        OH, OW = (2 * H, 2 * W) if ups else (H, W)
-        p.dtype, p.taps, p.M, p.N, p.K, p.Z, p.zdiv = 0, 9, B * OH * OW, N, K or 9 * cin, 1, 1
-        p.a1, p.C1, p.ld1, p.w, p.ldw = base, cin, ld or cin, base, ldw or 9 * cin
-        p.IH, p.IW, p.OH, p.OW, p.stride, p.pad_t, p.pad_l, p.upsample2x = H, W, OH, OW, 1, 1, 1, ups
-        p.alpha, p.out, p.ldc, p.tile, p.splitk = 1.0, base, N, 0, splitk
-        if splitk > 1:
-            p.workspace, p.workspace_bytes = base, splitk * p.M * N * 4
-        if a_gn:
-            p.a_gn, p.a_gn_silu = base, 1
-        p.w_phase_stride = phase
-        return lib.edtr_igemm_plan(C.byref(p))
-
+    got = predicate_answers(ops, cases)
+    # every accepted case is one the library takes, on both halo tiles that apply a GroupNorm and on the sub-pixel geometry
     seen = {16: 0, 17: 0}
-    shapes = [(8, 512, 512, 128, 128), (8, 1024, 1024, 128, 128), (8, 1024, 1024, 256, 128), (1, 64, 64, 64, 128), (4, 32, 32, 128, 128), (8, 16, 16, 1280, 128),
-              (8, 256, 256, 256, 256), (2, 16, 16, 192, 128), (3, 64, 64, 64, 128), (8, 64, 48, 128, 128), (8, 2048, 1024, 128, 128)]
-    for (B, H, W, cin, N) in shapes:
-        for splitk in (1, 2, 3, 6):
-            for ld in (cin, 2 * cin):
-                if ops.gn_in_conv_ok(B, H, W, cin, N, splitk, ld):
-                    t = plan(B, H, W, cin, N, ld=ld, splitk=splitk, a_gn=True)
-                    assert t in (16, 17), (B, H, W, cin, N, splitk, ld, t)
-                    seen[t] += 1
+    for (B, H, W, cin, N, splitk, ld) in (c for c, ok in zip(cases["gn_in_conv"], got["gn_in_conv"]) if ok):
+        t = ops.conv3x3_plan(B, H, W, cin, N, ld=ld, splitk=splitk, a_gn=True)
+        assert t in (16, 17), (B, H, W, cin, N, splitk, ld, t)
+        seen[t] += 1
     assert seen[16] and seen[17]
-    # the cases the old predicates got wrong are now refused by the predicate (and by the library, which is why they must be)
-    assert not ops.gn_in_conv_ok(8, 1024, 1024, 256, 128, 1, 256) and plan(8, 1024, 1024, 256, 128, a_gn=True) < 0       # 4.29-GB operand
+    # refused by the predicate (and by the library, which is why they must be)
+    assert not ops.gn_in_conv_ok(8, 1024, 1024, 256, 128, 1, 256) and ops.conv3x3_plan(8, 1024, 1024, 256, 128, a_gn=True) < 0       # 4.29-GB operand
     assert not ops.gn_in_conv_ok(8, 16, 16, 128, 128, 6, 128)                                                           # 6 splits of 2 chunks
     n_sub = 0
-    for (B, H, W, Ce, N) in [(8, 256, 256, 256, 256), (8, 128, 128, 512, 512), (8, 32, 32, 640, 640), (2, 16, 16, 64, 128), (8, 512, 512, 768, 128),
-                             (8, 1024, 1024, 384, 128)]:
-        for ld in (Ce, 3 * Ce):
-            if ops.subpixel_ok(H, W, Ce, N, B, ld):
-                assert plan(B, H, W, Ce, N, ld=ld, ups=2, ldw=4 * Ce, phase=N * 4 * Ce) == 16, (B, H, W, Ce, N, ld)
-                n_sub += 1
+    for (H, W, Ce, N, B, ld) in (c for c, ok in zip(cases["subpixel"], got["subpixel"]) if ok):
+        assert ops.conv3x3_plan(B, H, W, Ce, N, ld=ld, subpixel=True) == 16, (B, H, W, Ce, N, ld)
+        n_sub += 1
     assert n_sub >= 4 and not ops.subpixel_ok(1024, 1024, 384, 128, 8, 384)
 
 
@@ -694,23 +718,9 @@ def test_ffn_host_packing_matches_the_header():
 def test_tile21_is_opt_in_and_refuses_what_it_cannot_hold():
     """Tile 21 (the persistent form of tile 17 with deferred stores, round 6) runs only when asked for: 16-bit output, no residual, no
     time-embedding row, an even number of 32-channel chunks (edtr_igemm_plan: every check of the launch, no HIP call)."""
-    import ctypes as C
-    from edtr_amd import lib as L
-    lib = L.load()
-    buf = (C.c_char * 4096)()
-    base = C.addressof(buf) & ~15
-
     def plan(tile, cin=64, N=128, residual=False, out_f32=False, rowvec=False, H=512, W=512):
-        p = L.IgemmParams()
-        p.dtype, p.taps, p.M, p.N, p.K, p.Z, p.zdiv = 0, 9, H * W, N, 9 * cin, 1, 1
-        p.a1, p.C1, p.ld1, p.w, p.ldw = base, cin, cin, base, 9 * cin
-        p.IH, p.IW, p.OH, p.OW, p.stride, p.pad_t, p.pad_l = H, W, H, W, 1, 1, 1
-        p.alpha, p.out, p.ldc, p.tile, p.splitk, p.out_f32 = 1.0, base, N, tile, 1, int(out_f32)
-        if residual:
-            p.residual, p.ldr = base, N
-        if rowvec:
-            p.rowvec, p.rowvec_ld, p.rows_per_image = base, N, H * W
-        return lib.edtr_igemm_plan(C.byref(p))
+        return ops.conv3x3_plan(1, H, W, cin, N, tile=tile, out_f32=out_f32, residual=residual, ldr=N, rowvec=rowvec, rowvec_ld=N,
+                                rows_per_image=H * W)
 
     assert plan(21) == 21 and plan(21, cin=128, N=256) == 21
     assert plan(0) == 17                                            # the automatic choice stays tile 17 (EDTR_IGEMM_HALO512P is the A/B switch)

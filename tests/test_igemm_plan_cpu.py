@@ -15,9 +15,11 @@ import shutil
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+for _p in (HERE, ROOT):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
 
 TABLE = os.path.join(ROOT, "tests", "golden", "igemm_plan_table.json")
 BREAKDOWN = os.path.join(ROOT, "profiles", "r06", "bench_det512_b8_bf16.breakdown.json")
@@ -437,14 +439,6 @@ def generate():
 
 
 # ---- evaluation ----------------------------------------------------------------------------------------------------------------------
-def to_params(d):
-    from edtr_amd import lib as L
-    p = L.IgemmParams()
-    for k, v in d.items():
-        setattr(p, k, v)
-    return p
-
-
 def case_bytes(cases):
     return [bytes(to_params(d)) for d in cases]
 
@@ -502,6 +496,7 @@ if __name__ == "__main__":
 
 
 import pytest  # noqa: E402
+from igemm_cells import to_params  # noqa: E402  (a case is a dict of fields, pointers included; the child above needs neither)
 
 
 @pytest.fixture(scope="module")

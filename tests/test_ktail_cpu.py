@@ -58,7 +58,7 @@ def test_packed_tail_weight_and_summed_bias():
 def test_plan_takes_a_tail_on_the_halo_tiles_only():
     """edtr_igemm_plan (no device) for the headline's shapes: tile 16 (8 x 8 images with split-K, 16 x 16 patches), tile 20, tile 17
     (also with the fused input GroupNorm) — and UNSUPPORTED wherever another tile would run, or the geometry is not the plain one."""
-    from edtr_amd import lib, ops
+    from edtr_amd import ops
     bf = torch.bfloat16
     plan = ops.ktail_plan
     assert plan(bf, 8, 8, 8, 1280, 1280, 1280, 2560, 2560, splitk=10) == 16         # 8 x 8 level, four images per workgroup
@@ -75,15 +75,7 @@ def test_plan_takes_a_tail_on_the_halo_tiles_only():
     assert plan(bf, 8, 32, 32, 640, 640, 640, 320, 320, a_gn=True) == UNSUPPORTED   # tile 16 normalises no tail operand apart
 
     def explicit(**kw):
-        p = lib.IgemmParams()
-        B, H, W, C1, N, C3 = 8, 32, 32, 128, 128, 64
-        p.dtype, p.taps, p.M, p.N, p.K, p.Z, p.zdiv = lib.BF16, 9, B * H * W, N, 9 * C1 + C3, 1, 1
-        p.a1, p.C1, p.ld1, p.a3, p.C3, p.ld3 = 0x1000, C1, C1, 0x1000, C3, C3
-        p.IH, p.IW, p.OH, p.OW, p.stride, p.pad_t, p.pad_l = H, W, H, W, 1, 1, 1
-        p.w, p.ldw, p.out, p.ldc, p.alpha = 0x1000, 9 * C1 + C3, 0x1000, N, 1.0
-        for k, v in kw.items():
-            setattr(p, k, v)
-        return lib.load().edtr_igemm_plan(ctypes.byref(p))
+        return ops.conv3x3_plan(8, 32, 32, 128, 128, tail=(64, 64), raw=kw)
 
     assert explicit(tile=16) == 16 and explicit(tile=0) == UNSUPPORTED               # (32 units: the automatic choice is the 128 x 128 loop)
     for t in (1, 2, 3, 6, 8, 14, 21):

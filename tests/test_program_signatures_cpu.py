@@ -8,7 +8,8 @@ that differs and leaves the rebuilt listing in the test's temporary directory; t
 listings, so the two can be diffed line by line.
 
 Every group of programs is built in a fresh child process with a clean EDTR_* environment plus the group's own switches (some
-switches are read once at import or on the first plan); the children of all groups run side by side."""
+switches are read once at import or on the first plan); the children of all groups run side by side.  The same children ask the
+library's planners about every record that has one: what Python promised at emission, the library must take at launch."""
 import json
 import os
 import subprocess
@@ -79,14 +80,30 @@ def _small_engines():
     return out
 
 
+PLANNERS = ("edtr_igemm", "edtr_ffn", "edtr_lin320", "edtr_flash_attn64")     # launches with an edtr_*_plan that answers without a device
+PLANNED = {}            # group -> {"asked": {launch: records}, "refused": [descriptions]}, filled by finish_child
+
+
+def ask_planners(recs, planned: dict) -> None:
+    """The library's own answer for every record of PLANNERS' launches: counted in planned["asked"], a refusal described in
+    planned["refused"]."""
+    from edtr_amd import lib
+    for r in recs:
+        fn = getattr(r.fn, "__name__", "")
+        if fn in PLANNERS:
+            answer = getattr(lib.load(), fn + "_plan")(r.args[0], *((None,) if fn == "edtr_flash_attn64" else ()))
+            planned["asked"][fn] = planned["asked"].get(fn, 0) + 1
+            if answer < 0:
+                planned["refused"].append(f"{fn} {answer}: {r.name} {r.tag}")
+
+
 def build_group(group: str):
-    """Yields (program name, listing) for every program of ``group``, built on the CPU in this process."""
+    """Yields (program name, launch records, arenas) for every program of ``group``, built on the CPU in this process."""
     import torch
     from edtr_amd import synth
     from edtr_amd.model import ControlLDM
     from edtr_amd.model.cldm import CldmEngine, VaeEngine
     from edtr_amd.model.params import skip_init
-    from edtr_amd.testing import program_signature
     _, config, modes, cldm_shapes, vae_args, small = GROUPS[group]
     cfg = synth.tiny_config() if config == "tiny" else synth.sd21_config()
     with skip_init():                  # emission reads shapes only: no state dict is loaded
@@ -98,27 +115,30 @@ def build_group(group: str):
         for shape in cldm_shapes:
             eng = CldmEngine(model, *shape, 77)
             key = f"{config}.{mode}.cldm." + "x".join(map(str, shape))
-            yield key + ".context", program_signature(eng.ctx_prog.recs, [eng.arena, eng.arena_cn])
-            yield key + ".step", program_signature(eng.step_prog.recs, [eng.arena, eng.arena_cn])
+            yield key + ".context", eng.ctx_prog.recs, [eng.arena, eng.arena_cn]
+            yield key + ".step", eng.step_prog.recs, [eng.arena, eng.arena_cn]
         for args in vae_args:
             eng = VaeEngine(model, *args)
-            yield f"{config}.{mode}.vae." + ".".join(map(str, args)), program_signature(eng.prog.recs, [eng.arena])
+            yield f"{config}.{mode}.vae." + ".".join(map(str, args)), eng.prog.recs, [eng.arena]
     if small:
         for name, (recs, arenas) in _small_engines().items():
-            yield name, program_signature(recs, arenas)
+            yield name, recs, arenas
 
 
 def child_main(group: str, dump: str = "") -> None:
     import torch
-    from edtr_amd.testing import signature_summary
+    from edtr_amd.testing import program_signature, signature_summary
     torch.set_num_threads(2)
-    out = {}
-    for name, lines in build_group(group):
+    out, planned = {}, {"asked": {}, "refused": []}
+    for name, recs, arenas in build_group(group):
+        lines = program_signature(recs, arenas)
+        ask_planners(recs, planned)
         out[name] = signature_summary(lines)
         if dump:
             os.makedirs(dump, exist_ok=True)
             with open(os.path.join(dump, f"{group}--{name}.txt"), "w") as fh:
                 fh.write("\n".join(lines) + "\n")
+    print("PLANNED " + json.dumps(planned, sort_keys=True))
     print("SIGNATURES " + json.dumps(out, sort_keys=True))
 
 
@@ -137,6 +157,7 @@ def finish_child(group: str, proc: subprocess.Popen) -> dict:
     lines = [ln for ln in out.splitlines() if ln.startswith("SIGNATURES ")]
     if proc.returncode != 0 or len(lines) != 1:
         raise RuntimeError(f"{group}: the child process failed ({proc.returncode})\n{err[-4000:]}")
+    PLANNED[group] = json.loads(next(ln for ln in out.splitlines() if ln.startswith("PLANNED "))[len("PLANNED "):])
     return json.loads(lines[0][len("SIGNATURES "):])
 
 
@@ -193,6 +214,18 @@ def test_programs_match_the_recorded_signatures(group, rebuilt, table):
             pytest.fail(f"{group} / {name}: records {want[name]['records']} -> {got[group][name]['records']}, launch counts that moved "
                         f"(recorded, rebuilt): {moved or 'none'}\n"
                         + _first_difference(os.path.join(dump, f"{group}--{name}.txt"), group, name, want[name], got[group][name]))
+
+
+def test_the_library_admits_every_launch_the_emitters_promise(rebuilt):
+    """Every edtr_igemm, edtr_ffn, edtr_lin320 and edtr_flash_attn64 record of every rebuilt program, asked of the library's own planner
+    (no device): nothing is refused.  This is what holds the Python-side promises (ops.gn_in_conv_ok, subpixel_ok, gn_fusable,
+    choose_splitk, ffn_ok, lin320_ok, the K tails) inside the library's rules."""
+    assert sorted(PLANNED) == sorted(GROUPS)
+    asked = {fn: sum(p["asked"].get(fn, 0) for p in PLANNED.values()) for fn in PLANNERS}
+    print("records asked of the planners:", asked)
+    assert all(asked.values()), asked
+    refused = [f"{g}: {what}" for g in ORDER for what in PLANNED[g]["refused"]]
+    assert not refused, "%d records refused, the first: %r" % (len(refused), refused[:5])
 
 
 def test_the_table_covers_every_switch_and_mode(table):
