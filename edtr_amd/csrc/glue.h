@@ -1,4 +1,4 @@
-// What the fp32 / uint8 glue kernels share (elementwise.hip, rng.hip, imageio.hip, degrade.hip, degrade2.hip, labels.hip, boxes.hip, coco.hip, coco_acc.hip, cls.hip, rois.hip, det_transform.hip, targets.hip; no
+// What the fp32 / uint8 glue kernels share (elementwise.hip, rng.hip, imageio.hip, degrade.hip, degrade2.hip, labels.hip, boxes.hip, coco.hip, coco_acc.hip, cls.hip, rois.hip, det_transform.hip, targets.hip, seg_loss.hip; no
 // MFMA translation unit includes this file): the grid of a grid-stride launch, the alignment predicates and the batch check of the
 // host side, and the device helpers whose roundings the numpy restatements repeat bit for bit.  ONE definition each: a rounding rule
 // that lived in three files could be fixed in one and drift in the other two.
@@ -91,6 +91,30 @@ __device__ __forceinline__ float bilinear_blend(const float* src, int ih, int iw
     const float* r0 = src + (int64_t)y0 * iw;
     const float* r1 = src + (int64_t)y1 * iw;
     return blend_taps(r0[x0], r0[x1], r1[x0], r1[x1], ty, tx);
+}
+
+// ---- coarse logits: what edtr_seg_confusion_coarse (labels.hip) and the segmentation loss (seg_loss.hip) blend alike ----------------
+
+// element i of the coarse logits, widened exactly to fp32
+template <int DT>
+__device__ __forceinline__ float load1(const void* base, int64_t i) {
+    if (DT == EDTR_LOGITS_F32) return static_cast<const float*>(base)[i];
+    const uint16_t r = static_cast<const uint16_t*>(base)[i];
+    return DT == EDTR_LOGITS_F16 ? F16::to_f32(r) : BF16::to_f32(r);
+}
+
+// an fp32 blend as F.interpolate hands it on in the input's type: rounded to nearest even to fp16 / bf16 (fp32: as it is)
+template <int DT>
+__device__ __forceinline__ float as_stored(float v) {
+    if (DT == EDTR_LOGITS_F16) return F16::to_f32(F16::from_f32(v));
+    if (DT == EDTR_LOGITS_BF16) return BF16::to_f32(BF16::from_f32(v));
+    return v;
+}
+
+// one blended value as argmax sees it: the seven roundings of blend_taps, then the rounding to the input's type
+template <int DT>
+__device__ __forceinline__ float blended(float v00, float v01, float v10, float v11, float ty, float tx) {
+    return as_stored<DT>(blend_taps(v00, v01, v10, v11, ty, tx));
 }
 
 // the lanes of a wave below `lane`, as a ballot mask: popcount(vote & lanes_below(lane)) is a lane's place in an ordered compaction

@@ -165,28 +165,7 @@ __global__ void __launch_bounds__(256) confusion_kernel(const void* logits, cons
 
 constexpr int kTileH = 16, kTileW = 64;     // the output tile of the coarse launch: 16 rows of 16 lanes, four pixels a lane
 constexpr int kPatchFloats = 4096;          // a tile's coarse patch, all n planes as fp32, is staged in LDS while it fits these 16 KiB
-
-// element i of the coarse logits, widened exactly to fp32
-template <int DT>
-__device__ __forceinline__ float load1(const void* base, int64_t i) {
-    if (DT == EDTR_LOGITS_F32) return static_cast<const float*>(base)[i];
-    const uint16_t r = static_cast<const uint16_t*>(base)[i];
-    return DT == EDTR_LOGITS_F16 ? F16::to_f32(r) : BF16::to_f32(r);
-}
-
-// an fp32 blend as F.interpolate hands it on in the input's type: rounded to nearest even to fp16 / bf16 (fp32: as it is)
-template <int DT>
-__device__ __forceinline__ float as_stored(float v) {
-    if (DT == EDTR_LOGITS_F16) return F16::to_f32(F16::from_f32(v));
-    if (DT == EDTR_LOGITS_BF16) return BF16::to_f32(BF16::from_f32(v));
-    return v;
-}
-
-// one blended value as argmax sees it: the seven roundings of blend_taps, then the rounding to the input's type
-template <int DT>
-__device__ __forceinline__ float blended(float v00, float v01, float v10, float v11, float ty, float tx) {
-    return as_stored<DT>(blend_taps(v00, v01, v10, v11, ty, tx));
-}
+// (load1 / as_stored / blended, which the segmentation loss of seg_loss.hip blends with as well, are glue.h's)
 
 // The argmax over the n planes of a lane's four pixels from the staged patch, which holds the planes of one coarse position side by
 // side: patch[position * npad + c], npad = n rounded up to 4.  tap[j]: the offsets of pixel j's four positions (row 0 / 1 x column

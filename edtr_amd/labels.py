@@ -16,7 +16,9 @@ Three layers, as in `degrade`:
 
 `prepare_pair` / `paired_mask` are the data sets' `load_items`, `evaluate` the test loop's tail.  `coarse_confusion` takes the logits
 at the network's stride and scores their bilinear upsample (model/deeplabv3.py:44-47) without storing it; `assemble_segmenter` puts
-the reference's segmenter together from its learned parts so that it ends there (`CoarseLogits`)."""
+the reference's segmenter together from its learned parts so that it ends there (`CoarseLogits`).  `coarse_cross_entropy` is the
+training loss on the same coarse logits (main/seg/train_edtr.py:213), forward and gathered backward without the upsample in either
+direction, and `assemble_training_segmenter` the train-mode twin of `assemble_segmenter` that ends in it."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -160,6 +162,124 @@ def coarse_confusion_reference(coarse, target, size=None, n: Optional[int] = Non
         raise ValueError(f"expected a uint8 target [B, H, W], got {target.shape}")
     return confusion_reference(upsample_logits_reference(coarse, target.shape[1:] if size is None else size, dtype), target, n, sizes,
                                return_pred)
+
+
+SEG_CE_MAX_CLASSES = 256                # EDTR_SEG_CE_MAX_CLASSES
+CE_TILE = (16, 64)                      # the output tile whose fp64 sum is one addend of the loss
+
+
+def _ce_inputs(coarse, target, size, dtype):
+    """(logits as fp32 [B, n, ih, iw], target uint8 [B, H, W]) of the two cross-entropy restatements, checked"""
+    if dtype not in LOGIT_TYPES:
+        raise ValueError(f"dtype must be one of {LOGIT_TYPES}, got {dtype!r}")
+    x, target = np.asarray(coarse), np.asarray(target)
+    if x.ndim != 4 or x.dtype not in (np.float32, np.float16) or 0 in x.shape:
+        raise ValueError(f"expected fp32 / fp16 logits [B, n, ih, iw], got {x.dtype} {x.shape}")
+    if x.shape[1] > SEG_CE_MAX_CLASSES:
+        raise ValueError(f"at most {SEG_CE_MAX_CLASSES} classes, got {x.shape[1]}")
+    if target.dtype != np.uint8 or target.ndim != 3 or target.shape[0] != x.shape[0] or 0 in target.shape:
+        raise ValueError(f"target must be uint8 [B, H, W] with the logits' batch, got {target.dtype} {target.shape}")
+    if size is not None and _hw(size) != tuple(target.shape[1:]):
+        raise ValueError(f"size {_hw(size)} is not the target's extent {tuple(target.shape[1:])}")
+    return np.ascontiguousarray(x.astype(np.float32)), target
+
+
+def _tile_sum(tile: np.ndarray) -> float:
+    """fp64 [16, 64] -> its sum in the order of the launch: a lane's four pixels left to right, then lane i += lane i + o for o = 128 ... 1"""
+    lane = tile.reshape(16, 16, 4)
+    v = (((lane[:, :, 0] + lane[:, :, 1]) + lane[:, :, 2]) + lane[:, :, 3]).reshape(256).copy()
+    o = 128
+    while o:
+        v[:o] = v[:o] + v[o:2 * o]
+        o >>= 1
+    return float(v[0])
+
+
+def coarse_cross_entropy_reference(coarse, target, size=None, ignore_index: int = 255, dtype: str = "float32"):
+    """`F.cross_entropy(F.interpolate(coarse, size=, mode="bilinear", align_corners=False), target, ignore_index=)` by a written rule;
+    NORMATIVE for `coarse_cross_entropy`.  Returns (loss fp32, lse fp32 [B, H, W], count, bad).
+      z_c    `upsample_logits_reference`: seven rounded fp32 operations and, for 16-bit logits, the rounding to that type (what
+             torch's interpolate returns under autocast; cross_entropy itself runs in fp32)
+      lse    m + log(sum_c exp(z_c - m)), m the maximum over c, the sum over c ascending from 0, every step one rounded fp32 operation.
+             (The launch takes the planes once with a running maximum and rescales its sum where the maximum moves: the same
+             quantity with a few more roundings, inside the bound the tests derive.)
+      count  pixels with target != ignore_index and target < n.  A target with n <= t != ignore_index makes torch RAISE; here it is
+             IGNORED and counted in ``bad``, so that nothing has to wait for the device to find out.
+      loss   float32(sum of float32(lse - z_target) over the counted pixels / count), the sum in fp64 in an order the shape alone
+             decides: per 16 x 64 output tile (`_tile_sum`), then over the tiles ascending.  count == 0 gives NaN, torch's answer."""
+    x, target = _ce_inputs(coarse, target, size, dtype)
+    n = x.shape[1]
+    B, H, W = target.shape
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        z = upsample_logits_reference(x, (H, W), dtype)
+        m = z.max(axis=1)
+        s = np.zeros_like(m)
+        for c in range(n):
+            s = s + np.exp(z[:, c] - m)
+        lse = (m + np.log(s)).astype(np.float32)
+        t = target.astype(np.int64)
+        keep = (t != int(ignore_index)) & (t < n)
+        bad = int(np.count_nonzero((t >= n) & (t != int(ignore_index))))
+        zt = np.take_along_axis(z, np.minimum(t, n - 1)[:, None], axis=1)[:, 0]
+        ell = np.where(keep, (lse - zt).astype(np.float32), np.float32(0)).astype(np.float64)
+    th, tw = CE_TILE
+    padded = np.zeros((B, -(-H // th) * th, -(-W // tw) * tw), dtype=np.float64)
+    padded[:, :H, :W] = ell
+    total = 0.0
+    for b in range(B):
+        for y in range(0, padded.shape[1], th):
+            for x0 in range(0, padded.shape[2], tw):
+                total = total + _tile_sum(padded[b, y:y + th, x0:x0 + tw])
+    count = int(np.count_nonzero(keep))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        loss = np.float32(np.float64(total) / np.float64(count))
+    return loss, lse, count, bad
+
+
+def coarse_cross_entropy_backward_reference(coarse, target, lse, count, grad_loss=1.0, size=None, ignore_index: int = 255,
+                                            dtype: str = "float32") -> np.ndarray:
+    """The gradient of `coarse_cross_entropy_reference`'s loss in ``coarse``, times ``grad_loss``: fp32 [B, n, ih, iw] that holds values
+    of ``dtype``.  NORMATIVE for the backward launch; ``lse`` and ``count`` are what the forward returned.  The exact adjoint of the
+    forward's rule: element (b, c, i, j) is the sum, over the output pixels whose row taps and column taps land on (i, j), of
+    row weight * column weight * (exp(z_c - lse) - [c == target]) * (grad_loss / count); ignored pixels contribute nothing.  In fp32,
+    every product, sum and difference rounded on its own, in a fixed two-level order:
+      g = float32(grad_loss) / float32(count);  per pixel e = (exp(z_c - lse) - [c == t]) * g
+      per output row y:  r_j = 0; for x ascending: r_{j0(x)} += (1 - tx) * e, then r_{j1(x)} += tx * e
+      acc_ij = 0; for y ascending: acc_{i0(y), j} += (1 - ty) * r_j, then acc_{i1(y), j} += ty * r_j
+    with (i0, i1, t) of `upsample_logits_reference`.  Where an edge clamp puts both taps of an axis on one position (i0 == i1 at the last
+    row or column, where t can be non-zero), both weights land there, 1 - t first.  A position no pixel reaches (down-sampling)
+    gets +0.0, and with count == 0 every element is +0.0, torch's answer.  The fp32 sum is rounded ONCE to a 16-bit ``dtype``: a
+    deliberate difference from torch, which rounds the upstream gradient to 16 bits before it is scattered."""
+    from . import degrade
+    x, target = _ce_inputs(coarse, target, size, dtype)
+    B, n, ih, iw = x.shape
+    _, H, W = target.shape
+    lse = np.asarray(lse, dtype=np.float32)
+    if lse.shape != target.shape:
+        raise ValueError(f"lse must be fp32 [B, H, W] like the target, got {lse.shape}")
+    out = np.zeros(x.shape, dtype=np.float32)
+    if int(count) <= 0:
+        return out
+    g = np.float32(grad_loss) / np.float32(int(count))
+    y0, ty = degrade._index_lambda(np.maximum(degrade._source_index(ih, H), np.float32(0)), ih)
+    x0, tx = degrade._index_lambda(np.maximum(degrade._source_index(iw, W), np.float32(0)), iw)
+    y1, x1 = y0 + (y0 < ih - 1), x0 + (x0 < iw - 1)
+    wy0, wx0 = np.float32(1) - ty, np.float32(1) - tx
+    t = target.astype(np.int64)
+    keep = (t != int(ignore_index)) & (t < n)
+    with np.errstate(invalid="ignore", over="ignore"):
+        z = upsample_logits_reference(x, (H, W), dtype)
+        hot = (np.arange(n)[None, :, None, None] == t[:, None]).astype(np.float32)
+        e = ((np.exp(z - lse[:, None]) - hot) * g).astype(np.float32)
+        e = np.where(keep[:, None], e, np.float32(0))
+        r = np.zeros((B, n, H, iw), dtype=np.float32)
+        for xx in range(W):
+            r[:, :, :, x0[xx]] = r[:, :, :, x0[xx]] + wx0[xx] * e[:, :, :, xx]
+            r[:, :, :, x1[xx]] = r[:, :, :, x1[xx]] + tx[xx] * e[:, :, :, xx]
+        for yy in range(H):
+            out[:, :, y0[yy], :] = out[:, :, y0[yy], :] + wy0[yy] * r[:, :, yy, :]
+            out[:, :, y1[yy], :] = out[:, :, y1[yy], :] + ty[yy] * r[:, :, yy, :]
+        return _round_to(out, dtype)
 
 
 def compute_iou(mat) -> np.ndarray:
@@ -405,20 +525,27 @@ def window(x, out_hw, origin=(0, 0), hflip: bool = False, vflip: bool = False, f
     return dst[:, :, 0] if flat else dst
 
 
-def _confusion_args(what: str, logits, target, n, sizes, mat, return_pred: bool, full: bool):
-    """The argument checks `confusion` and `coarse_confusion` share; returns (target on the device, sizes, mat, pred or None).
-    ``full``: the target's extent must be the logits' (else any [B, H, W] is taken)."""
+def _logits_and_target(what: str, logits, target, full: bool):
+    """What every launch on logits and a label map checks first: contiguous [B, n, H, W] logits on the device and a uint8 [B, H, W]
+    target of their batch, which is returned on their device.  ``full``: its extent must be the logits' (else any [B, H, W] is taken)."""
     import torch
     if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.ndim != 4 or not logits.is_contiguous():
         raise TypeError(f"{what} takes a contiguous [B, n, H, W] logits tensor on the device")
-    if logits.shape[1] != int(n):
-        raise ValueError(f"{logits.shape[1]} logit planes for n = {n}")
     target = torch.as_tensor(target)
     fits = target.ndim == 3 and target.shape[0] == logits.shape[0] and (tuple(target.shape[1:]) == tuple(logits.shape[2:]) if full
                                                                          else 0 not in target.shape)
     if target.dtype != torch.uint8 or not fits:
         raise ValueError(f"target must be uint8 [B, H, W] matching the logits, got {target.dtype} {tuple(target.shape)}")
-    target = target.to(logits.device).contiguous()
+    return target.to(logits.device).contiguous()
+
+
+def _confusion_args(what: str, logits, target, n, sizes, mat, return_pred: bool, full: bool):
+    """The argument checks `confusion` and `coarse_confusion` share; returns (target on the device, sizes, mat, pred or None).
+    ``full``: the target's extent must be the logits' (else any [B, H, W] is taken)."""
+    import torch
+    if isinstance(logits, torch.Tensor) and logits.ndim == 4 and logits.shape[1] != int(n):
+        raise ValueError(f"{logits.shape[1]} logit planes for n = {n}")
+    target = _logits_and_target(what, logits, target, full)
     if sizes is not None:
         sizes = [(int(h), int(w)) for h, w in sizes]
         if len(sizes) != logits.shape[0]:
@@ -540,6 +667,127 @@ def assemble_segmenter(backbone, classifier, feature: str = "C5", normalize: boo
             return CoarseLogits(classifier(feats[feature] if hasattr(feats, "keys") else feats), size)
 
     return segnet
+
+
+def _ce_forward(coarse, target, ignore_index: int, max_blocks: int):
+    """the forward launches: (loss fp32 [], counts int64 [2], lse fp32 [B, H, W]) on the device"""
+    import torch
+    from . import ops
+    B, H, W = target.shape
+    dev = coarse.device
+    lse = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    counts = torch.empty((2,), dtype=torch.int64, device=dev)
+    workspace = torch.empty((ops.seg_ce_workspace(B, H, W),), dtype=torch.uint8, device=dev)
+    ops.launch(ops.make_seg_ce_forward(coarse=coarse, target=target, lse=lse, workspace=workspace, loss=loss, counts=counts,
+                                       ignore_index=ignore_index, max_blocks=max_blocks))
+    return loss, counts, lse
+
+
+def coarse_cross_entropy_backward(coarse, target, lse, counts, grad_loss, ignore_index: int = 255, max_blocks: int = 0):
+    """`coarse_cross_entropy_backward_reference` on the device, one launch: the gradient [B, n, ih, iw] in the type of ``coarse`` from
+    the ``lse`` and ``counts`` of the forward (`coarse_cross_entropy(..., return_saved=True)`) and the upstream gradient ``grad_loss``, a
+    number or an fp32 device scalar.  A gather with a fixed order: two calls give the same bits, and every element is written."""
+    import torch
+    from . import ops
+    target = _logits_and_target("coarse_cross_entropy_backward", coarse, target, full=False)
+    if not (isinstance(lse, torch.Tensor) and lse.dtype == torch.float32 and lse.shape == target.shape and lse.is_contiguous()
+            and lse.device == coarse.device):
+        raise TypeError("lse must be the contiguous fp32 [B, H, W] tensor the forward wrote")
+    if not (isinstance(counts, torch.Tensor) and counts.dtype == torch.int64 and counts.numel() == 2 and counts.device == coarse.device):
+        raise TypeError("counts must be the int64 [2] tensor the forward wrote")
+    g = grad_loss if isinstance(grad_loss, torch.Tensor) else torch.tensor(float(grad_loss), dtype=torch.float32)
+    if g.numel() != 1:
+        raise ValueError("grad_loss is one number")
+    g = g.to(device=coarse.device, dtype=torch.float32).contiguous()
+    grad = torch.empty_like(coarse)
+    ops.launch(ops.make_seg_ce_backward(coarse=coarse, target=target, lse=lse, counts=counts, grad_loss=g, grad=grad,
+                                        ignore_index=int(ignore_index), max_blocks=int(max_blocks)))
+    return grad
+
+
+_CE_FUNCTION = None
+
+
+def _ce_function():
+    """the autograd.Function behind a `coarse_cross_entropy` whose logits require grad (made on first use: this module imports without torch)"""
+    global _CE_FUNCTION
+    if _CE_FUNCTION is None:
+        import torch
+        from torch.autograd.function import once_differentiable
+
+        class CoarseCrossEntropy(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, coarse, target, ignore_index, max_blocks):
+                loss, counts, lse = _ce_forward(coarse.detach(), target, ignore_index, max_blocks)
+                ctx.save_for_backward(coarse, target, lse, counts)
+                ctx.ignore_index, ctx.max_blocks = ignore_index, max_blocks
+                ctx.mark_non_differentiable(counts)
+                return loss, counts
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, grad_loss, _):
+                coarse, target, lse, counts = ctx.saved_tensors
+                return coarse_cross_entropy_backward(coarse.detach(), target, lse, counts, grad_loss, ctx.ignore_index, ctx.max_blocks), None, None, None
+
+        _CE_FUNCTION = CoarseCrossEntropy
+    return _CE_FUNCTION
+
+
+def coarse_cross_entropy(coarse, target, size=None, ignore_index: int = 255, return_counts: bool = False, max_blocks: int = 0,
+                         return_saved: bool = False):
+    """`coarse_cross_entropy_reference` on the device: `F.cross_entropy(F.interpolate(coarse, size, mode="bilinear"), target,
+    ignore_index=)` of ``coarse`` (a contiguous fp32 / fp16 / bf16 [B, n, ih, iw] device tensor, n <= 256, or a `CoarseLogits` in place
+    of (coarse, size)) against ``target`` uint8 [B, H, W], without the [B, n, H, W] logits, their log-softmax or a gradient of that
+    extent ever being stored.  ``size`` (default: the target's extent) must be the target's extent.  Returns the loss, an fp32 scalar on
+    the device; with ``return_counts`` also the int64 [2] device tensor (count, bad): a label n <= t != ignore_index is ignored and
+    counted in bad, where torch raises.  No counted pixel: NaN.  Nothing waits for the device.
+    With grad mode on and a ``coarse`` that requires grad the loss is differentiable (once) in ``coarse``: its backward is one gather
+    launch that takes the upstream gradient as a device scalar and gives the same bits on every run.  In every other case only the
+    forward launches run.  ``max_blocks`` caps the grids (0: the default cap); no result depends on it.  ``return_saved`` (forward
+    only): returns (loss, counts, lse), what `coarse_cross_entropy_backward` takes."""
+    import torch
+    if isinstance(coarse, CoarseLogits):
+        if size is not None and _hw(size) != coarse.size:
+            raise ValueError(f"size {_hw(size)} against CoarseLogits that stand for {coarse.size}")
+        coarse, size = coarse.logits, coarse.size
+    target = _logits_and_target("coarse_cross_entropy", coarse, target, full=False)
+    if coarse.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(f"logits must be float32, float16 or bfloat16, got {coarse.dtype}")
+    if coarse.shape[1] > SEG_CE_MAX_CLASSES:
+        raise ValueError(f"at most {SEG_CE_MAX_CLASSES} classes, got {coarse.shape[1]}")
+    if size is not None and _hw(size) != tuple(target.shape[1:]):
+        raise ValueError(f"size {_hw(size)} is not the target's extent {tuple(target.shape[1:])}")
+    ignore_index, max_blocks = int(ignore_index), int(max_blocks)
+    if max_blocks < 0:
+        raise ValueError(f"max_blocks must not be negative, got {max_blocks}")
+    if return_saved:
+        return _ce_forward(coarse.detach(), target, ignore_index, max_blocks)
+    if torch.is_grad_enabled() and coarse.requires_grad:
+        loss, counts = _ce_function().apply(coarse, target, ignore_index, max_blocks)
+    else:
+        loss, counts, _ = _ce_forward(coarse, target, ignore_index, max_blocks)
+    return (loss, counts) if return_counts else loss
+
+
+def assemble_training_segmenter(backbone, classifier, feature: str = "C5", normalize: bool = True):
+    """The train-mode twin of `assemble_segmenter`: the "Train segnet" step of the reference (main/seg/train_edtr.py:208-213) from its
+    learned parts.  Returns ``train_step(images, masks) -> (loss_ce, features)``: ``images`` a contiguous fp32 [B, 3, h, w] device
+    tensor, ``masks`` uint8 [B, h, w]; Normalize (``normalize``), ``backbone`` and ``classifier`` run with grad on, and ``loss_ce`` is
+    `coarse_cross_entropy` of the classifier's logits at the network's stride against the masks, differentiable in every learned
+    part.  ``features`` is what the backbone returned, so that the caller can form the feature-matching L1 of train_edtr.py:218 in
+    torch.  Without the aux head (the reference has it commented out), class weights or label smoothing (it uses neither)."""
+    def train_step(images, masks):
+        import torch
+        from . import cls
+        with torch.enable_grad():
+            feats = backbone(cls.normalize(images) if normalize else images)
+            logits = classifier(feats[feature] if hasattr(feats, "keys") else feats)
+            loss = coarse_cross_entropy(CoarseLogits(logits.contiguous(), tuple(images.shape[-2:])), masks)
+        return loss, feats
+
+    return train_step
 
 
 def evaluate(images, masks, segnet, n_classes: int = 21, return_preds: bool = False, palette=None):

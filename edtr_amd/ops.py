@@ -951,6 +951,41 @@ def make_seg_confusion_coarse(*, coarse, target, mat, sizes=None, pred=None, max
     return Rec(L.load().edtr_seg_confusion_coarse, args, (coarse, target, sizes_host, dsizes, mat, pred), name, 0.0, nbytes)
 
 
+def seg_ce_workspace(B: int, H: int, W: int) -> int:
+    """bytes of the workspace `make_seg_ce_forward` takes (edtr_hip.h `edtr_seg_ce_workspace`: 16 per 16 x 64 output tile)"""
+    return int(L.load().edtr_seg_ce_workspace(int(B), int(H), int(W)))
+
+
+def make_seg_ce_forward(*, coarse, target, lse, workspace, loss, counts, ignore_index: int = 255, max_blocks: int = 0,
+                        name="labels.coarse_cross_entropy") -> Rec:
+    """`F.cross_entropy` of the bilinear upsample of ``coarse`` [B, n, ih, iw] (fp32 / fp16 / bf16) to the extent of uint8 ``target``
+    [B, H, W], which is never stored: fp32 ``lse`` [B, H, W], fp32 ``loss`` [1] and int64 ``counts`` [2] (count, bad) are written;
+    ``workspace``: a uint8 device tensor of `seg_ce_workspace` bytes.  The launch pair of edtr_hip.h `edtr_seg_ce_forward`."""
+    B, n, ih, iw = coarse.shape
+    _, H, W = target.shape
+    if coarse.dtype not in _LOGITS_DT:
+        raise TypeError(f"logits must be float32, float16 or bfloat16, got {coarse.dtype}")
+    args = (_LOGITS_DT[coarse.dtype], ptr(coarse), B, n, ih, iw, ptr(target), H, W, int(ignore_index), ptr(lse), ptr(workspace),
+            workspace.numel() if workspace is not None else 0, ptr(loss), ptr(counts), int(max_blocks))
+    nbytes = float(coarse.element_size() * coarse.numel() + 5 * target.numel())
+    return Rec(L.load().edtr_seg_ce_forward, args, (coarse, target, lse, workspace, loss, counts), name, 0.0, nbytes)
+
+
+def make_seg_ce_backward(*, coarse, target, lse, counts, grad_loss, grad, ignore_index: int = 255, max_blocks: int = 0,
+                         name="labels.coarse_cross_entropy_backward") -> Rec:
+    """``grad`` [B, n, ih, iw] (the type of ``coarse``) = the gradient of `make_seg_ce_forward`'s loss in ``coarse``, scaled by the fp32
+    device scalar ``grad_loss``, from the ``lse`` and ``counts`` that launch wrote: a gather, every element written (edtr_hip.h
+    `edtr_seg_ce_backward`)."""
+    B, n, ih, iw = coarse.shape
+    _, H, W = target.shape
+    if coarse.dtype not in _LOGITS_DT:
+        raise TypeError(f"logits must be float32, float16 or bfloat16, got {coarse.dtype}")
+    args = (_LOGITS_DT[coarse.dtype], ptr(coarse), B, n, ih, iw, ptr(target), H, W, int(ignore_index), ptr(lse), ptr(counts), ptr(grad_loss),
+            ptr(grad), int(max_blocks))
+    nbytes = float(2 * coarse.element_size() * coarse.numel() + 5 * target.numel())
+    return Rec(L.load().edtr_seg_ce_backward, args, (coarse, target, lse, counts, grad_loss, grad), name, 0.0, nbytes)
+
+
 def make_label_resize_nearest(*, src, dst, y_idx, x_idx, name="labels.resize_nearest") -> Rec:
     """uint8 ``src`` [in_h, in_w, C] -> ``dst`` [out_h, out_w, C] (C 1 or 3) through the int32 device tables ``y_idx`` [out_h] /
     ``x_idx`` [out_w] of `labels.nearest_index`."""

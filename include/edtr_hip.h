@@ -999,6 +999,48 @@ int edtr_seg_confusion(int logits_dtype, const void* logits, const uint8_t* targ
 int edtr_seg_confusion_coarse(int logits_dtype, const void* coarse, int B, int n, int ih, int iw, const uint8_t* target, int H, int W,
                               const int32_t* sizes_host, const int32_t* sizes, int64_t* mat, uint8_t* pred, int max_blocks,
                               edtr_stream_t stream);
+/* Segmentation loss from coarse logits (additive to ABI 10): the loss every segmentation training script of the reference forms,
+ *   F.cross_entropy(F.interpolate(coarse, size=(H, W), mode="bilinear", align_corners=False), target, ignore_index=255),
+ * forward and backward without the [B][n][H][W] tensor in either direction.  coarse [B][n][ih][iw] (contiguous, fp32 / fp16 / bf16 by
+ * logits_dtype), target uint8 [B][H][W], n <= EDTR_SEG_CE_MAX_CLASSES.  edtr_amd/labels.py restates both launches in numpy
+ * (coarse_cross_entropy_reference, coarse_cross_entropy_backward_reference); the launches differ from that only in expf / logf and in
+ * the running form of the sum below.
+ *   z_c     the value edtr_seg_confusion_coarse compares: seven rounded fp32 operations, then the rounding to a 16-bit input's type
+ *   lse     m + logf(sum over c of expf(z_c - m)), m the maximum, c ascending, every step rounded to fp32; the launch takes the planes
+ *           once with a running maximum, multiplying the sum so far by expf(old m - new m) where the maximum moves
+ *   counts  a pixel counts iff target != ignore_index and target < n; n <= target != ignore_index is counted in counts[1] ("bad") and
+ *           ignored, where torch raises (no launch here waits for the device).  ignore_index: any int (one outside [0, 255] ignores nothing)
+ *   loss    float(sum of (lse - z_target) over the counted pixels / count), the sum in fp64: per 16 x 64 output tile (a lane's four pixels
+ *           left to right, then a tree over the tile's 256 lanes), then over the tiles ascending.  count = 0 gives NaN, as torch does
+ * edtr_seg_ce_forward writes lse (fp32 [B][H][W], every word: all the backward needs saved), loss (fp32 [1]) and counts (int64 [2] =
+ * count, bad).  Two launches: the tile kernel (edtr_seg_confusion_coarse's tile, tables and staged patch; taps from memory where the
+ * patch does not fit) writes one fp64 sum and two int32 counts per TILE into workspace (8-byte aligned, at least
+ * edtr_seg_ce_workspace(B, H, W) = 16 bytes per tile; 0 for a non-positive extent), then one workgroup folds them in tile order.  No
+ * atomics, no memset; no result depends on the grid (max_blocks caps it; 0: the default cap).
+ * edtr_seg_ce_backward writes grad [B][n][ih][iw] in the logits' type, every element, zeros included: the exact adjoint of the rule
+ * above scaled by g = grad_loss[0] / float(counts[0]), both read on the device.  A gather, one writer per word: a workgroup owns 8 x 8
+ * coarse positions of an image and four of its planes; the output rows whose taps reach coarse row i are the contiguous range
+ * [first y with i1 >= i, first y with i0 > i), found with the forward's own index functions, columns alike.  lse and the targets of
+ * the tile's footprint are staged in LDS while it has at most 6144 pixels and 160 rows and columns (else read from memory: the same
+ * result), each pixel's z_c is blended again by the forward's device function, and element (c, i, j) is
+ *   acc = 0; for y ascending { r = 0; for x ascending, counted pixels only { e = fmul(fadd(expf(fadd(z_c, -lse)), -[c == target]), g);
+ *   if (j0 == j) r = fadd(r, fmul(1 - tx, e)); if (j1 == j) r = fadd(r, fmul(tx, e)); }
+ *   if (i0 == i) acc = fadd(acc, fmul(1 - ty, r)); if (i1 == i) acc = fadd(acc, fmul(ty, r)); }
+ * in fp32, rounded once to a 16-bit type (torch rounds the upstream gradient to 16 bits first: a deliberate difference).  A clamped edge
+ * puts both taps of an axis on one position: both weights land there, 1 - t first.  counts[0] = 0: every element +0.0.
+ * Errors (nothing is launched): a NULL pointer EDTR_E_NULL; unknown logits_dtype EDTR_E_DTYPE; B, n, ih, iw, H, W <= 0, max_blocks < 0
+ * or a workspace smaller than edtr_seg_ce_workspace EDTR_E_SHAPE; n > EDTR_SEG_CE_MAX_CLASSES or an extent above 2^24
+ * EDTR_E_UNSUPPORTED; coarse / grad not aligned to an element, lse / loss / grad_loss to 4, workspace / counts to 8 bytes EDTR_E_ALIGN.
+ * replaces: F.interpolate(x, size=input_shape, mode="bilinear", align_corners=False) -> F.cross_entropy(pred["out"], mask,
+ * ignore_index=255) and its backward, model/deeplabv3.py:44-47, main/seg/train_edtr.py:213. */
+#define EDTR_SEG_CE_MAX_CLASSES 256
+int64_t edtr_seg_ce_workspace(int B, int H, int W);
+int edtr_seg_ce_forward(int logits_dtype, const void* coarse, int B, int n, int ih, int iw, const uint8_t* target, int H, int W,
+                        int ignore_index, float* lse, void* workspace, int64_t workspace_bytes, float* loss, int64_t* counts,
+                        int max_blocks, edtr_stream_t stream);
+int edtr_seg_ce_backward(int logits_dtype, const void* coarse, int B, int n, int ih, int iw, const uint8_t* target, int H, int W,
+                         int ignore_index, const float* lse, const int64_t* counts, const float* grad_loss, void* grad,
+                         int max_blocks, edtr_stream_t stream);
 /* src [in_h][in_w][channels] -> dst [out_h][out_w][channels], uint8, channels 1 or 3 (EDTR_E_UNSUPPORTED otherwise):
  * dst (y, x) = src (y_idx[y], x_idx[x]) with the int32 tables y_idx [out_h] / x_idx [out_w] on the device.  The host builds them by
  * Pillow's accumulating rule (ImagingScaleAffine: xo = 0.5 s; idx[x] = (int)xo; xo += s, in double, s = in / out), which is not
