@@ -9,7 +9,12 @@ E_UNSUPPORTED for a refusal cell) and the kernel it is meant to reach (`path`). 
   reference(cell, d, dt)  (ref, absref) of edtr_hip.h's epilogue order in `dt` (fp64 for the gates), [Z, M, n] each: the two parts
                           edtr_amd.testing.elem_ratio takes
   layout(cell, code)      the edtr_igemm_params fields and where every operand lives inside its poisoned buffer: ld = width + 8, two
-                          guard rows behind every slice, z slices NOT in z order (outer / inner strides that differ per operand)."""
+                          guard rows behind every slice, z slices NOT in z order (outer / inner strides that differ per operand).
+tests/stream_cells.py (the fp32-stream forms of the parity modes) uses the same three builders with further option keys, none of which
+an older cell sets: res_f32 (an fp32 residual of that scale, ldr = N + 4 floats), out16 (the 16-bit mirror, ld16 = N + 16), a_wrap
+(A read twice against [Wh | Wl]), gnp / slot (GroupNorm partials of the output, the reducer's slot rows), a_gn (GroupNorm + SiLU of the
+input in the staging), split (A written as the real hi / lo parts of an fp32 tensor), ups = 2 (the sub-pixel form: four phase
+matrices, guard rows between them), act = GEGLU."""
 import math
 import zlib
 from collections import namedtuple
@@ -17,13 +22,13 @@ from collections import namedtuple
 import torch
 import torch.nn.functional as F
 
-from edtr_amd.testing import LIPSCHITZ
+from edtr_amd.testing import ACC_F32, LIPSCHITZ, geglu_slack
 
 E_UNSUPPORTED = -5
 PTR = 0x10000               # a 16-byte aligned placeholder: the planner looks at addresses, never through them
 PLAN_CUS = 256              # the CU count edtr_igemm_plan assumes without a device (igemm.hip: igemm_plan::plan(pp, 256)); the three
                             # automatic rules asserted here (tiles 1 / 2, 6, 8) count tiles only and do not depend on it
-SILU, LRELU = 2, 4
+GEGLU, SILU, LRELU = 1, 2, 4
 TILE_BM_BN = {1: (128, 128), 2: (64, 64), 3: (128, 128), 6: (256, 256), 8: (128, 160), 14: (256, 32)}      # igemm_plan.h kTiles + the launches
 GEMM_TILES = (1, 2, 3, 6, 8, 14)
 WIDE_LD1, WIDE_LDW = 1 << 22, 1 << 24      # row strides (elements) that put 520 A rows / 136 W rows past 0xF0000000 bytes (kBufferLimit)
@@ -144,7 +149,20 @@ def dims(c):
 def a_shape(c):
     """(rows, columns) of one z slice of the A operand: the matrix, or the NHWC image."""
     s = c.s
-    return (s["M"], s["K"]) if c.kind == "gemm" else (s["B"] * s["H"] * s["W"], s["cin"])
+    if c.kind == "gemm":
+        return s["M"], s["K"] // 2 if c.o.get("a_wrap") else s["K"]      # a_wrap: the columns are read twice
+    return s["B"] * s["H"] * s["W"], s["cin"]
+
+
+def n_out(c):
+    """Stored columns: GEGLU folds the value / gate pairs."""
+    N = dims(c)[1]
+    return N // 2 if c.o.get("act") == GEGLU else N
+
+
+def phases(c):
+    """Weight matrices per launch: 4 in the sub-pixel form of the upsample convolution (edtr_hip.h: w_phase_stride), each [N][2][2][C1]."""
+    return 4 if c.kind == "conv" and c.s["ups"] == 2 else 1
 
 
 def images(c):
@@ -166,7 +184,16 @@ def operands(c, dtype):
     def r(*shape, scale=1.0):
         return torch.randn(shape, generator=g) * scale
     # W keeps n_valid rows per slice: the rows at and beyond n_valid "read as zero" (edtr_hip.h) and belong to the next slice in memory
-    d = {"a": r(1 if o.get("shared_a") else Z, rows, C1).to(dtype), "w": r(Z, o.get("n_valid") or N, K, scale=1 / math.sqrt(K)).to(dtype)}
+    if o.get("split"):      # the real parts of an fp32 tensor: [hi | lo | hi][:parts] (edtr_split_operand's formats), C1 = parts * C
+        x = r(Z, rows, C1 // o["split"])
+        hi = x.to(dtype)
+        a = torch.cat([hi, (x - hi.float()).to(dtype), hi][:o["split"]], dim=2)
+    else:
+        a = r(1 if o.get("shared_a") else Z, rows, C1).to(dtype)
+    if phases(c) == 4:
+        d = {"a": a, "w": r(4, N, 4 * C1, scale=1 / math.sqrt(4 * C1)).to(dtype)}
+    else:
+        d = {"a": a, "w": r(Z, o.get("n_valid") or N, K, scale=1 / math.sqrt(K)).to(dtype)}
     if o.get("bias_n"):
         d["bias_n"] = r(N)
     if o.get("bias_m"):
@@ -174,7 +201,9 @@ def operands(c, dtype):
     if o.get("rowvec"):
         d["rowvec"] = r(images(c)[0], N)
     if o.get("residual"):
-        d["res"] = r(M, N).to(dtype)
+        d["res"] = r(M, n_out(c), scale=o["res_f32"]) if o.get("res_f32") else r(M, N).to(dtype)
+    if o.get("a_gn"):       # the (scale, shift) table edtr_gn_table would derive: [B][C1][2] fp32
+        d["gn_table"] = torch.stack([1 + 0.2 * r(c.s["B"], C1), 0.2 * r(c.s["B"], C1)], dim=-1)
     return d
 
 
@@ -183,6 +212,14 @@ def _product(c, a, w):
     if c.kind == "gemm":
         return a @ w.transpose(1, 2)
     s = c.s
+    if phases(c) == 4:      # output pixel (2 sy + py, 2 sx + px) = a 2 x 2 convolution of source rows sy + py - 1 .. sy + py with phase 2 py + px
+        x = F.pad(a[0].reshape(s["B"], s["H"], s["W"], s["cin"]).permute(0, 3, 1, 2), (1, 1, 1, 1))
+        y = x.new_zeros((s["B"], w.shape[1], 2 * s["H"], 2 * s["W"]))
+        for py in (0, 1):
+            for px in (0, 1):
+                wp = w[2 * py + px].reshape(-1, 2, 2, s["cin"]).permute(0, 3, 1, 2)
+                y[:, :, py::2, px::2] = F.conv2d(x[:, :, py:py + s["H"] + 1, px:px + s["W"] + 1], wp)
+        return y.permute(0, 2, 3, 1).reshape(1, -1, y.shape[1])
     outs = []
     for z in range(w.shape[0]):
         x = a[z].reshape(s["B"], s["H"], s["W"], s["cin"]).permute(0, 3, 1, 2)
@@ -202,7 +239,14 @@ def reference(c, d, dt=torch.float64):
     M, N, _ = dims(c)
     Z, o = c.s["Z"], c.o
     a, w = d["a"].to(dt), d["w"].to(dt)
-    a = a.expand(Z, -1, -1)
+    if "gn_table" in d:     # a_gn: silu(a * scale + shift) rounded to 16 bits as edtr_gn_apply stores it (stream_cells adds the flip term)
+        from swin_cases import gn_apply16
+        t = d["gn_table"]
+        a = gn_apply16(d["a"].float().reshape(c.s["B"], -1, a.shape[2]), t[:, None, :, 0], t[:, None, :, 1], d["a"].dtype)[0].reshape(a.shape).to(dt)
+    if o.get("a_wrap"):
+        a = torch.cat([a, a], dim=2)
+    if phases(c) == 1:
+        a = a.expand(Z, -1, -1)
     w = F.pad(w, (0, 0, 0, N - w.shape[1]))
     alpha = o.get("alpha", 1.0)
     ref, ab = alpha * _product(c, a, w), abs(alpha) * _product(c, a.abs(), w.abs())
@@ -215,7 +259,16 @@ def reference(c, d, dt=torch.float64):
     if "rowvec" in d:
         t = d["rowvec"].to(dt).repeat_interleave(images(c)[1], dim=0)[:M]
         ref, ab = ref + t, ab + t.abs()
-    if o.get("act") == SILU:
+    if o.get("act") == GEGLU:      # value / gate blocks of 32 columns interleaved by the weight packer (ops.geglu_perm)
+        from edtr_amd.ops import geglu_perm
+        perm, K = geglu_perm(N // 2), dims(c)[2]
+        h, hab = torch.empty_like(ref), torch.empty_like(ab)
+        h[..., perm], hab[..., perm] = ref, ab
+        val, gate = h[..., :N // 2], h[..., N // 2:]
+        ref = val * F.gelu(gate)
+        # the product rule's slack stands in for absref: the caller's k 2^-22 absref is then geglu_slack exactly
+        ab = geglu_slack(val, gate, hab[..., :N // 2], hab[..., N // 2:], K).to(dt) / (K * ACC_F32)
+    elif o.get("act") == SILU:
         ref, ab = F.silu(ref), LIPSCHITZ["silu"] * ab
     elif o.get("act") == LRELU:
         ref, ab = torch.where(ref > 0, ref, o["slope"] * ref), LIPSCHITZ["leaky"] * ab
@@ -230,14 +283,16 @@ Slab = namedtuple("Slab", "numel offs rows cols ld")      # a poisoned buffer of
 
 
 def layout(c, dtype_code=0, shape=None, tile=None):
-    """-> (fields, pointer field names, {"a", "w", "out"[, "res"]: Slab}).  `shape` overrides entries of the cell's shape (the full-size
-    production shape of an `auto` check), `tile` the explicit tile."""
+    """-> (fields, pointer field names, {"a", "w", "out"[, "res", "out16", "gnp"]: Slab}).  `shape` overrides entries of the cell's shape
+    (the full-size production shape of an `auto` check), `tile` the explicit tile.  The row strides all differ: ldc = n + 8, ldr = n + 4
+    floats for an fp32 residual, ld16 = n + 16; the "gnp" slab is [slots][2 N] floats with one guard slot behind it."""
     c = c._replace(s=dict(c.s, **(shape or {})))
     s, o = c.s, c.o
     M, N, K = dims(c)
     Z, zdiv = s["Z"], s["zdiv"]
     rows, C1 = a_shape(c)
-    ld1, ldw, ldc = o.get("ld1", C1 + 8), o.get("ldw", K + 8), N + 8
+    No, P = n_out(c), phases(c)
+    ld1, ldw, ldc = o.get("ld1", C1 + 8), o.get("ldw", (4 * C1 if P == 4 else K) + 8), No + 8
     nv = o.get("n_valid", 0)
     SA, SO = (rows + 2) * ld1, (M + 3) * ldc
     SW = nv * ldw if nv else (N + 2) * ldw      # n_valid: the next slice's live rows follow at once, so reading a row >= n_valid shows
@@ -254,8 +309,11 @@ def layout(c, dtype_code=0, shape=None, tile=None):
     a_zs = (0, 0) if o.get("shared_a") else strides(SA, 1, 2)
     w_zs, o_zs = strides(SW, 3, 2, 1 if nv else 2), strides(SO, 1, 3)
     ao, wo, oo = offsets(a_zs), offsets(w_zs), offsets(o_zs)
-    slabs = {"a": Slab(max(ao) + SA, ao, rows, C1, ld1), "w": Slab(max(wo) + SW + 2 * ldw, wo, nv or N, K, ldw), "out": Slab(max(oo) + SO, oo, M, N, ldc)}
-    f = dict(dtype=dtype_code, taps=9 if c.kind == "conv" else 1, M=M, N=N, K=K, n_valid=nv, Z=Z, zdiv=zdiv, C1=C1, ld1=ld1, ldw=ldw,
+    if P == 4:      # the four phase matrices, w_phase_stride apart: two guard rows behind each
+        wo = [i * SW for i in range(4)]
+    slabs = {"a": Slab(max(ao) + SA, ao, rows, C1, ld1), "w": Slab(max(wo) + SW + 2 * ldw, wo, nv or N, 4 * C1 if P == 4 else K, ldw),
+             "out": Slab(max(oo) + SO, oo, M, No, ldc)}
+    f = dict(dtype=dtype_code, taps=9 if c.kind == "conv" else 1, M=M, N=N, K=K, n_valid=nv, Z=Z, zdiv=zdiv, C1=K if o.get("a_wrap") else C1, ld1=ld1, ldw=ldw,
              a_zs_outer=a_zs[0], a_zs_inner=a_zs[1], w_zs_outer=w_zs[0], w_zs_inner=w_zs[1], o_zs_outer=o_zs[0], o_zs_inner=o_zs[1],
              alpha=o.get("alpha", 1.0), ldc=ldc, out_f32=int(bool(o.get("out_f32"))), act=o.get("act", 0), act_slope=o.get("slope", 0.0),
              tile=c.tile if tile is None else tile, splitk=o.get("splitk", 0))
@@ -269,10 +327,27 @@ def layout(c, dtype_code=0, shape=None, tile=None):
     if o.get("rowvec"):
         f.update(rowvec_ld=N, rows_per_image=images(c)[1])
         ptrs.append("rowvec")
+    if P == 4:
+        f.update(w_phase_stride=SW)
+    if o.get("a_wrap"):
+        f.update(a_wrap=K // 2)
     if o.get("residual"):
-        f.update(ldr=N + 8)
+        ldr = No + 4 if o.get("res_f32") else N + 8
+        f.update(ldr=ldr, residual_f32=int(bool(o.get("res_f32"))))
         ptrs.append("residual")
-        slabs["res"] = Slab((M + 2) * (N + 8), [0], M, N, N + 8)
+        slabs["res"] = Slab((M + 2) * ldr, [0], M, No, ldr)
+    if o.get("out16"):
+        f.update(ld16=No + 16)
+        ptrs.append("out16")
+        slabs["out16"] = Slab((M + 2) * (No + 16), [0], M, No, No + 16)
+    if o.get("gnp"):
+        slots = M // (o.get("slot") or 128)
+        f.update(gn_slot_rows=o.get("slot", 0))
+        ptrs.append("gn_partial")
+        slabs["gnp"] = Slab((slots + 1) * 2 * N, [0], slots, 2 * N, 2 * N)
+    if o.get("a_gn"):
+        f.update(a_gn_silu=1, rows_per_image=images(c)[1])
+        ptrs.append("a_gn")
     if o.get("splitk", 0) > 1:
         f.update(workspace_bytes=o["splitk"] * M * N * 4)
         ptrs.append("workspace")

@@ -345,9 +345,23 @@ def test_igemm_fp32_output_with_fp16_mirror(case):
     assert torch.isfinite(out).all()
     assert torch.equal(mir[:, :N], out.to(dt))
     assert bool((mir[:, N:] == 9.0).all())
-    if not conv:
-        ref = x.float().cpu() @ w.float().cpu().t() + bias.cpu() + (res.cpu() if use_res else 0.0)
-        assert rel(out, ref) < 2e-5
+    # fp64 reference of the 16-bit values read, every case (the halo convolution included: its weights are packed [N][ky][kx][cin]),
+    # under the whole-tensor gate and the rounding-aware element bound of an fp32 output with k = K
+    import torch.nn.functional as F
+    from edtr_amd.testing import elem_ratio
+    xc, wc = x.cpu().double(), w.cpu().double()
+    if conv:
+        xi, wi = xc.reshape(B, H, H, cin).permute(0, 3, 1, 2), wc.reshape(N, 3, 3, cin).permute(0, 3, 1, 2)
+        ref, ab = (F.conv2d(a, b, padding=1).permute(0, 2, 3, 1).reshape(M, N) for a, b in ((xi, wi), (xi.abs(), wi.abs())))
+    else:
+        ref, ab = xc @ wc.t(), xc.abs() @ wc.abs().t()
+    for t in (bias, res):
+        if t is not None:
+            ref, ab = ref + t.cpu().double(), ab + t.cpu().double().abs()
+    assert rel(out, ref) < 2e-5
+    r, where = elem_ratio(out, ref, ab, torch.float32, K)
+    print(f"\n[fp32 out + mirror {case}] element ratio {r:.3f}")
+    assert r <= 1.0, f"element bound exceeded: ratio {r:.3g} at {where}"
 
 
 @pytest.mark.parametrize("M,N,C,tile", [(300, 320, 192, 0), (2048, 640, 1280, 8), (512, 1280, 320, 3), (130, 136, 128, 1), (77, 72, 64, 2),

@@ -17,6 +17,8 @@ attention cases at the launch geometry of a batch-8 run (test_flash_attn64_launc
 and the output that way (HostileAttn) and assert edtr_flash_attn64_plan's answer before they launch.  igemm's z-batched launches
 (Z > 1 on every tile, zdiv > 1), its wide operands (the 64-bit-address form of tile 3), tile 14 against fp64 and split-K on tiles 8 /
 14 or with empty trailing splits live in tests/test_gpu_igemm_cells.py (case table: tests/igemm_cells.py), under the same two gates.
+The fp32-stream forms the parity modes emit (fp32 output, fp32 residual, 16-bit mirror, a_wrap, GroupNorm partials of an fp32 output, the
+split-K reducer doing these, operands of two or three parts) live in tests/test_gpu_stream_cells.py (table: tests/stream_cells.py).
 The six MFMA kernels of csrc/swin.hip run here in the friendly layout only; their references live in tests/swin_cases.py, and
 tests/test_gpu_swin_edges.py launches them into guarded buffers with hostile strides at the smallest shape that reaches each branch
 (persistent-loop rounds, thin shifts, head width 32, row-count edges, rejections); tests/test_swin_edges_cpu.py shows on the CPU
