@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libedtr_hip.so")
 SOURCES = ["igemm.hip", "halo512.hip", "attention.hip", "attn512.hip", "norm.hip", "elementwise.hip", "swin.hip", "ffn.hip", "lin320.hip", "rng.hip", "imageio.hip", "degrade.hip", "degrade2.hip", "labels.hip", "boxes.hip"]
 # units that include glue.h and are newer than the glue / MFMA table tests/test_host_logic.py pins SOURCES to; compiled and linked alike
-GLUE_SOURCES = ["coco.hip", "cls.hip", "rois.hip", "coco_acc.hip", "det_transform.hip", "targets.hip", "seg_loss.hip"]
+GLUE_SOURCES = ["coco.hip", "cls.hip", "rois.hip", "coco_acc.hip", "det_transform.hip", "targets.hip", "seg_loss.hip", "losses.hip"]
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 ABI_HEADER = os.path.join(INCLUDE, "edtr_hip.h")
 ARCH = "gfx950"

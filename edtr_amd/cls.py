@@ -3,7 +3,8 @@
 --calc-fd, `F.l1_loss(feat_res, feat_gt, reduction='none').mean(dim=(1, 2, 3))` — and the geometry its data set applies to the ground
 truth (datasets/classification.py:65-96: shorter side to gt_size, crop, `augment`'s flips and rot90).  The five launches are
 include/edtr_hip.h "Classification" (kernels in csrc/cls.hip).  The task networks stay outside, as in `labels` and `boxes`: `evaluate`
-takes any callable.
+takes any callable, and `assemble_training_classifier` puts the reference's "Train clsnet" step (main/cls/train_edtr.py:207-213)
+together from the classifier, its teacher and the loss launches of `losses`.
 
 Three layers, as in `labels` and `coco`:
   * `rank`, `fdist`, `normalize`, `window`, `Scores`: thin wrappers over the launches (torch tensors on the device, the caller's
@@ -644,3 +645,28 @@ def evaluate(images, labels, clsnet, teacher=None, gts=None, batch_size: int = 8
         scores.update(logits, lab[lo:hi], *feats)
     records = scores.to_host()
     return {**summarize(records), "pred": records["top"][:, 0].copy(), "rank": records["rank"], "fd_image": records["fd"], "records": records}
+
+
+def assemble_training_classifier(clsnet, teacher=None, weight_ce: float = 1.0, weight_fm: float = 1.0):
+    """The "Train clsnet" step of the reference (main/cls/train_edtr.py:207-213) from its learned parts, the train-mode twin of
+    `evaluate`'s use of ``clsnet``.  Returns ``train_step(images, labels, gts=None) -> (losses, (pred, feat_student))``: ``images`` an
+    fp32 [B, 3, h, w] device tensor (the restored half and the clean half already concatenated, normalised as the classifier expects:
+    `prepare`), ``labels`` B integers.  ``clsnet(images, return_feat=True)`` runs with grad on and returns (logits [B, C], features);
+    ``losses["ce"]`` is ``weight_ce`` * `losses.cross_entropy` of the logits, differentiable in every learned part.  With ``teacher``,
+    ``teacher(gts, return_feat=True)`` runs under no_grad (``gts`` defaults to ``images``) and ``losses["fm"]`` is `losses.l1_mean` of
+    (student features, teacher features) with weight ``weight_fm``; without a teacher there is no "fm".  Both are fp32 device
+    scalars: ``sum(losses.values()).backward()`` is the reference's `accelerator.backward(loss_ce + loss_fm)`.  No label smoothing
+    (the reference passes 0.0)."""
+    def train_step(images, labels, gts=None):
+        import torch
+        from . import losses
+        with torch.enable_grad():
+            pred, feat_student = clsnet(images, return_feat=True)
+            out = {"ce": losses.cross_entropy(pred, labels) * float(weight_ce)}
+            if teacher is not None:
+                with torch.no_grad():
+                    _, feat_teacher = teacher(images if gts is None else gts, return_feat=True)
+                out["fm"] = losses.l1_mean([(feat_student, feat_teacher)], [float(weight_fm)])
+        return out, (pred, feat_student)
+
+    return train_step

@@ -1,4 +1,4 @@
-// What the fp32 / uint8 glue kernels share (elementwise.hip, rng.hip, imageio.hip, degrade.hip, degrade2.hip, labels.hip, boxes.hip, coco.hip, coco_acc.hip, cls.hip, rois.hip, det_transform.hip, targets.hip, seg_loss.hip; no
+// What the fp32 / uint8 glue kernels share (elementwise.hip, rng.hip, imageio.hip, degrade.hip, degrade2.hip, labels.hip, boxes.hip, coco.hip, coco_acc.hip, cls.hip, rois.hip, det_transform.hip, targets.hip, seg_loss.hip, losses.hip; no
 // MFMA translation unit includes this file): the grid of a grid-stride launch, the alignment predicates and the batch check of the
 // host side, and the device helpers whose roundings the numpy restatements repeat bit for bit.  ONE definition each: a rounding rule
 // that lived in three files could be fixed in one and drift in the other two.

@@ -776,8 +776,8 @@ def assemble_training_segmenter(backbone, classifier, feature: str = "C5", norma
     learned parts.  Returns ``train_step(images, masks) -> (loss_ce, features)``: ``images`` a contiguous fp32 [B, 3, h, w] device
     tensor, ``masks`` uint8 [B, h, w]; Normalize (``normalize``), ``backbone`` and ``classifier`` run with grad on, and ``loss_ce`` is
     `coarse_cross_entropy` of the classifier's logits at the network's stride against the masks, differentiable in every learned
-    part.  ``features`` is what the backbone returned, so that the caller can form the feature-matching L1 of train_edtr.py:218 in
-    torch.  Without the aux head (the reference has it commented out), class weights or label smoothing (it uses neither)."""
+    part.  ``features`` is what the backbone returned, so that the caller can form the feature-matching L1 of train_edtr.py:218 with
+    `losses.feature_matching(features, teacher_features, keys=("C5",))`.  Without the aux head (the reference has it commented out), class weights or label smoothing (it uses neither)."""
     def train_step(images, masks):
         import torch
         from . import cls

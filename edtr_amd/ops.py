@@ -1183,6 +1183,89 @@ def make_cls_window(*, src, dst, out_hw, y0: int, x0: int, hflip: bool, vflip: b
     return Rec(L.load().edtr_cls_window, args, (src, dst), name, 0.0, 2.0 * dst.numel())
 
 
+# -- training losses (edtr_hip.h "Training losses"; the callers and the host restatements are edtr_amd/losses.py) ----------------------
+def _l1_tables(pairs, weights):
+    """the host arrays of the L1 entry points for ``pairs`` = [(a, b)] of device tensors and one host float per pair, checked"""
+    pairs = [tuple(p) for p in pairs]
+    if not 1 <= len(pairs) <= L.L1_MAX_PAIRS:
+        raise ValueError(f"1 to {L.L1_MAX_PAIRS} pairs, got {len(pairs)}")
+    if len(weights) != len(pairs):
+        raise ValueError(f"{len(weights)} weights for {len(pairs)} pairs")
+    for a, b in pairs:
+        if a.dtype not in _LOGITS_DT or b.dtype != a.dtype:
+            raise TypeError(f"both tensors of a pair must be float32, float16 or bfloat16 alike, got {a.dtype} and {b.dtype}")
+        if a.shape != b.shape or a.numel() == 0:
+            raise ValueError(f"the tensors of a pair have one non-empty shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+        if a.numel() > L.L1_MAX_ELEMS:
+            raise ValueError(f"at most {L.L1_MAX_ELEMS} elements a pair, got {a.numel()}")
+        if not (a.is_contiguous() and b.is_contiguous()):
+            raise ValueError("the tensors of a pair must be contiguous")
+    k = len(pairs)
+    return (pairs, (ct.c_int32 * k)(*[_LOGITS_DT[a.dtype] for a, _ in pairs]), _pointer_table([a for a, _ in pairs]),
+            _pointer_table([b for _, b in pairs]), (ct.c_int64 * k)(*[a.numel() for a, _ in pairs]), (ct.c_float * k)(*[float(w) for w in weights]))
+
+
+def l1_workspace(counts: Sequence[int]) -> int:
+    """bytes of the workspace `make_l1_forward` takes for pairs of these element counts (edtr_hip.h `edtr_l1_workspace`: 8 per chunk)"""
+    n_host = (ct.c_int64 * max(len(counts), 1))(*[int(n) for n in counts])
+    return int(L.load().edtr_l1_workspace(n_host, len(counts)))
+
+
+def make_l1_forward(*, pairs, weights, workspace, loss, terms=None, max_blocks: int = 0, name="losses.l1_mean") -> Rec:
+    """fp32 ``loss`` [1] = sum_k weights[k] * mean |a_k - b_k| over ``pairs`` = [(a, b)] (contiguous device tensors, fp32 / fp16 / bf16 per
+    pair) and, where given, fp32 ``terms`` [len(pairs)] = the unweighted means; ``workspace``: a uint8 device tensor of `l1_workspace`
+    bytes.  The launch pair of edtr_hip.h `edtr_l1_forward`."""
+    pairs, dt, pa, pb, n_host, w_host = _l1_tables(pairs, weights)
+    if terms is not None and terms.numel() < len(pairs):
+        raise ValueError("terms takes one fp32 word per pair")
+    args = (dt, pa, pb, n_host, w_host, len(pairs), ptr(workspace), workspace.numel() if workspace is not None else 0, ptr(loss), ptr(terms),
+            int(max_blocks))
+    nbytes = float(sum(2 * a.element_size() * a.numel() for a, _ in pairs))
+    return Rec(L.load().edtr_l1_forward, args, (dt, pa, pb, n_host, w_host, pairs, workspace, loss, terms), name, 0.0, nbytes)
+
+
+def make_l1_backward(*, pairs, weights, grad_loss, grads_a, grads_b, max_blocks: int = 0, name="losses.l1_mean_backward") -> Rec:
+    """``grads_a[k]`` / ``grads_b[k]`` (a tensor like the pair's, or None) = the gradient of `make_l1_forward`'s loss in a_k / b_k scaled
+    by the fp32 device scalar ``grad_loss``: one launch for all pairs, every element written (edtr_hip.h `edtr_l1_backward`)."""
+    pairs, dt, pa, pb, n_host, w_host = _l1_tables(pairs, weights)
+    grads_a, grads_b = list(grads_a), list(grads_b)
+    if len(grads_a) != len(pairs) or len(grads_b) != len(pairs):
+        raise ValueError("one gradient slot (a tensor or None) per pair and side")
+    for (a, _), ga, gb in zip(pairs, grads_a, grads_b):
+        for g in (ga, gb):
+            if g is not None and (g.dtype != a.dtype or g.shape != a.shape or not g.is_contiguous()):
+                raise TypeError("a gradient is a contiguous tensor of its pair's shape and type")
+    pga, pgb = _pointer_table(grads_a), _pointer_table(grads_b)
+    args = (dt, pa, pb, n_host, w_host, len(pairs), ptr(grad_loss), pga, pgb, int(max_blocks))
+    nbytes = float(sum(a.element_size() * a.numel() * (2 + (ga is not None) + (gb is not None))
+                       for (a, _), ga, gb in zip(pairs, grads_a, grads_b) if ga is not None or gb is not None))
+    return Rec(L.load().edtr_l1_backward, args, (dt, pa, pb, n_host, w_host, pga, pgb, pairs, grad_loss, grads_a, grads_b), name, 0.0, nbytes)
+
+
+def make_cls_ce_forward(*, logits, labels, lse, workspace, loss, counts, ignore_index: int = -100, name="losses.cross_entropy") -> Rec:
+    """`F.cross_entropy` of ``logits`` [B, C] (fp32 / fp16 / bf16) against int32 ``labels`` [B]: fp32 ``lse`` [B], fp32 ``loss`` [1] and
+    int64 ``counts`` [2] (count, bad) are written; ``workspace``: a uint8 device tensor of 8 B bytes.  The launch pair of edtr_hip.h
+    `edtr_cls_ce_forward`."""
+    B, C = logits.shape
+    if logits.dtype not in _LOGITS_DT:
+        raise TypeError(f"logits must be float32, float16 or bfloat16, got {logits.dtype}")
+    args = (_LOGITS_DT[logits.dtype], ptr(logits), ptr(labels), B, C, int(ignore_index), ptr(lse), ptr(workspace),
+            workspace.numel() if workspace is not None else 0, ptr(loss), ptr(counts))
+    return Rec(L.load().edtr_cls_ce_forward, args, (logits, labels, lse, workspace, loss, counts), name, 0.0,
+               float(2 * logits.element_size() * logits.numel()))
+
+
+def make_cls_ce_backward(*, logits, labels, lse, counts, grad_loss, grad, ignore_index: int = -100, name="losses.cross_entropy_backward") -> Rec:
+    """``grad`` [B, C] (the type of ``logits``) = the gradient of `make_cls_ce_forward`'s loss in ``logits`` scaled by the fp32 device
+    scalar ``grad_loss``, from the ``lse`` and ``counts`` that launch wrote; every element written (edtr_hip.h `edtr_cls_ce_backward`)."""
+    B, C = logits.shape
+    if logits.dtype not in _LOGITS_DT:
+        raise TypeError(f"logits must be float32, float16 or bfloat16, got {logits.dtype}")
+    args = (_LOGITS_DT[logits.dtype], ptr(logits), ptr(labels), B, C, int(ignore_index), ptr(lse), ptr(counts), ptr(grad_loss), ptr(grad))
+    return Rec(L.load().edtr_cls_ce_backward, args, (logits, labels, lse, counts, grad_loss, grad), name, 0.0,
+               float(2 * logits.element_size() * logits.numel()))
+
+
 # -- region proposals and RoI pooling (edtr_hip.h; the callers and the host restatements are edtr_amd/rois.py) -----------------------
 def _level_table(levels):
     """int32 [L][5] on the host from [(H, W, A, stride_h, stride_w)]"""

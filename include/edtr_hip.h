@@ -1492,6 +1492,76 @@ int edtr_targets_gather(const float* boxes, const float* gt_boxes, const int32_t
                         const int32_t* table, int N, const int32_t* sampled, int batch, const float* weights_host, float* out_boxes,
                         int64_t* out_labels, int64_t* out_matched, float* out_targets, edtr_stream_t stream);
 
+/* ---- Training losses: the feature-matching L1 and the classifier's cross-entropy (additive to ABI 10) -------------------------------
+ * The two loss terms every training script of the reference shares: F.l1_loss(feat_a, feat_b, reduction="mean") * w, its loss_fm and
+ * loss_hlf (and the val_fd of the segmentation and detection test loops), and F.cross_entropy(pred, label) of the classifier.
+ * edtr_amd/losses.py restates every launch in numpy (l1_mean_reference, l1_mean_backward_reference, cross_entropy_reference,
+ * cross_entropy_backward_reference): the L1 launches equal the restatements bit for bit, the cross-entropy ones except in expf / logf.
+ * No atomics, no memset, one writer per word; no result depends on the grid.
+ *
+ * Weighted mean-L1 over a list of pairs:  loss = sum over k of w_k mean_i |a_k[i] - b_k[i]|,  pairs <= EDTR_L1_MAX_PAIRS.
+ * Per pair, in HOST arrays: dtype_host (EDTR_LOGITS_F32 / _F16 / _BF16), a_host / b_host (device pointers, contiguous, n elements of
+ * that type), n_host (int64, 1 ... EDTR_L1_MAX_ELEMS), weight_host (fp32).  Offsets are 64-bit.
+ *   difference  formed in fp32: both operands widened exactly, ONE rounded subtraction, fabsf; added in fp64.  For 16-bit inputs this is
+ *               what torch computes under autocast (l1_loss runs in fp32 there) and a deliberate difference from a plain 16-bit
+ *               l1_loss, which rounds each difference to 16 bits.  A NaN difference makes the loss NaN, as in torch.
+ *   order       of the fp64 sum: a function of n alone, the same for the three element types.  A chunk is EDTR_L1_CHUNK elements; lane l
+ *               of 256 owns elements 4 l ... 4 l + 3 of each of the chunk's four 1024-element quarters and adds its (up to) 16
+ *               differences in ascending order from +0; the tree s = 128, 64, ..., 1 with sum[l] += sum[l + s] gives the chunk's
+ *               partial, one fp64 word per chunk in the workspace, the pairs concatenated.  Workgroups stride over the chunks.
+ *   finalize    one workgroup: per pair, lane l adds partials l, l + 256, ... ascending from +0, then the same tree; term_k = sum /
+ *               (double)n_k; total = sum over k ascending from +0 of (double)w_k term_k; loss[0] = (float)total and, where terms is
+ *               not NULL, terms[k] = (float)term_k, the unweighted means.
+ *   loads       16 bytes a lane (8 for 16-bit types) where both pointers of a pair are aligned to them, element loads otherwise and in
+ *               a pair's last partial group of four: the same bits.
+ * edtr_l1_workspace(n_host, pairs) = 8 bytes per chunk (0 for a NULL array, pairs outside 1 ... EDTR_L1_MAX_PAIRS or an n outside
+ * 1 ... EDTR_L1_MAX_ELEMS); the workspace may hold anything before the call.  edtr_l1_forward is two launches (chunks, finalize).
+ * edtr_l1_backward, one launch for all pairs: grad_a_host[k] / grad_b_host[k] are device pointers of n_k elements in the pair's type,
+ * either may be NULL per pair, a pair with both NULL is skipped, all NULL is an error.
+ *   c_k      = (float)((double)grad_loss[0] (double)w_k / (double)n_k), grad_loss read on the device
+ *   grad_a[i] = +c_k where the fp32 difference is positive, -c_k where it is negative, +0.0 where it is zero or NaN (torch's sign);
+ *   grad_b[i] = -grad_a[i] by a flip of the sign bit (-0.0 where grad_a is +0.0).  A 16-bit output takes c_k rounded once (nearest even).
+ * Every element is written, one writer per word.  max_blocks caps the grid of both (0: the default cap).
+ * Errors (nothing is launched), in this order: a NULL array, loss, workspace or grad_loss EDTR_E_NULL; pairs outside 1 ...
+ * EDTR_L1_MAX_PAIRS or max_blocks < 0 EDTR_E_SHAPE; a NULL a / b, or every gradient pointer NULL, EDTR_E_NULL; an unknown dtype
+ * EDTR_E_DTYPE; n <= 0 EDTR_E_SHAPE; n > EDTR_L1_MAX_ELEMS EDTR_E_UNSUPPORTED; a workspace smaller than edtr_l1_workspace
+ * EDTR_E_SHAPE; a / b / a gradient not aligned to its element, loss / terms / grad_loss to 4 or the workspace to 8 bytes EDTR_E_ALIGN.
+ * replaces: F.l1_loss(feat_a, feat_b, reduction="mean") * w and its backward, main/cls/train_edtr.py:175-176, 213,
+ * main/seg/train_edtr.py:180-181, 218, main/det/train_edtr.py:194-197, 236-237, main/seg/test_edtr.py:165, main/det/test_edtr.py:167-168. */
+#define EDTR_L1_MAX_PAIRS 8
+#define EDTR_L1_CHUNK 4096
+#define EDTR_L1_MAX_ELEMS (1 << 30)
+int64_t edtr_l1_workspace(const int64_t* n_host, int pairs);
+int edtr_l1_forward(const int32_t* dtype_host, const void* const* a_host, const void* const* b_host, const int64_t* n_host,
+                    const float* weight_host, int pairs, void* workspace, int64_t workspace_bytes, float* loss, float* terms,
+                    int max_blocks, edtr_stream_t stream);
+int edtr_l1_backward(const int32_t* dtype_host, const void* const* a_host, const void* const* b_host, const int64_t* n_host,
+                     const float* weight_host, int pairs, const float* grad_loss, void* const* grad_a_host, void* const* grad_b_host,
+                     int max_blocks, edtr_stream_t stream);
+/* The classifier's loss: F.cross_entropy(logits [B][C], labels, reduction="mean", ignore_index=), the rule of the segmentation loss
+ * ("Label maps") on rows.  logits fp32 / fp16 / bf16 by logits_dtype (widened exactly), labels int32 [B] on the device, C <=
+ * EDTR_CLS_MAX_CLASSES, B <= 65535.
+ *   lse     one wave64 workgroup per row: m the row maximum; s = sum of expf(z_c - m) in fp32, lane l adding c = l, l + 64, ... ascending
+ *           from +0, then the tree o = 32, 16, ..., 1 with s[l] += s[l + o] over the 64 lanes; lse = m + logf(s).  Every step rounded.
+ *   counts  a row counts iff label != ignore_index and 0 <= label < C; any other label that is not ignore_index is counted in
+ *           counts[1] ("bad") and ignored, where torch raises (no launch here waits for the device)
+ *   loss    the row term (double)(lse - z_label) goes to workspace (fp64 [B], 8-byte aligned, at least 8 B bytes; may hold anything
+ *           before); one workgroup folds the counted rows in row order in fp64: loss[0] = (float)(sum / count), counts (int64 [2]) =
+ *           count, bad.  count = 0 gives NaN, as torch does
+ * edtr_cls_ce_forward writes lse (fp32 [B], every row: all the backward needs saved), loss and counts.  edtr_cls_ce_backward writes
+ * grad [B][C] in the logits' type, every element: fmul(fadd(expf(fadd(z_c, -lse_b)), -[c == label_b]), g) with g = grad_loss[0] /
+ * (float)counts[0], both read on the device; +0.0 on every row that does not count and everywhere with counts[0] = 0; a 16-bit
+ * output is rounded once (torch rounds the upstream gradient to 16 bits first: a deliberate difference).
+ * Errors (nothing is launched): a NULL pointer EDTR_E_NULL; unknown logits_dtype EDTR_E_DTYPE; B, C <= 0 or a workspace below 8 B
+ * bytes EDTR_E_SHAPE; B > 65535 or C > EDTR_CLS_MAX_CLASSES EDTR_E_UNSUPPORTED; logits / grad not aligned to an element, labels / lse /
+ * loss / grad_loss to 4, workspace / counts to 8 bytes EDTR_E_ALIGN.
+ * replaces: F.cross_entropy(pred, label, reduction="mean", label_smoothing=0.0) and its backward, main/cls/train_edtr.py:208,
+ * main/cls/train_cls.py:93. */
+int edtr_cls_ce_forward(int logits_dtype, const void* logits, const int32_t* labels, int B, int C, int ignore_index, float* lse,
+                        void* workspace, int64_t workspace_bytes, float* loss, int64_t* counts, edtr_stream_t stream);
+int edtr_cls_ce_backward(int logits_dtype, const void* logits, const int32_t* labels, int B, int C, int ignore_index, const float* lse,
+                         const int64_t* counts, const float* grad_loss, void* grad, edtr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * hipGraph capture of a launch sequence issued on `stream` (one denoise step, or a whole batch).
  * ---------------------------------------------------------------------------------------- */
